@@ -8,17 +8,23 @@ smoothing -> chi^2) over the batch, theta already resident in HBM.  With --gpus 
 every rank fits its own synthetic star (weak scaling, no data-path collective);
 posterior-style summaries are all-gathered over RCCL once after the timed region.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--config C2|C3|C5|small] [--shard-batch]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--config C2|C3|C5|small] [--shard-batch] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...
 
 `python bench.py --gpus N` without a torchrun environment starts the N ranks itself (fresh child
 processes, before this process touches a GPU).  Prints ONE JSON line (rank 0).
 
-The headline is C2.  On one GPU the same line also carries, under `also_measured`, short runs of C3 (C2 + photometry in
-seven filters, the joint likelihood of SURVEY 8(d)) and C5 (65 536 pixels, 2048 candidates: the HBM-bound regime), each
-with its own kernel times and roofline block.  `--shard-batch` (N > 1) is SURVEY 8(e)-2: ONE star, every batch split
-in contiguous blocks over the ranks, the B log-likelihoods rebuilt on every rank by one all_gather per step
-(strong scaling; pays for C5-class batches).
+A plain run does what the headline needs and no more: set-up, W warm-up steps, ONE timed block of exactly K steps, the
+outputs of its last step (--dump-outputs DIR: DIR/lnl.npy), the line.  Its inputs are seeded: the same arguments give the
+same inputs whatever the build, so two builds can be compared output for output.
+
+--full adds everything else the benchmark measures: the headline timed as the median of at least 15 blocks of K steps
+(until 120 ms of timed work), the CPU baseline (the oracle in the reference's calling pattern), per-kernel device times
+with the roofline / HBM blocks, and on one GPU, under `also_measured`, short runs of C3 (C2 + photometry in seven
+filters, the joint likelihood of SURVEY 8(d)), C5 (65 536 pixels, 2048 candidates: the HBM-bound regime) and others, each
+with its own kernel times and roofline block, and the end-to-end sampler runs.  `--shard-batch` (N > 1) is SURVEY 8(e)-2:
+ONE star, every batch split in contiguous blocks over the ranks, the B log-likelihoods rebuilt on every rank by one
+all_gather per step (strong scaling; pays for C5-class batches).
 """
 import argparse
 import json
@@ -35,18 +41,25 @@ if ROOT not in sys.path:
 PEAK_BF16_TFLOPS = 2500.0      # dense bf16 MFMA (MI355X_MICROARCH.md)
 PEAK_FP32_TFLOPS = 157.3          # MI355X_MICROARCH.md: fp32 MFMA = packed-fp32 vector peak (spec)
 PEAK_HBM_GBS = 8000.0
+REPEATS_FULL, MIN_TIMED_MS_FULL = 15, 120.0      # --full's headline timing (a plain run: one block of --steps steps)
 
 
-def parse_args():
+def parse_args(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=200)
+    ap.add_argument("--steps", type=int, default=200, help="timed steps (a plain run times exactly this many, once)")
     ap.add_argument("--warmup", type=int, default=20)
     ap.add_argument("--config", default="C2")
     ap.add_argument("--batch", type=int, default=0)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-kernel-timing", action="store_true")
-    ap.add_argument("--no-e2e", action="store_true", help="skip the short nested-sampling run behind `end_to_end`")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beside the headline too: the headline as the median of --repeats blocks, the CPU baseline, "
+                         "per-kernel times with the roofline / HBM blocks, the `also_measured` configurations and `end_to_end`")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the timed path returned in its last timed step as DIR/<name>.npy (lnl.npy: the batch's "
+                         "log-likelihoods, float64; lnl_rank<r>.npy: rank r's, N > 1)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
+    ap.add_argument("--no-kernel-timing", action="store_true", help="--full: skip the per-kernel times and the roofline blocks")
+    ap.add_argument("--no-e2e", action="store_true", help="--full: skip the short nested-sampling run behind `end_to_end`")
     ap.add_argument("--unchecked", action="store_true", help="timing experiments with a deliberately incomplete library "
                     "(tools/exp/ablate.py): skip the result checks and mark the line invalid")
     ap.add_argument("--variant", type=int, default=0, help="payne_opts.variant (kernel variants of include/payne_hip.h; A/B runs)")
@@ -54,21 +67,28 @@ def parse_args():
                     help="independent batches in flight (one engine + HIP stream each); the headline uses 1")
     ap.add_argument("--shard-batch", action="store_true",
                     help="N > 1: one star, each batch split over the ranks, one all_gather of lnL per step (SURVEY 8(e)-2)")
-    ap.add_argument("--no-also", action="store_true", help="skip the `also_measured` runs (C3, C5) behind the C2 headline")
+    ap.add_argument("--no-also", action="store_true", help="--full: skip the `also_measured` runs (C3, C5) behind the C2 headline")
     ap.add_argument("--e2e-calls", type=int, default=700000,
                     help="likelihood calls per end-to-end sampler run (three runs; a C2 run converges -- nothing left of the evidence at "
                          "dlogz = 1e-9 -- after ~727 k calls, so longer runs do not exist)")
-    ap.add_argument("--repeats", type=int, default=15,
+    ap.add_argument("--repeats", type=int, default=None,
                     help="the block of --steps steps is timed this many times back to back (each between barriers); the MEDIAN "
-                         "block is the headline, min / max ride along: a 20-step block is 0.8 ms, one clock ramp moved it 3 %%")
-    ap.add_argument("--min-timed-ms", type=float, default=120.0,
+                         "block is the headline, min / max ride along: a 20-step block is 0.8 ms, one clock ramp moved it 3 %%.  "
+                         + "Default 1, %d with --full" % REPEATS_FULL)
+    ap.add_argument("--min-timed-ms", type=float, default=None,
                     help="keep timing blocks (beyond --repeats) until this much timed work has been done: an MI355X that was idle takes "
                          "15-20 ms of work to reach its clocks (tools/exp/block_ramp.py: a 20-step block 30.7 us a step in the first 9 ms, "
-                         "28.9 from 20 ms on), and --steps 20 --repeats 15 is 9 ms in all; 0: exactly --repeats blocks")
+                         "28.9 from 20 ms on), and --steps 20 --repeats 15 is 9 ms in all; 0: exactly --repeats blocks.  "
+                         + "Default 0, %g with --full" % MIN_TIMED_MS_FULL)
     ap.add_argument("--force-dist", action="store_true",
                     help="one rank, but through a torch.distributed process group (RCCL, world size 1): the collectives of "
                          "the N > 1 path on a one-GPU box (tests/test_rccl_world1_gpu.py)")
-    return ap.parse_args()
+    args = ap.parse_args(argv)
+    if args.repeats is None:
+        args.repeats = REPEATS_FULL if args.full else 1
+    if args.min_timed_ms is None:
+        args.min_timed_ms = MIN_TIMED_MS_FULL if args.full else 0.0
+    return args
 
 
 # ----------------------------------------------------------------------------
@@ -212,6 +232,7 @@ def make_problem(cfg_name, B, rank, local_rank, variant=0, streams=1):
     """Engines (one per batch in flight) + resident theta / lnL for config `cfg_name`; star seed = rank."""
     import numpy as np
     import torch
+    import oracle as O
     from thepayne_amd import nnio, synth
     from thepayne_amd.engine import PayneEngine
     cfg = dict(synth.CONFIGS["C2" if cfg_name == "LinNet300" else cfg_name])
@@ -222,15 +243,14 @@ def make_problem(cfg_name, B, rank, local_rank, variant=0, streams=1):
         raw = synth.make_yst_net(npix=cfg["npix"], lam0=cfg["lam0"], R_fwhm=cfg["R"], seed=0)
         net = nnio.normalize_spec_net(raw)
     obs = synth.obs_grid(raw["wavelength"], cfg["nobs"])
-    eng0 = PayneEngine(net, obs=(obs,), b_max=1, device=local_rank)
+    # the observed spectrum: the truth through the host oracle (fp64 numpy) + seeded noise, so that the inputs do not depend on
+    # the build being measured and two builds' outputs (--dump-outputs) can be compared one for one
     T = synth.TRUTH
     rng = np.random.default_rng(rank)
-    truth = np.full((1, eng0.ncols), np.nan)
-    truth[0, :8] = [T["Teff"] + 20.0 * rank, T["logg"], T["feh"], T["afe"], T["vrad"], T["vrot"], np.nan, T["inst_R"]]
-    clean = eng0.predict_batch(truth, stage=2, fwhm_R=True).cpu().numpy()[0].astype(np.float64)
+    _, clean = O.getspec(raw, Teff=T["Teff"] + 20.0 * rank, logg=T["logg"], feh=T["feh"], afe=T["afe"], rad_vel=T["vrad"],
+                         rot_vel=T["vrot"], vmic=np.nan, inst_R=2.355 * T["inst_R"], outwave=obs)
     flux = clean + rng.normal(0, 0.01, len(obs))
     eflux = np.full(len(obs), 0.01)
-    eng0.close()
     kw = {}
     phot = None
     if cfg.get("phot"):                       # C3: + seven filters, photscale parametrisation
@@ -359,13 +379,14 @@ def run_config(cfg_name, args, steps, warmup, rank, world, local_rank, B=0, stre
     dt_wall = sorted(blocks_wall)[len(blocks_wall) // 2]
     if shard and world > 1:
         lnl = sb.result()
+    outputs = {"lnl": lnl.cpu().numpy().copy()}      # what the caller of the timed path received from its last timed step
     for l_ in lnls[1:]:                  # every in-flight batch evaluated the same candidates: same answers
         assert args.unchecked or bool(torch.equal(torch.nan_to_num(l_), torch.nan_to_num(lnl)))
     assert args.unchecked or int(torch.isfinite(lnl).sum()) >= B - max(4, B // 128), \
         "non-finite lnL in the benchmark batch"   # Inst_R tail draws are NaN by contract
 
     kern = None
-    if not args.no_kernel_timing and not (shard and world > 1):
+    if args.full and not args.no_kernel_timing and not (shard and world > 1):
         # per-kernel device time (HIP events attached to the launches, on the launch stream), same steps replayed
         eng.profile(True)
         for _ in range(max(steps, 100) if min_timed_s > 0 and dt / steps < 2e-4 else steps):   # (short steps: at least a hundred launches a kernel)
@@ -374,8 +395,18 @@ def run_config(cfg_name, args, steps, warmup, rank, world, local_rank, B=0, stre
         kern = eng.profile_read()
         eng.profile(False)
     res = dict(P, dt=dt, dt_local=dt_local, dt_wall=dt_wall, timed_by=("hip-events" if use_events else "host-clock"), blocks=blocks, steps=steps, warmup=warmup, B=B, S=S, kern=kern, lnl=lnl, shard=bool(shard and world > 1),
-               evals=(B * steps if shard else world * B * steps))
+               evals=(B * steps if shard else world * B * steps), outputs=outputs)
     return res
+
+
+def dump_outputs(dirname, arrays, rank=0):
+    """--dump-outputs: each array as DIR/<name>.npy (float32 / float64 only; rank r > 0 adds _rank<r> to the name)."""
+    import numpy as np
+    os.makedirs(dirname, exist_ok=True)
+    for name, a in arrays.items():
+        a = np.ascontiguousarray(a)
+        assert a.dtype in (np.float32, np.float64), (name, a.dtype)
+        np.save(os.path.join(dirname, (name if rank == 0 else "%s_rank%d" % (name, rank)) + ".npy"), a)
 
 
 def roofline_blocks(cfg_name, res, args):
@@ -687,7 +718,7 @@ def main():
         raise SystemExit("--gpus %d but WORLD_SIZE=%d" % (args.gpus, world))
 
     cpu = cpu_c3 = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         cpu = cpu_baseline("C2" if args.config == "LinNet300" else args.config)
         if args.config == "C2" and not args.no_also:
             cpu_c3 = cpu_baseline("C3", budgets=(6.0, 0.0))   # the joint likelihood's baseline (the reference itself: 212 evals/s/core)
@@ -711,6 +742,8 @@ def main():
     res = run_config(args.config, args, args.steps, args.warmup, rank, world, local_rank, B=args.batch,
                      streams=args.streams, shard=args.shard_batch, repeats=args.repeats, min_timed_s=1e-3 * args.min_timed_ms)
     B, d, lnl, theta = res["B"], res["dims"], res["lnl"], res["theta"]
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, res["outputs"], rank)
 
     # ---- the one collective of the multi-star job: gather per-star summaries (RCCL)
     summary = torch.stack([lnl.max(), lnl.mean(), lnl.std(), theta[lnl.argmax(), 0], theta[lnl.argmax(), 1],
@@ -737,12 +770,13 @@ def main():
         "ms_per_step_max": 1e3 * max(res["blocks"]) / args.steps,
         "ms_per_step_first15": 1e3 * sorted(res["blocks"][:15])[len(res["blocks"][:15]) // 2] / args.steps,
         "ms_per_step_wall": 1e3 * res["dt_wall"] / args.steps,
-        "timing": ("median of `repeats` blocks of `steps` steps (at least --repeats of them, and blocks until --min-timed-ms of timed work: "
-                   "`ms_per_step_first15` is the median of the first fifteen, which an idle GPU's clock ramp covers when blocks are short), MAX over ranks; every block sits between barrier + synchronize on both "
-                   "sides and is timed by a HIP event pair on the launch stream around its steps (`value`, `ms_per_step`) and by the host "
-                   "clock between the barriers (`ms_per_step_wall`: + ~55 us of synchronize / barrier edges per block)")
-                  if res["timed_by"] == "hip-events" else
-                  "median of `repeats` blocks of `steps` steps, each block between barrier + synchronize (host clock), MAX over ranks",
+        "timing": ("one block of exactly `steps` steps after `warmup` warm-up steps (a plain run's timing) -- " if len(res["blocks"]) == 1 else "") +
+                  (("median of `repeats` blocks of `steps` steps (at least --repeats of them, and blocks until --min-timed-ms of timed work: "
+                    "`ms_per_step_first15` is the median of the first fifteen, which an idle GPU's clock ramp covers when blocks are short), MAX over ranks; every block sits between barrier + synchronize on both "
+                    "sides and is timed by a HIP event pair on the launch stream around its steps (`value`, `ms_per_step`) and by the host "
+                    "clock between the barriers (`ms_per_step_wall`: + ~55 us of synchronize / barrier edges per block)")
+                   if res["timed_by"] == "hip-events" else
+                   "median of `repeats` blocks of `steps` steps, each block between barrier + synchronize (host clock), MAX over ranks"),
         "higher_is_better": True, "scaling": "strong" if res["shard"] else "weak", "vs_baseline": None,
         "dtype": "f32", "data": "synthetic",
         "config": {"workload": workload_text(args.config, d),
@@ -771,7 +805,7 @@ def main():
     res = None
     torch.cuda.empty_cache()
 
-    if world == 1 and not args.no_also and args.config == "C2" and not args.batch and args.streams == 1:
+    if args.full and world == 1 and not args.no_also and args.config == "C2" and not args.batch and args.streams == 1:
         # the configurations the headline does not show: short runs, same code path, own kernel times and roofline blocks
         also = {}
         # C2r: C2 on a model grid that is NOT a power of two long (3600 pixels of the same lambda_0 and R, 3200 observed pixels):
@@ -798,7 +832,7 @@ def main():
             torch.cuda.empty_cache()
         out["also_measured"] = also
 
-    if world == 1 and not args.no_e2e and B <= 4096 and d["N"] <= 16384:
+    if args.full and world == 1 and not args.no_e2e and B <= 4096 and d["N"] <= 16384:
         out["end_to_end"] = end_to_end(args.config, B, out["value"], args.e2e_calls, cpu=cpu)
         if args.config == "C2" and "also_measured" in out and "value" in out["also_measured"].get("C3", {}):
             try:

@@ -1,8 +1,9 @@
 """CPU oracle for the ThePayne nested-sampling likelihood hot path.
 
 TEST INFRASTRUCTURE ONLY.  Nothing under ``thepayne_amd/`` may import this
-package; only ``tests/``, ``__graft_entry__.smoke()`` and the ``cpu_baseline``
-leg of ``bench.py`` do, and there only as the checker / the timed CPU baseline.
+package; only ``tests/``, ``__graft_entry__.smoke()`` and ``bench.py`` do, and
+there only as the checker, the maker of ``bench.py``'s observed spectra (before
+the timed steps) and the timed CPU baseline.
 
 What it is: a plain numpy (fp64) restatement of the reference's algorithm for
 the path ``lnprobfn -> likelihood.lnlikefn -> lnlike -> GenMod.genspec ->

@@ -383,3 +383,35 @@ def test_bench_times_blocks_until_the_clock_ramp_is_behind():
         blocks.append(1e-9)
     assert len(blocks) == 50
 
+
+def test_bench_plain_run_times_its_steps_once():
+    """A plain `bench.py --steps N` times ONE block of exactly N steps and measures nothing beside the headline; --full brings back
+    the median of at least 15 blocks until 120 ms of timed work, and explicit --repeats / --min-timed-ms still win."""
+    import bench
+    a = bench.parse_args(["--gpus", "1", "--steps", "37", "--warmup", "3"])
+    assert not a.full and a.steps == 37 and a.warmup == 3 and a.repeats == 1 and a.min_timed_ms == 0.0 and a.dump_outputs is None
+    blocks = []
+    while bench.more_blocks(blocks, a.repeats, 1e-3 * a.min_timed_ms):
+        blocks.append(37 * 29e-6)
+    assert len(blocks) == 1
+    f = bench.parse_args(["--full", "--steps", "20"])
+    assert f.full and f.repeats == 15 and f.min_timed_ms == 120.0
+    g = bench.parse_args(["--full", "--repeats", "3", "--min-timed-ms", "0", "--dump-outputs", "out"])
+    assert g.repeats == 3 and g.min_timed_ms == 0.0 and g.dump_outputs == "out"
+
+
+def test_bench_dump_outputs_writes_float_arrays(tmp_path):
+    """--dump-outputs: DIR/<name>.npy as handed over (float32 / float64 only, NaN kept); rank r > 0 names its files _rank<r>."""
+    import bench
+    lnl = np.linspace(-3.0, 1.0, 7)
+    lnl[2] = np.nan
+    d = tmp_path / "out"
+    bench.dump_outputs(str(d), {"lnl": lnl})
+    bench.dump_outputs(str(d), {"lnl": lnl.astype(np.float32)}, rank=2)
+    got = np.load(d / "lnl.npy")
+    assert got.dtype == np.float64 and np.array_equal(got, lnl, equal_nan=True)
+    got2 = np.load(d / "lnl_rank2.npy")
+    assert got2.dtype == np.float32 and np.array_equal(got2, lnl.astype(np.float32), equal_nan=True)
+    with pytest.raises(AssertionError):
+        bench.dump_outputs(str(d), {"counts": np.arange(3)})
+

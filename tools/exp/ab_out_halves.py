@@ -23,7 +23,7 @@ print("lnL equal to the bit:", np.array_equal(np.nan_to_num(a[0]), np.nan_to_num
       " max |d rows|", float(np.abs(a[1] - b[1]).max()))
 for rep in range(int(os.environ.get("REPS", "4"))):
     for name, v, parts in (("halves", 0, "2"), ("whole", _lib.V_OUT_WHOLE_TILE, "2")):       # (("3 parts", 0, "3"): with tools/exp/out_three_parts.patch applied)
-        res = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "300", "--warmup", "30", "--no-cpu-baseline", "--no-e2e", "--no-also",
+        res = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--steps", "300", "--warmup", "30", "--no-cpu-baseline", "--no-e2e", "--no-also",
                               "--variant", str(v)], capture_output=True, text=True, env=dict(os.environ, PAYNE_OUT_PARTS=parts))
         try:
             d = json.loads(res.stdout.strip().splitlines()[-1])

@@ -18,7 +18,7 @@ libs = {b: (build.build_variant("st%d" % b, ["-DPAYNE_EXP_ST=%d" % b]) if b else
 for rep in range(int(os.environ.get("REPS", "2"))):
     for b in which:
         env = dict(os.environ, PAYNE_HIP_LIB=libs[b])
-        res = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "300", "--warmup", "30", "--no-cpu-baseline", "--no-e2e",
+        res = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--steps", "300", "--warmup", "30", "--no-cpu-baseline", "--no-e2e",
                               "--no-also"], env=env, capture_output=True, text=True)
         try:
             d = json.loads(res.stdout.strip().splitlines()[-1])

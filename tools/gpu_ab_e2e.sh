@@ -6,7 +6,7 @@ CFG=${1:-C2}; REP=${2:-2}
 OLD=$PWD/thepayne_amd/build/old/libpayne_hip_head.so
 mkdir -p gpurun_out
 one() {
-  python bench.py --config $CFG --steps 200 --warmup 30 --no-cpu-baseline --no-also 2>/dev/null | python -c "
+  python bench.py --full --config $CFG --steps 200 --warmup 30 --no-cpu-baseline --no-also 2>/dev/null | python -c "
 import json,sys; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); e=d.get('end_to_end',{}); print('$1', '$CFG', round(d['value']), 'evals/s kernel-only;', 'e2e', e.get('value'), e.get('frac_of_kernel_only'), e.get('runs'))"
 }
 for i in $(seq $REP); do
