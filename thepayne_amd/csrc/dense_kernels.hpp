@@ -587,22 +587,10 @@ __global__ void __launch_bounds__(256) payne_split2h_kernel(const float* __restr
 // as long as its six matrix instructions per wave at KD = 32).  A 1-KiB piece = 1024 / (2 KD) rows of one plane; 16-byte chunk c of
 // tile row r sits at chunk c ^ sw(r), sw = (r >> 2) & 3 for 64-byte rows, (r >> 1) & 7 for 128-byte rows: the sixteen lanes of
 // every lane group of a fragment read (ds_read_b128) cover sixteen different 16-byte bank groups.
-// The rows' stores: streamed (nt) -- the next reader is the post kernel, on other XCDs.  (PAYNE_EXP_ST: timing twins of other cache
-// policies, tools/exp/store_policy.py: 1 plain, 2 sc1, 3 sc0 sc1, 4 sc1 nt, 5 sc0 nt.)
+// The rows' stores: streamed (nt) -- the next reader is the post kernel, on other XCDs.  (The other cache policies -- plain, sc1,
+// sc0 sc1, sc1 nt, sc0 nt -- measured: NOTES R6.9.)
 __device__ __forceinline__ void d2_store_row(float* q, float v) {
-#if defined(PAYNE_EXP_ST) && PAYNE_EXP_ST == 1
-  *q = v;
-#elif defined(PAYNE_EXP_ST) && PAYNE_EXP_ST == 2
-  asm volatile("global_store_dword %0, %1, off sc1" :: "v"(q), "v"(v) : "memory");
-#elif defined(PAYNE_EXP_ST) && PAYNE_EXP_ST == 3
-  asm volatile("global_store_dword %0, %1, off sc0 sc1" :: "v"(q), "v"(v) : "memory");
-#elif defined(PAYNE_EXP_ST) && PAYNE_EXP_ST == 4
-  asm volatile("global_store_dword %0, %1, off sc1 nt" :: "v"(q), "v"(v) : "memory");
-#elif defined(PAYNE_EXP_ST) && PAYNE_EXP_ST == 5
-  asm volatile("global_store_dword %0, %1, off sc0 nt" :: "v"(q), "v"(v) : "memory");
-#else
   __builtin_nontemporal_store(v, q);
-#endif
 }
 template <int KD> constexpr int d2_stage() { return 2 * (64 + 128) * 2 * KD; }
 template <int KD> constexpr int d2_ns() { return KD == 64 ? 3 : 4; }
@@ -658,9 +646,6 @@ __global__ void __launch_bounds__(512) payne_dense_dma2h_kernel(PAYNE_D3_LEAD_PA
                    : reinterpret_cast<const unsigned char*>(p.Wp) + 2 * (size_t)pl * p.plane_w;
     voff[j] = (unsigned)r * (isA ? pitch_a : pitch_b) + 16u * (unsigned)c;
     dst[j] = isA ? pl * A_PLANE + blk * 1024 : 2 * A_PLANE + pl * B_PLANE + blk * 1024;
-#if defined(PAYNE_EXP_D2H) && (PAYNE_EXP_D2H & 1)       /* timing twin (tools/exp/d2h_ablate_time.py): every piece comes from ONE kilobyte (no L2 traffic to speak of) */
-    sbase[j] = reinterpret_cast<const unsigned char*>(p.Xp); voff[j] = 16u * (unsigned)lane;
-#endif
   }
   auto issue = [&](int stage, int k0) {                    // k0 in elements (2 bytes each)
 #pragma unroll
@@ -693,13 +678,9 @@ __global__ void __launch_bounds__(512) payne_dense_dma2h_kernel(PAYNE_D3_LEAD_PA
     }
   };
   auto products = [&](const Frag& f, int ks) {             // smallest partial products first
-#if defined(PAYNE_EXP_D2H) && (PAYNE_EXP_D2H & 2)       /* timing twin: one of the three products */
-    acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(f.a[ks][0] + f.a[ks][1], f.b[ks][0] + f.b[ks][1], acc, 0, 0, 0);
-#else
     acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(f.a[ks][1], f.b[ks][0], acc, 0, 0, 0);
     acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(f.a[ks][0], f.b[ks][1], acc, 0, 0, 0);
     acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(f.a[ks][0], f.b[ks][0], acc, 0, 0, 0);
-#endif
   };
   const int nk = NK > 0 ? NK : p.K / KD;                   // padded: exact
   const int k_tail = (p.k_real > 0 ? p.k_real : p.K) - (nk - 1) * KD;
@@ -757,9 +738,6 @@ __global__ void __launch_bounds__(512) payne_dense_dma2h_kernel(PAYNE_D3_LEAD_PA
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
         const unsigned char* rowp = yb + (size_t)((r & 3) + 8 * (r >> 2)) * p.ldy * 4;
-#if defined(PAYNE_EXP_D2H) && (PAYNE_EXP_D2H & 4)       /* timing twin: (practically) no stores */
-        if (!(acc[r] == 12345.678f)) continue;
-#endif
         d2_store_row(reinterpret_cast<float*>(const_cast<unsigned char*>(rowp + voff)), __builtin_fmaf(acc[r], rs, bv));
       }
     } else if (act_none) {
@@ -786,10 +764,6 @@ __global__ void __launch_bounds__(512) payne_dense_dma2h_kernel(PAYNE_D3_LEAD_PA
     head(it + 1, f0, f1);
     all_products(f1);
     __builtin_amdgcn_sched_barrier(0);
-#if defined(PAYNE_EXP_D2H) && (PAYNE_EXP_D2H & 24)      /* timing twins: half of the waves store in the middle of the k-loop and leave (what a tile finished in two
-                                                           halves would do; their later operand pieces are not requested: an upper bound) -- 8: after two stages of five, 16: after four */
-    if (it == ((PAYNE_EXP_D2H & 8) ? 0 : 2) && wave < 4) { epilogue(); return; }
-#endif
   }
   if (it + 1 < nk) {
     head(it, f1, f0);
@@ -1254,14 +1228,8 @@ __global__ void __launch_bounds__(512) payne_dense_dma3f_kernel(PAYNE_D3_LEAD_PA
   auto issueB = [&](BRegs& b, auto K0) {
     constexpr int off = decltype(K0)::value * 4;
     const float* s0_ = srcB0; const float* s1_ = srcB1;
-#if defined(PAYNE_EXP_D3F) && (PAYNE_EXP_D3F & 4)       /* timing twin: the weights' loads hit one line (no port traffic to speak of) */
-    const float* w_ = p_.bias;
-    asm volatile("global_load_dwordx4 %0, %2, off nt\n\tglobal_load_dwordx4 %1, %2, off nt"
-                 : "=&v"(b.lo), "=&v"(b.hi) : "v"(w_), "v"(s1_), "n"(off) : "memory");
-#else
     asm volatile("global_load_dwordx4 %0, %2, off offset:%4 nt\n\tglobal_load_dwordx4 %1, %3, off offset:%4 nt"
                  : "=&v"(b.lo), "=&v"(b.hi) : "v"(s0_), "v"(s1_), "n"(off) : "memory");
-#endif
   };
   auto landed = [&](BRegs& b) { asm volatile("" : "+v"(b.lo), "+v"(b.hi)); };
   // (pairs: one v_cvt_pk_bf16_f32 rounds two values and leaves them packed as the plane wants them; what it rounded away, exactly:
@@ -1280,12 +1248,8 @@ __global__ void __launch_bounds__(512) payne_dense_dma3f_kernel(PAYNE_D3_LEAD_PA
   typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
   auto splitB = [&](const BRegs& b, int stage) {
     unsigned ph[4], pm[4], pl[4];
-#if defined(PAYNE_EXP_D3F) && (PAYNE_EXP_D3F & 1)       /* timing twin (tools/exp/d3f_ablate.py): no split arithmetic */
-    for (int j = 0; j < 4; ++j) { ph[j] = __builtin_bit_cast(unsigned, j < 2 ? b.lo[j] : b.hi[j]); pm[j] = ph[j]; pl[j] = ph[j]; }
-#else
     split_pair(b.lo[0], b.lo[1], ph[0], pm[0], pl[0]); split_pair(b.lo[2], b.lo[3], ph[1], pm[1], pl[1]);
     split_pair(b.hi[0], b.hi[1], ph[2], pm[2], pl[2]); split_pair(b.hi[2], b.hi[3], ph[3], pm[3], pl[3]);
-#endif
     unsigned char* B0 = d3_sm + stage * D3_STAGE + dstB0;
     unsigned char* B1 = d3_sm + stage * D3_STAGE + dstB1;
     *reinterpret_cast<u32x2*>(B0) = u32x2{ph[0], ph[1]}; *reinterpret_cast<u32x2*>(B0 + 8192) = u32x2{pm[0], pm[1]};
@@ -1316,11 +1280,9 @@ __global__ void __launch_bounds__(512) payne_dense_dma3f_kernel(PAYNE_D3_LEAD_PA
     acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(f.a[ks][2], f.b[ks][0], acc, 0, 0, 0);
     acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(f.a[ks][1], f.b[ks][1], acc, 0, 0, 0);
     acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(f.a[ks][0], f.b[ks][2], acc, 0, 0, 0);
-#if !(defined(PAYNE_EXP_D3F) && (PAYNE_EXP_D3F & 2))    /* timing twin: three of the six products */
     acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(f.a[ks][1], f.b[ks][0], acc, 0, 0, 0);
     acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(f.a[ks][0], f.b[ks][1], acc, 0, 0, 0);
     acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(f.a[ks][0], f.b[ks][0], acc, 0, 0, 0);
-#endif
   };
   constexpr int nk = NK;
   const int k_tail = (p.k_real > 0 ? p.k_real : p.K) - (nk - 1) * 32;
@@ -2457,31 +2419,43 @@ __global__ void __launch_bounds__(256, 1) payne_dense_chain_kernel(const ChainPa
 }
 #endif
 
-// The instantiations that exist (compiled in k_dense.hip; `extern template` elsewhere).
+// The dense kernels that exist, each with the dynamic LDS it is launched with: T(kernel, parameter types, LDS bytes) for an instantiation
+// of a template (compiled in k_dense.hip; `extern template` elsewhere), F(kernel, LDS bytes) for a plain function.  The instantiations
+// below, set_dense_attributes() and every launch (DenseLds<kernel>::value) come from this list: a kernel that is not on it does not compile.
+#define PAYNE_DENSE_KERNELS(T, F)                                                                                                 \
+  T((payne_dense_kernel<64, 64, 32, true>), (DenseParams), dense_lds_bytes<64, 64, 32>())                                          \
+  T((payne_dense_kernel<64, 64, 32, false>), (DenseParams), dense_lds_bytes<64, 64, 32>())                                         \
+  T((payne_dense_dma_kernel<4, 32, 0, 4, true>), (DenseParams), dm_lds_bytes<4, 32, 4>())                                          \
+  T((payne_dense_dma_kernel<4, 32, 10, 4, true>), (DenseParams), dm_lds_bytes<4, 32, 4>())                                         \
+  T((payne_dense_dma_kernel<4, 32, 0, 3, false>), (DenseParams), dm_lds_bytes<4, 32, 3>())                                         \
+  T((payne_dense_dma_kernel<4, 64, 0, 3, true>), (DenseParams), dm_lds_bytes<4, 64, 3>())                                          \
+  T((payne_dense_dma_kernel<4, 64, 5, 3, true>), (DenseParams), dm_lds_bytes<4, 64, 3>())                                          \
+  T((payne_dense_dma3_kernel<0, 4, true>), (PAYNE_D3_LEAD_TYPES, DenseParams), d3_lds_bytes<4>())                                  \
+  T((payne_dense_dma3_kernel<10, 4, true>), (PAYNE_D3_LEAD_TYPES, DenseParams), d3_lds_bytes<4>())                                 \
+  T((payne_dense_dma3_kernel<0, 2, false>), (PAYNE_D3_LEAD_TYPES, DenseParams), d3_lds_bytes<2>())                                 \
+  T((payne_dense_dma3f_kernel<10>), (PAYNE_D3_LEAD_TYPES, DenseParams), d3_lds_bytes<4>())                                         \
+  T((payne_dense_dma2h_kernel<10, 32>), (PAYNE_D3_LEAD_TYPES, DenseParams), d2_lds_bytes<32>())                                    \
+  T((payne_dense_dma2h_kernel<0, 32>), (PAYNE_D3_LEAD_TYPES, DenseParams), d2_lds_bytes<32>())                                     \
+  T((payne_dense_dma2h_kernel<5, 64>), (PAYNE_D3_LEAD_TYPES, DenseParams), d2_lds_bytes<64>())                                     \
+  T((payne_dense_big3_kernel<false>), (DenseParams), b3_lds_bytes(false))                                                          \
+  T((payne_dense_big3_kernel<true>), (DenseParams), b3_lds_bytes(true))                                                            \
+  T((payne_dense_dma2hh_kernel<5>), (PAYNE_D3_LEAD_TYPES, DenseParams), d2hh_lds_bytes<5>())                                       \
+  F(payne_dense_chain_kernel, HK_LDS_BYTES)                                                                                        \
+  T((payne_dense_hidden_kernel<true, 4>), (PAYNE_HK_LEAD_TYPES, DenseParams, const PrepArgs), HK_LDS_BYTES)                        \
+  T((payne_dense_hidden_kernel<true, PAYNE_MAX_LABELS>), (PAYNE_HK_LEAD_TYPES, DenseParams, const PrepArgs), HK_LDS_BYTES)         \
+  T((payne_dense_hidden_kernel<false, 4>), (PAYNE_HK_LEAD_TYPES, DenseParams, const PrepArgs), HK_LDS_BYTES)                       \
+  T((payne_dense_hidden_kernel<true, 4, 8>), (PAYNE_HK_LEAD_TYPES, DenseParams, const PrepArgs), HK_LDS_BYTES)                     \
+  T((payne_dense_hidden_kernel<true, PAYNE_MAX_LABELS, 8>), (PAYNE_HK_LEAD_TYPES, DenseParams, const PrepArgs), HK_LDS_BYTES)
+#define PAYNE_UNPAREN(...) __VA_ARGS__
 #ifdef PAYNE_TU_DENSE
 #define PAYNE_DENSE_T template
 #else
 #define PAYNE_DENSE_T extern template
 #endif
-PAYNE_DENSE_T __global__ void payne_dense_kernel<64, 64, 32, true>(DenseParams);
-PAYNE_DENSE_T __global__ void payne_dense_kernel<64, 64, 32, false>(DenseParams);
-PAYNE_DENSE_T __global__ void payne_dense_dma_kernel<4, 32, 0, 4, true>(DenseParams);
-PAYNE_DENSE_T __global__ void payne_dense_dma_kernel<4, 32, 10, 4, true>(DenseParams);
-PAYNE_DENSE_T __global__ void payne_dense_dma_kernel<4, 32, 0, 3, false>(DenseParams);
-PAYNE_DENSE_T __global__ void payne_dense_dma_kernel<4, 64, 0, 3, true>(DenseParams);
-PAYNE_DENSE_T __global__ void payne_dense_dma_kernel<4, 64, 5, 3, true>(DenseParams);
-PAYNE_DENSE_T __global__ void payne_dense_dma3_kernel<0, 4, true>(PAYNE_D3_LEAD_TYPES, DenseParams);
-PAYNE_DENSE_T __global__ void payne_dense_dma3_kernel<10, 4, true>(PAYNE_D3_LEAD_TYPES, DenseParams);
-PAYNE_DENSE_T __global__ void payne_dense_dma3_kernel<0, 2, false>(PAYNE_D3_LEAD_TYPES, DenseParams);
-PAYNE_DENSE_T __global__ void payne_dense_dma3f_kernel<10>(PAYNE_D3_LEAD_TYPES, DenseParams);
-PAYNE_DENSE_T __global__ void payne_dense_dma2h_kernel<10, 32>(PAYNE_D3_LEAD_TYPES, DenseParams);
-PAYNE_DENSE_T __global__ void payne_dense_dma2h_kernel<0, 32>(PAYNE_D3_LEAD_TYPES, DenseParams);
-PAYNE_DENSE_T __global__ void payne_dense_dma2h_kernel<5, 64>(PAYNE_D3_LEAD_TYPES, DenseParams);
-PAYNE_DENSE_T __global__ void payne_dense_big3_kernel<false>(DenseParams);
-PAYNE_DENSE_T __global__ void payne_dense_big3_kernel<true>(DenseParams);
-PAYNE_DENSE_T __global__ void payne_dense_dma2hh_kernel<5>(PAYNE_D3_LEAD_TYPES, DenseParams);
-PAYNE_DENSE_T __global__ void payne_dense_hidden_kernel<true, 4>(PAYNE_HK_LEAD_TYPES, DenseParams, const PrepArgs);
-PAYNE_DENSE_T __global__ void payne_dense_hidden_kernel<true, PAYNE_MAX_LABELS>(PAYNE_HK_LEAD_TYPES, DenseParams, const PrepArgs);
-PAYNE_DENSE_T __global__ void payne_dense_hidden_kernel<false, 4>(PAYNE_HK_LEAD_TYPES, DenseParams, const PrepArgs);
-PAYNE_DENSE_T __global__ void payne_dense_hidden_kernel<true, 4, 8>(PAYNE_HK_LEAD_TYPES, DenseParams, const PrepArgs);
-PAYNE_DENSE_T __global__ void payne_dense_hidden_kernel<true, PAYNE_MAX_LABELS, 8>(PAYNE_HK_LEAD_TYPES, DenseParams, const PrepArgs);
+#define PAYNE_DENSE_INST(K, ARGS, ...) PAYNE_DENSE_T __global__ void PAYNE_UNPAREN K ARGS;
+#define PAYNE_DENSE_NONE(K, ...)
+PAYNE_DENSE_KERNELS(PAYNE_DENSE_INST, PAYNE_DENSE_NONE)
+template <auto K> struct DenseLds;
+#define PAYNE_DENSE_LDS_T(K, ARGS, ...) template <> struct DenseLds<PAYNE_UNPAREN K> { static constexpr size_t value = __VA_ARGS__; };
+#define PAYNE_DENSE_LDS_F(K, ...) template <> struct DenseLds<K> { static constexpr size_t value = __VA_ARGS__; };
+PAYNE_DENSE_KERNELS(PAYNE_DENSE_LDS_T, PAYNE_DENSE_LDS_F)

@@ -178,10 +178,13 @@ struct ProfScope {
   }
 };
 #include <hip/hip_ext.h>
-#define PAYNE_LAUNCH(kernel, grid, block, lds, stream, ...)                                               \
+#define PAYNE_LAUNCH(kernel, grid, block, lds, stream, ...) PAYNE_LAUNCH_AS(#kernel, kernel, grid, block, lds, stream, __VA_ARGS__)
+// (a dense kernel: its dynamic LDS is the one the list in dense_kernels.hpp gives it)
+#define PAYNE_LAUNCH_DENSE(kernel, grid, block, stream, ...) PAYNE_LAUNCH_AS(#kernel, kernel, grid, block, DenseLds<kernel>::value, stream, __VA_ARGS__)
+#define PAYNE_LAUNCH_AS(name, kernel, grid, block, lds, stream, ...)                                      \
   do {                                                                                                    \
     ProfScope* ps_ = g_prof_scope;                                                                        \
-    if (ps_) ps_->c->last_kernel[ps_->kind] = #kernel;                                                    \
+    if (ps_) ps_->c->last_kernel[ps_->kind] = name;                                                       \
     if (ps_ && ps_->r && !ps_->used) {                                                                    \
       ps_->used = true;                                                                                   \
       hipExtLaunchKernelGGL(kernel, grid, block, (std::uint32_t)(lds), stream, ps_->r->e0, ps_->r->e1, 0, __VA_ARGS__); \
@@ -381,6 +384,200 @@ static int make_h2_planes(payne_ctx* c, const float* d_w, const std::vector<floa
   return PAYNE_OK;
 }
 
+// Which kernel the output layer gets: decided by plan_out (below run_net's NetRef) and by nothing else.  The forms, each falling
+// back to the one before it: the generic tile kernel | fp32 operands by LDS-DMA | three bf16 planes an operand, six products
+// (equal hidden widths) | two fp16 planes, three products (activations calibrated on the label box).
+enum class OutForm { Generic, F32Dma, Bf16x3, H2 };
+// What the variant bits ask for; payne_ctx_create builds the fp16 planes for OutForm::H2 only.
+static OutForm wanted_out_form(unsigned variant) {
+  if (variant & PAYNE_V_OUT_GENERIC) return OutForm::Generic;
+  if (variant & (PAYNE_V_OUT_F32 | PAYNE_V_OUT_BK64)) return OutForm::F32Dma;
+  if (variant & (PAYNE_V_OUT_BF16X3 | PAYNE_V_OUT_PLANES)) return OutForm::Bf16x3;
+  return OutForm::H2;
+}
+// The power of two a layer's activations are written with as fp16 pairs: their largest magnitude on the label box lands in
+// [2048, 4096] (a factor of 8 to spare below fp16's range); 0 where the calibration found nothing usable.
+static float h2_act_scale(double amax) {
+  if (!(amax > 0.0 && amax < 1e30)) return 0.f;
+  return (float)std::ldexp(1.0, std::max(-60, std::min(60, (int)std::floor(std::log2(4096.0 / amax)))));
+}
+// A layer's weights (device, [n][k]) as fp16-pair planes [n][kp], rows zero-padded to kp columns, for activations written at `scale`.
+static int layer_h2_planes(payne_ctx* c, const float* d_w, int n, int k, int kp, float scale, const char* what,
+                           unsigned short** planes, const float** rscale) {
+  std::vector<float> h((size_t)n * k);
+  const hipError_t he = hipMemcpy(h.data(), d_w, h.size() * 4, hipMemcpyDeviceToHost);
+  if (he != hipSuccess) return fail(c, PAYNE_E_HIP, std::string("hipMemcpy(") + what + "): " + hipGetErrorString(he));
+  if (k == kp) return make_h2_planes(c, d_w, h, n, kp, scale, planes, rscale);          // (padded on the device already)
+  std::vector<float> hp((size_t)n * kp, 0.f);
+  for (int i = 0; i < n; ++i) std::copy(h.begin() + (size_t)i * k, h.begin() + (size_t)(i + 1) * k, hp.begin() + (size_t)i * kp);
+  const float* d_hp = nullptr;
+  std::vector<void*> tmp;
+  int rc = upload(c, hp, &d_hp, tmp);
+  if (!rc) rc = make_h2_planes(c, d_hp, hp, n, kp, scale, planes, rscale);
+  for (void* q : tmp) (void)hipFree(q);
+  return rc;
+}
+
+// payne_ctx_create, step by step: each returns a PAYNE_E_* code with c->err set.
+// The dense kernels' operand copies of the spectral net (c->layers is filled in; maxh: the widest hidden layer).
+static int create_dense_operands(payne_ctx* c, const payne_model_desc* model, const payne_opts* opts, int maxh) {
+  int rc = PAYNE_OK;
+  hipError_t he = hipSuccess;
+  // k-padded copy of the output layer's weights for the LDS-DMA kernel (operands cannot be masked on the way)
+  const payne_layer& L = c->layers[model->n_layers - 1];
+  const int Kp = (L.n_in + 31) & ~31;
+  float* wp = nullptr;
+  if ((rc = dev_alloc(c, (size_t)L.n_out * Kp, &wp, c->owned))) return rc;
+  he = hipMemcpy2D(wp, (size_t)Kp * 4, L.w, (size_t)L.n_in * 4, (size_t)L.n_in * 4, L.n_out, hipMemcpyDeviceToDevice);
+  if (he != hipSuccess) return fail(c, PAYNE_E_HIP, std::string("hipMemcpy2D: ") + hipGetErrorString(he));
+  c->w_out_pad = wp; c->w_out_kp = Kp;
+  // the activations' pad columns are zero only if no wider layer ever wrote them: all hidden widths equal
+  bool same = model->n_layers >= 3;
+  for (int l = 1; l + 1 < model->n_layers; ++l) same = same && model->layers[l].n_out == model->layers[0].n_out;
+  c->dma_ok = same;
+  if (!same) return PAYNE_OK;
+  // hidden layers past the second (launch_hidden<false>): operand tiles straight into LDS need rows >= HK_PITCH floats apart that
+  // may be read to their end -- the activations' buffers are (pitch ld_hid, pad columns zero while all widths are equal); the
+  // weights get a copy with the same pitch
+  const int ldh = (maxh + 31) & ~31;
+  if (ldh >= HK_PITCH) {
+    for (int l = 1; l + 1 < model->n_layers; ++l) {
+      const payne_layer& Lh = c->layers[l];
+      if (Lh.n_in > HK_KC) continue;
+      float* wh = nullptr;
+      if ((rc = dev_alloc(c, (size_t)Lh.n_out * ldh, &wh, c->owned))) return rc;
+      he = hipMemcpy2D(wh, (size_t)ldh * 4, Lh.w, (size_t)Lh.n_in * 4, (size_t)Lh.n_in * 4, Lh.n_out, hipMemcpyDeviceToDevice);
+      if (he != hipSuccess) return fail(c, PAYNE_E_HIP, std::string("hipMemcpy2D: ") + hipGetErrorString(he));
+      c->w_hid_pad[l] = wh;
+    }
+  }
+  // the output layer's weights as three bf16 planes (OutForm::Bf16x3) ...
+  const size_t nw = (size_t)L.n_out * Kp;
+  if ((rc = dev_alloc(c, 3 * nw, &c->w_out_p3, c->owned))) return rc;
+  hipLaunchKernelGGL(payne_split3_kernel, dim3((unsigned)((nw + 255) / 256)), dim3(256), 0, nullptr, wp, nw, c->w_out_p3, nw);
+  he = hipDeviceSynchronize();
+  if (he != hipSuccess) return fail(c, PAYNE_E_HIP, std::string("weight split: ") + hipGetErrorString(he));
+  // ... and as two fp16 planes (OutForm::H2), the activations' scale calibrated on the label box.  The hidden layers' fp16 planes
+  // need the same calibration: it is made unless neither form is asked for.
+  const bool out_h2 = wanted_out_form(opts->variant) == OutForm::H2, hid_h2 = !(opts->variant & PAYNE_V_HID_F32);
+  std::string why;
+  double amaxl[PAYNE_MAX_LAYERS] = {};
+  const double amax = (out_h2 || hid_h2) ? hidden_amax(model, why, amaxl) : 0.0;
+  // the second layer's weights for hk_tile_h2: widths whose padded K is the tile's 304 columns
+  const payne_layer& L1 = model->layers[1];
+  if (h2_act_scale(amaxl[0]) > 0.f && L1.n_in > 288 && L1.n_in <= 304 && c->w_hid_pad[1] && hid_h2) {
+    c->a0_scale = h2_act_scale(amaxl[0]);
+    if ((rc = layer_h2_planes(c, L1.w, L1.n_out, L1.n_in, 304, c->a0_scale, "second layer", &c->w1_h2, &c->rs1))) return rc;
+    c->w1_rows = L1.n_out;
+    c->hs[0] = c->a0_scale;
+    // deeper nets (LinNet: five hidden layers): the layers past the second the same way, their activations handed on as planes
+    bool deep = model->n_layers > 3;
+    for (int l = 1; l + 1 < model->n_layers; ++l) deep = deep && h2_act_scale(amaxl[l]) > 0.f && model->layers[l].n_out == L1.n_out;
+    if (deep) {
+      for (int l = 1; l + 1 < model->n_layers; ++l) c->hs[l] = h2_act_scale(amaxl[l]);
+      for (int l = 2; l + 1 < model->n_layers; ++l) {
+        const payne_layer& Ll = model->layers[l];
+        if ((rc = layer_h2_planes(c, Ll.w, Ll.n_out, Ll.n_in, 304, c->hs[l - 1], "hidden layer", &c->wl_h2[l], &c->rsl[l]))) return rc;
+      }
+      for (int q = 0; q < 2; ++q)
+        if ((rc = dev_alloc(c, (size_t)2 * opts->b_max * 304, &c->hid_h2[q], c->owned))) return rc;
+      if ((rc = dev_alloc(c, (size_t)((opts->b_max + 31) / 32) * kChainMax, &c->chain_flags, c->owned))) return rc;
+    }
+  }
+  if (h2_act_scale(amax) > 0.f && out_h2) {
+    c->act_scale = h2_act_scale(amax);
+    if ((rc = layer_h2_planes(c, wp, L.n_out, Kp, Kp, c->act_scale, "output layer", &c->w_out_h2, &c->rscale))) return rc;
+  }
+  return PAYNE_OK;
+}
+// The first convolution stage's forward transform is linear and the same for every candidate: with identity vsini maps and a
+// compile-time geometry the output layer writes the rows already transformed (weights = the transform of each hidden unit's
+// pixel vector, computed here once in fp64), and the post kernel starts at the taper.
+static int create_freq_rows(payne_ctx* c, const payne_model_desc* model, const payne_opts* opts, int geom_n1) {
+  int rc = PAYNE_OK;
+  hipError_t he = hipSuccess;
+  const PostTables& T = c->T;
+  const bool fixed = geom_n1 != 0 && ((c->post_tw_lds && (T.n1 == 1024 || T.n1 == 2048 || T.n1 == 4096)) || (!c->post_tw_lds && T.n1 == 8192));
+  // (65 536 / 32 768 points with the stages on the compute unit: the rows in the order those kernels' registers hold the transform)
+  // (a model grid of any other length -- what a trained network has: readc3k.py:441-447 -- is resampled by the rotation stage first,
+  //  a static linear map as well: the LDS kernels' lengths take rows of the RESAMPLED spectrum's transform, freq_rs)
+  const bool ident = T.rot_identity && T.n1 == model->npix;
+  if (((fixed || c->big_chip || c->big_chip2) && ident || (fixed && !ident)) && c->w_out_p3 && c->hid_p3 && !(opts->variant & PAYNE_V_ROWS_PIXEL)) {
+    const payne_layer& L = model->layers[model->n_layers - 1];
+    const int K = L.n_in, Kp = c->w_out_kp, n = ident ? L.n_out : T.n1;
+    std::vector<float> W((size_t)L.n_out * K), b((size_t)L.n_out), Wz, bz;
+    he = hipMemcpy(W.data(), L.w, W.size() * 4, hipMemcpyDeviceToHost);
+    if (he == hipSuccess) he = hipMemcpy(b.data(), L.b, b.size() * 4, hipMemcpyDeviceToHost);
+    if (he != hipSuccess) return fail(c, PAYNE_E_HIP, std::string("hipMemcpy(output layer): ") + hipGetErrorString(he));
+    if (ident) freq_rows(W.data(), b.data(), -(double)kBase, n, K, Wz, bz, c->big_chip ? 1 : (c->big_chip2 ? 2 : 0));   // (rows are kept shifted by -1, as the pixel rows are)
+    else {
+      freq_rows(W.data(), b.data(), -(double)kBase, n, K, Wz, bz, 0, c->H.rs1_idx.data(), c->H.rs1_frac.data(), L.n_out);
+      c->freq_rs = true;
+      if ((rc = dev_alloc(c, (size_t)1, &c->rot_flag, c->owned))) return rc;            // (zeroed; sequence numbers start at 1)
+    }
+    std::vector<float> Wp((size_t)n * Kp, 0.f);
+    for (int i = 0; i < n; ++i) std::copy(Wz.begin() + (size_t)i * K, Wz.begin() + (size_t)(i + 1) * K, Wp.begin() + (size_t)i * Kp);
+    const float* d_wp = nullptr;
+    std::vector<void*> tmp;
+    if ((rc = upload(c, Wp, &d_wp, c->owned))) return rc;      // (kept: the fp32 form is what the one-tile-per-CU kernel reads)
+    c->w_out_padz = d_wp;
+    const size_t nw = (size_t)n * Kp;
+    rc = dev_alloc(c, 3 * nw, &c->w_out_p3z, c->owned);
+    if (!rc) {
+      hipLaunchKernelGGL(payne_split3_kernel, dim3((unsigned)((nw + 255) / 256)), dim3(256), 0, nullptr, d_wp, nw, c->w_out_p3z, nw);
+      he = hipDeviceSynchronize();
+    }
+    for (void* q : tmp) (void)hipFree(q);
+    if (rc) return rc;
+    if (he != hipSuccess) return fail(c, PAYNE_E_HIP, std::string("weight split: ") + hipGetErrorString(he));
+    if ((rc = upload(c, bz, &c->bias_z, c->owned))) return rc;
+    if (c->w_out_h2 && (rc = make_h2_planes(c, d_wp, Wp, n, Kp, c->act_scale, &c->w_out_h2z, &c->rscalez))) return rc;
+    c->freq_ok = true;
+  }
+  return PAYNE_OK;
+}
+// The photometric nets.
+static int create_phot(payne_ctx* c, const payne_phot_desc* phot, const payne_opts* opts) {
+  int rc = PAYNE_OK;
+  hipError_t he = hipSuccess;
+  if (phot->n_filters <= 0 || phot->hidden <= 0 || phot->hidden > 2048) return fail(c, PAYNE_E_INVALID, "phot.n_filters/hidden out of range");
+  if (!phot->w1 || !phot->b1 || !phot->w2 || !phot->b2 || !phot->w3 || !phot->b3 || !phot->xmin || !phot->xmax)
+    return fail(c, PAYNE_E_INVALID, "phot descriptor has NULL members");
+  PhotTables& P = c->P;
+  const int F = phot->n_filters, H = phot->hidden;
+  P.F = F; P.H = H;
+  P.w1 = phot->w1; P.b1 = phot->b1; P.b2 = phot->b2; P.w3 = phot->w3; P.b3 = phot->b3;
+  for (int d = 0; d < 6; ++d) { P.xmin[d] = phot->xmin[d]; P.xden[d] = phot->xmax[d] - phot->xmin[d]; }
+  {   // w2 -> [F][k][h] so that lanes (h) read consecutive addresses
+    std::vector<float> w2((size_t)F * H * H), w2t((size_t)F * H * H);
+    he = hipMemcpy(w2.data(), phot->w2, w2.size() * 4, hipMemcpyDeviceToHost);
+    if (he != hipSuccess) return fail(c, PAYNE_E_HIP, std::string("hipMemcpy(w2): ") + hipGetErrorString(he));
+    for (int f = 0; f < F; ++f)
+      for (int h = 0; h < H; ++h)
+        for (int k = 0; k < H; ++k) w2t[((size_t)f * H + k) * H + h] = w2[((size_t)f * H + h) * H + k];
+    if ((rc = upload(c, w2t, &P.w2t, c->owned))) return rc;
+  }
+  if (phot->hiav) {
+    std::vector<double> hv(phot->hiav, phot->hiav + (size_t)F * 5);
+    if ((rc = upload(c, hv, &P.hiav, c->owned))) return rc;
+  }
+  if (phot->obs_mag && phot->obs_err) {
+    std::vector<double> m(phot->obs_mag, phot->obs_mag + F), e(phot->obs_err, phot->obs_err + F);
+    const double *dm, *de;
+    if ((rc = upload(c, m, &dm, c->owned))) return rc;
+    if ((rc = upload(c, e, &de, c->owned))) return rc;
+    c->obs_mag = const_cast<double*>(dm); c->obs_err = const_cast<double*>(de);
+    c->has_obs_phot = true;
+  }
+  if ((rc = dev_alloc(c, (size_t)opts->b_max * F, &c->mags_ws, c->owned))) return rc;
+  if ((size_t)H * 16 > 48 * 1024) {
+    he = hipFuncSetAttribute(reinterpret_cast<const void*>(payne_sed_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, H * 16);
+    if (he != hipSuccess) return fail(c, PAYNE_E_HIP, std::string("hipFuncSetAttribute(sed): ") + hipGetErrorString(he));
+  }
+  c->has_phot = true;
+  return PAYNE_OK;
+}
+
 extern "C" int payne_ctx_create(const payne_model_desc* model, const payne_obs_desc* obs, const payne_phot_desc* phot,
                                 const payne_opts* opts, int device, payne_ctx** out) {
   if (!out) return fail(nullptr, PAYNE_E_INVALID, "out is NULL");
@@ -423,95 +620,7 @@ extern "C" int payne_ctx_create(const payne_model_desc* model, const payne_obs_d
       }
       if (l + 1 < model->n_layers) maxh = std::max(maxh, L.n_out);
     }
-    {   // k-padded copy of the output layer's weights for the LDS-DMA kernel (operands cannot be masked on the way)
-      const payne_layer& L = c->layers[model->n_layers - 1];
-      const int Kp = (L.n_in + 31) & ~31;
-      float* wp = nullptr;
-      if ((rc = dev_alloc(c, (size_t)L.n_out * Kp, &wp, c->owned))) return bail(rc);
-      he = hipMemcpy2D(wp, (size_t)Kp * 4, L.w, (size_t)L.n_in * 4, (size_t)L.n_in * 4, L.n_out, hipMemcpyDeviceToDevice);
-      if (he != hipSuccess) return bail(fail(c, PAYNE_E_HIP, std::string("hipMemcpy2D: ") + hipGetErrorString(he)));
-      c->w_out_pad = wp; c->w_out_kp = Kp;
-      // the activations' pad columns are zero only if no wider layer ever wrote them: all hidden widths equal
-      bool same = model->n_layers >= 3;
-      for (int l = 1; l + 1 < model->n_layers; ++l) same = same && model->layers[l].n_out == model->layers[0].n_out;
-      c->dma_ok = same;
-      // hidden layers past the second (launch_hidden<false>): operand tiles straight into LDS need rows >= HK_PITCH floats apart that
-      // may be read to their end -- the activations' buffers are (pitch ld_hid, pad columns zero while all widths are equal); the
-      // weights get a copy with the same pitch
-      const int ldh = (maxh + 31) & ~31;
-      if (same && ldh >= HK_PITCH) {
-        for (int l = 1; l + 1 < model->n_layers; ++l) {
-          const payne_layer& Lh = c->layers[l];
-          if (Lh.n_in > HK_KC) continue;
-          float* wh = nullptr;
-          if ((rc = dev_alloc(c, (size_t)Lh.n_out * ldh, &wh, c->owned))) return bail(rc);
-          he = hipMemcpy2D(wh, (size_t)ldh * 4, Lh.w, (size_t)Lh.n_in * 4, (size_t)Lh.n_in * 4, Lh.n_out, hipMemcpyDeviceToDevice);
-          if (he != hipSuccess) return bail(fail(c, PAYNE_E_HIP, std::string("hipMemcpy2D: ") + hipGetErrorString(he)));
-          c->w_hid_pad[l] = wh;
-        }
-      }
-      if (same) {
-        const size_t nw = (size_t)L.n_out * Kp;
-        if ((rc = dev_alloc(c, 3 * nw, &c->w_out_p3, c->owned))) return bail(rc);
-        hipLaunchKernelGGL(payne_split3_kernel, dim3((unsigned)((nw + 255) / 256)), dim3(256), 0, nullptr, wp, nw, c->w_out_p3, nw);
-        he = hipDeviceSynchronize();
-        if (he != hipSuccess) return bail(fail(c, PAYNE_E_HIP, std::string("weight split: ") + hipGetErrorString(he)));
-        // ... and as two fp16 planes, the activations' scale calibrated on the label box (a factor of 8 to spare below fp16's range)
-        std::string why;
-        double amaxl[PAYNE_MAX_LAYERS] = {};
-        const bool want_h2 = (opts->variant & (PAYNE_V_OUT_BF16X3 | PAYNE_V_OUT_PLANES | PAYNE_V_OUT_F32 | PAYNE_V_OUT_GENERIC | PAYNE_V_OUT_BK64)) == 0 ||
-                             !(opts->variant & PAYNE_V_HID_F32);
-        const double amax = want_h2 ? hidden_amax(model, why, amaxl) : 0.0;
-        const double amax0 = amaxl[0];
-        // the second layer's weights for hk_tile_h2: widths whose padded K is the tile's 304 columns
-        const payne_layer& L1 = model->layers[1];
-        if (amax0 > 0.0 && amax0 < 1e30 && L1.n_in > 288 && L1.n_in <= 304 && c->w_hid_pad[1] && !(opts->variant & PAYNE_V_HID_F32)) {
-          c->a0_scale = (float)std::ldexp(1.0, std::max(-60, std::min(60, (int)std::floor(std::log2(4096.0 / amax0)))));
-          std::vector<float> h1((size_t)L1.n_out * L1.n_in), hp((size_t)L1.n_out * 304, 0.f);
-          he = hipMemcpy(h1.data(), L1.w, h1.size() * 4, hipMemcpyDeviceToHost);
-          if (he != hipSuccess) return bail(fail(c, PAYNE_E_HIP, std::string("hipMemcpy(second layer): ") + hipGetErrorString(he)));
-          for (int i = 0; i < L1.n_out; ++i) std::copy(h1.begin() + (size_t)i * L1.n_in, h1.begin() + (size_t)(i + 1) * L1.n_in, hp.begin() + (size_t)i * 304);
-          const float* d_hp = nullptr;
-          std::vector<void*> tmp1;
-          if ((rc = upload(c, hp, &d_hp, tmp1))) return bail(rc);
-          rc = make_h2_planes(c, d_hp, hp, L1.n_out, 304, c->a0_scale, &c->w1_h2, &c->rs1);
-          for (void* q : tmp1) (void)hipFree(q);
-          if (rc) return bail(rc);
-          c->w1_rows = L1.n_out;
-          c->hs[0] = c->a0_scale;
-          // deeper nets (LinNet: five hidden layers): the layers past the second the same way, their activations handed on as planes
-          bool deep = model->n_layers > 3;
-          for (int l = 1; l + 1 < model->n_layers; ++l) deep = deep && amaxl[l] > 0.0 && amaxl[l] < 1e30 && model->layers[l].n_out == L1.n_out;
-          if (deep) {
-            for (int l = 1; l + 1 < model->n_layers; ++l)
-              c->hs[l] = (float)std::ldexp(1.0, std::max(-60, std::min(60, (int)std::floor(std::log2(4096.0 / amaxl[l])))));
-            for (int l = 2; l + 1 < model->n_layers; ++l) {
-              const payne_layer& Ll = model->layers[l];
-              std::vector<float> hl((size_t)Ll.n_out * Ll.n_in), hq((size_t)Ll.n_out * 304, 0.f);
-              he = hipMemcpy(hl.data(), Ll.w, hl.size() * 4, hipMemcpyDeviceToHost);
-              if (he != hipSuccess) return bail(fail(c, PAYNE_E_HIP, std::string("hipMemcpy(hidden layer): ") + hipGetErrorString(he)));
-              for (int i = 0; i < Ll.n_out; ++i) std::copy(hl.begin() + (size_t)i * Ll.n_in, hl.begin() + (size_t)(i + 1) * Ll.n_in, hq.begin() + (size_t)i * 304);
-              const float* d_hq = nullptr;
-              std::vector<void*> tmp2;
-              if ((rc = upload(c, hq, &d_hq, tmp2))) return bail(rc);
-              rc = make_h2_planes(c, d_hq, hq, Ll.n_out, 304, c->hs[l - 1], &c->wl_h2[l], &c->rsl[l]);
-              for (void* q : tmp2) (void)hipFree(q);
-              if (rc) return bail(rc);
-            }
-            for (int q = 0; q < 2; ++q)
-              if ((rc = dev_alloc(c, (size_t)2 * opts->b_max * 304, &c->hid_h2[q], c->owned))) return bail(rc);
-            if ((rc = dev_alloc(c, (size_t)((opts->b_max + 31) / 32) * kChainMax, &c->chain_flags, c->owned))) return bail(rc);
-          }
-        }
-        if (amax > 0.0 && amax < 1e30 && !(opts->variant & (PAYNE_V_OUT_BF16X3 | PAYNE_V_OUT_PLANES | PAYNE_V_OUT_F32 | PAYNE_V_OUT_GENERIC | PAYNE_V_OUT_BK64))) {
-          c->act_scale = (float)std::ldexp(1.0, std::max(-60, std::min(60, (int)std::floor(std::log2(4096.0 / amax)))));
-          std::vector<float> hw(nw);
-          he = hipMemcpy(hw.data(), wp, nw * 4, hipMemcpyDeviceToHost);
-          if (he != hipSuccess) return bail(fail(c, PAYNE_E_HIP, std::string("hipMemcpy(output layer): ") + hipGetErrorString(he)));
-          if ((rc = make_h2_planes(c, wp, hw, L.n_out, Kp, c->act_scale, &c->w_out_h2, &c->rscale))) return bail(rc);
-        }
-      }
-    }
+    if ((rc = create_dense_operands(c, model, opts, maxh))) return bail(rc);
     c->n_layers = model->n_layers;
     c->n_labels = model->n_labels;
     for (int d = 0; d < model->n_labels; ++d) { c->xmin[d] = model->xmin[d]; c->xden[d] = model->xmax[d] - model->xmin[d]; }
@@ -582,89 +691,12 @@ extern "C" int payne_ctx_create(const payne_model_desc* model, const payne_obs_d
     if (he != hipSuccess) return bail(fail(c, PAYNE_E_HIP, std::string("hipFuncSetAttribute: ") + hipGetErrorString(he)));
     he = hipFuncSetAttribute(reinterpret_cast<const void*>(c->post_fn), hipFuncAttributeMaxDynamicSharedMemorySize, (int)c->post_lds);
     if (he != hipSuccess) return bail(fail(c, PAYNE_E_HIP, std::string("hipFuncSetAttribute: ") + hipGetErrorString(he)));
-    // The first convolution stage's forward transform is linear and the same for every candidate: with identity vsini maps and a
-    // compile-time geometry the output layer writes the rows already transformed (weights = the transform of each hidden unit's
-    // pixel vector, computed here once in fp64), and the post kernel starts at the taper.
-    {
-      const bool fixed = geom_n1 != 0 && ((c->post_tw_lds && (T.n1 == 1024 || T.n1 == 2048 || T.n1 == 4096)) || (!c->post_tw_lds && T.n1 == 8192));
-      // (65 536 / 32 768 points with the stages on the compute unit: the rows in the order those kernels' registers hold the transform)
-      // (a model grid of any other length -- what a trained network has: readc3k.py:441-447 -- is resampled by the rotation stage first,
-      //  a static linear map as well: the LDS kernels' lengths take rows of the RESAMPLED spectrum's transform, freq_rs)
-      const bool ident = T.rot_identity && T.n1 == model->npix;
-      if (((fixed || c->big_chip || c->big_chip2) && ident || (fixed && !ident)) && c->w_out_p3 && c->hid_p3 && !(opts->variant & PAYNE_V_ROWS_PIXEL)) {
-        const payne_layer& L = model->layers[model->n_layers - 1];
-        const int K = L.n_in, Kp = c->w_out_kp, n = ident ? L.n_out : T.n1;
-        std::vector<float> W((size_t)L.n_out * K), b((size_t)L.n_out), Wz, bz;
-        he = hipMemcpy(W.data(), L.w, W.size() * 4, hipMemcpyDeviceToHost);
-        if (he == hipSuccess) he = hipMemcpy(b.data(), L.b, b.size() * 4, hipMemcpyDeviceToHost);
-        if (he != hipSuccess) return bail(fail(c, PAYNE_E_HIP, std::string("hipMemcpy(output layer): ") + hipGetErrorString(he)));
-        if (ident) freq_rows(W.data(), b.data(), -(double)kBase, n, K, Wz, bz, c->big_chip ? 1 : (c->big_chip2 ? 2 : 0));   // (rows are kept shifted by -1, as the pixel rows are)
-        else {
-          freq_rows(W.data(), b.data(), -(double)kBase, n, K, Wz, bz, 0, c->H.rs1_idx.data(), c->H.rs1_frac.data(), L.n_out);
-          c->freq_rs = true;
-          if ((rc = dev_alloc(c, (size_t)1, &c->rot_flag, c->owned))) return bail(rc);            // (zeroed; sequence numbers start at 1)
-        }
-        std::vector<float> Wp((size_t)n * Kp, 0.f);
-        for (int i = 0; i < n; ++i) std::copy(Wz.begin() + (size_t)i * K, Wz.begin() + (size_t)(i + 1) * K, Wp.begin() + (size_t)i * Kp);
-        const float* d_wp = nullptr;
-        std::vector<void*> tmp;
-        if ((rc = upload(c, Wp, &d_wp, c->owned))) return bail(rc);      // (kept: the fp32 form is what the one-tile-per-CU kernel reads)
-        c->w_out_padz = d_wp;
-        const size_t nw = (size_t)n * Kp;
-        rc = dev_alloc(c, 3 * nw, &c->w_out_p3z, c->owned);
-        if (!rc) {
-          hipLaunchKernelGGL(payne_split3_kernel, dim3((unsigned)((nw + 255) / 256)), dim3(256), 0, nullptr, d_wp, nw, c->w_out_p3z, nw);
-          he = hipDeviceSynchronize();
-        }
-        for (void* q : tmp) (void)hipFree(q);
-        if (rc) return bail(rc);
-        if (he != hipSuccess) return bail(fail(c, PAYNE_E_HIP, std::string("weight split: ") + hipGetErrorString(he)));
-        if ((rc = upload(c, bz, &c->bias_z, c->owned))) return bail(rc);
-        if (c->w_out_h2 && (rc = make_h2_planes(c, d_wp, Wp, n, Kp, c->act_scale, &c->w_out_h2z, &c->rscalez))) return bail(rc);
-        c->freq_ok = true;
-      }
-    }
+    if ((rc = create_freq_rows(c, model, opts, geom_n1))) return bail(rc);
     c->has_model = true;
     if ((rc = bind_obs(c, obs))) return bail(rc);
   }
 
-  if (phot) {
-    if (phot->n_filters <= 0 || phot->hidden <= 0 || phot->hidden > 2048) return bail(fail(c, PAYNE_E_INVALID, "phot.n_filters/hidden out of range"));
-    if (!phot->w1 || !phot->b1 || !phot->w2 || !phot->b2 || !phot->w3 || !phot->b3 || !phot->xmin || !phot->xmax)
-      return bail(fail(c, PAYNE_E_INVALID, "phot descriptor has NULL members"));
-    PhotTables& P = c->P;
-    const int F = phot->n_filters, H = phot->hidden;
-    P.F = F; P.H = H;
-    P.w1 = phot->w1; P.b1 = phot->b1; P.b2 = phot->b2; P.w3 = phot->w3; P.b3 = phot->b3;
-    for (int d = 0; d < 6; ++d) { P.xmin[d] = phot->xmin[d]; P.xden[d] = phot->xmax[d] - phot->xmin[d]; }
-    {   // w2 -> [F][k][h] so that lanes (h) read consecutive addresses
-      std::vector<float> w2((size_t)F * H * H), w2t((size_t)F * H * H);
-      he = hipMemcpy(w2.data(), phot->w2, w2.size() * 4, hipMemcpyDeviceToHost);
-      if (he != hipSuccess) return bail(fail(c, PAYNE_E_HIP, std::string("hipMemcpy(w2): ") + hipGetErrorString(he)));
-      for (int f = 0; f < F; ++f)
-        for (int h = 0; h < H; ++h)
-          for (int k = 0; k < H; ++k) w2t[((size_t)f * H + k) * H + h] = w2[((size_t)f * H + h) * H + k];
-      if ((rc = upload(c, w2t, &P.w2t, c->owned))) return bail(rc);
-    }
-    if (phot->hiav) {
-      std::vector<double> hv(phot->hiav, phot->hiav + (size_t)F * 5);
-      if ((rc = upload(c, hv, &P.hiav, c->owned))) return bail(rc);
-    }
-    if (phot->obs_mag && phot->obs_err) {
-      std::vector<double> m(phot->obs_mag, phot->obs_mag + F), e(phot->obs_err, phot->obs_err + F);
-      const double *dm, *de;
-      if ((rc = upload(c, m, &dm, c->owned))) return bail(rc);
-      if ((rc = upload(c, e, &de, c->owned))) return bail(rc);
-      c->obs_mag = const_cast<double*>(dm); c->obs_err = const_cast<double*>(de);
-      c->has_obs_phot = true;
-    }
-    if ((rc = dev_alloc(c, (size_t)opts->b_max * F, &c->mags_ws, c->owned))) return bail(rc);
-    if ((size_t)H * 16 > 48 * 1024) {
-      he = hipFuncSetAttribute(reinterpret_cast<const void*>(payne_sed_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, H * 16);
-      if (he != hipSuccess) return bail(fail(c, PAYNE_E_HIP, std::string("hipFuncSetAttribute(sed): ") + hipGetErrorString(he)));
-    }
-    c->has_phot = true;
-  }
+  if (phot && (rc = create_phot(c, phot, opts))) return bail(rc);
   *out = c;
   return PAYNE_OK;
 }
@@ -807,29 +839,9 @@ static hipError_t set_dense_attributes() {
     const hipError_t r = hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     if (e == hipSuccess) e = r;
   };
-  set(reinterpret_cast<const void*>(payne_dense_kernel<64, 64, 32, true>), dense_lds_bytes<64, 64, 32>());
-  set(reinterpret_cast<const void*>(payne_dense_kernel<64, 64, 32, false>), dense_lds_bytes<64, 64, 32>());
-  set(reinterpret_cast<const void*>(payne_dense_dma_kernel<4, 32, 0, 4, true>), dm_lds_bytes<4, 32, 4>());
-  set(reinterpret_cast<const void*>(payne_dense_dma_kernel<4, 32, 10, 4, true>), dm_lds_bytes<4, 32, 4>());
-  set(reinterpret_cast<const void*>(payne_dense_dma_kernel<4, 32, 0, 3, false>), dm_lds_bytes<4, 32, 3>());
-  set(reinterpret_cast<const void*>(payne_dense_dma_kernel<4, 64, 0, 3, true>), dm_lds_bytes<4, 64, 3>());
-  set(reinterpret_cast<const void*>(payne_dense_dma_kernel<4, 64, 5, 3, true>), dm_lds_bytes<4, 64, 3>());
-  set(reinterpret_cast<const void*>(payne_dense_dma3_kernel<0, 4, true>), d3_lds_bytes<4>());
-  set(reinterpret_cast<const void*>(payne_dense_dma3_kernel<10, 4, true>), d3_lds_bytes<4>());
-  set(reinterpret_cast<const void*>(payne_dense_dma3_kernel<0, 2, false>), d3_lds_bytes<2>());
-  set(reinterpret_cast<const void*>(payne_dense_dma3f_kernel<10>), d3_lds_bytes<4>());
-  set(reinterpret_cast<const void*>(payne_dense_dma2h_kernel<10, 32>), d2_lds_bytes<32>());
-  set(reinterpret_cast<const void*>(payne_dense_dma2h_kernel<0, 32>), d2_lds_bytes<32>());
-  set(reinterpret_cast<const void*>(payne_dense_dma2h_kernel<5, 64>), d2_lds_bytes<64>());
-  set(reinterpret_cast<const void*>(payne_dense_dma2hh_kernel<5>), d2hh_lds_bytes<5>());
-  set(reinterpret_cast<const void*>(payne_dense_big3_kernel<false>), b3_lds_bytes(false));
-  set(reinterpret_cast<const void*>(payne_dense_big3_kernel<true>), b3_lds_bytes(true));
-  set(reinterpret_cast<const void*>(payne_dense_chain_kernel), HK_LDS_BYTES);
-  set(reinterpret_cast<const void*>(payne_dense_hidden_kernel<true, 4>), HK_LDS_BYTES);
-  set(reinterpret_cast<const void*>(payne_dense_hidden_kernel<true, PAYNE_MAX_LABELS>), HK_LDS_BYTES);
-  set(reinterpret_cast<const void*>(payne_dense_hidden_kernel<false, 4>), HK_LDS_BYTES);
-  set(reinterpret_cast<const void*>(payne_dense_hidden_kernel<true, 4, 8>), HK_LDS_BYTES);
-  set(reinterpret_cast<const void*>(payne_dense_hidden_kernel<true, PAYNE_MAX_LABELS, 8>), HK_LDS_BYTES);
+#define PAYNE_SET_T(K, ARGS, ...) set(reinterpret_cast<const void*>(PAYNE_UNPAREN K), __VA_ARGS__);
+#define PAYNE_SET_F(K, ...) set(reinterpret_cast<const void*>(K), __VA_ARGS__);
+  PAYNE_DENSE_KERNELS(PAYNE_SET_T, PAYNE_SET_F)
   return e;
 }
 
@@ -837,11 +849,10 @@ template <int BM, int BN, int BK, bool FUSE>
 static void launch_dense(DenseParams& p, hipStream_t s) {
   p.grid_m = (p.B + BM - 1) / BM;
   p.grid_n = (p.N + BN - 1) / BN;
-  constexpr size_t lds = dense_lds_bytes<BM, BN, BK>();
 #ifdef PAYNE_STAMPS
   p.stamps = FUSE ? nullptr : g_dense_stamps;
 #endif
-  PAYNE_LAUNCH((payne_dense_kernel<BM, BN, BK, FUSE>), dim3(p.grid_m * p.grid_n), dim3(256), lds, s, p);
+  PAYNE_LAUNCH_DENSE((payne_dense_kernel<BM, BN, BK, FUSE>), dim3(p.grid_m * p.grid_n), dim3(256), s, p);
 }
 
 // Output layer, LDS-DMA form (64 x 128 tiles, 512 threads, BK-deep stages; NK: k-steps fixed at compile time or 0; NS: ring;
@@ -849,110 +860,73 @@ static void launch_dense(DenseParams& p, hipStream_t s) {
 template <int BK, int NK, int NS, bool PIPE>
 static void launch_out_dma_nk(DenseParams& p, hipStream_t s) {
   constexpr int WN = 4;
-  constexpr size_t lds = dm_lds_bytes<WN, BK, NS>();
-  PAYNE_LAUNCH((payne_dense_dma_kernel<WN, BK, NK, NS, PIPE>), dim3(p.grid_m * p.grid_n), dim3(128 * WN), lds, s, p);
+  PAYNE_LAUNCH_DENSE((payne_dense_dma_kernel<WN, BK, NK, NS, PIPE>), dim3(p.grid_m * p.grid_n), dim3(128 * WN), s, p);
 }
-template <int BK>
-static void launch_out_dma(payne_ctx* c, DenseParams& p, hipStream_t s) {
-  constexpr int WN = 4;
+// What plan_out decides.
+struct OutPlan {
+  OutForm form = OutForm::Generic;
+  int grid_m = 0, grid_n = 0;        // tiles of the launch (64 x 128; big: 128 x 256), every form but Generic
+  bool sel = false;                  // rows of the resampled grid, or pixel rows if the batch's records say so
+  bool big = false;                  // Bf16x3, H2: many whole 128 x 256 tiles, persistent workgroups (payne_dense_big3_kernel)
+  bool own_cu = false;               // a compute unit for every tile: the deep / pipelined schedules
+  bool fixed = false;                // 300-wide nets: the k-steps of the 320 padded columns counted at compile time
+  bool bk64 = false;                 // F32Dma: three 64-deep stages (PAYNE_V_OUT_BK64)
+  bool halves = false;               // H2, fixed, own_cu: the tile finished in two halves (payne_dense_dma2hh_kernel)
+  bool split_w = false;              // Bf16x3, fixed, own_cu: fp32 weights split on their way into LDS (payne_dense_dma3f_kernel)
+};
+// F32Dma: 64 x 128 tiles, 512 threads (payne_dense_dma_kernel<WN = 4, BK, NK, NS, PIPE>).
+static void launch_out_dma(payne_ctx* c, DenseParams& p, hipStream_t s, const OutPlan& plan) {
   p.k_real = p.K;                                          // the layer's own width: the padded tail is skipped
   p.W = c->w_out_pad; p.K = c->w_out_kp;                   // padded pitch; X's pitch (ld_hid) is a multiple of 32 too
-  p.grid_m = (p.B + 63) / 64;
-  p.grid_n = (p.N + 32 * WN - 1) / (32 * WN);
+  p.grid_m = plan.grid_m; p.grid_n = plan.grid_n;
 #ifdef PAYNE_STAMPS
   p.stamps = g_dense_stamps;
 #endif
-  constexpr int NKC = 320 / BK;                            // H = 300 -> 320 columns
-  const bool fixed = p.K == NKC * BK && !(c->opts.variant & PAYNE_V_OUT_ROLLED);
-  if constexpr (BK == 64) {                                // (variant: three 64-deep stages)
-    if (fixed) launch_out_dma_nk<64, NKC, 3, true>(p, s); else launch_out_dma_nk<64, 0, 3, true>(p, s);
-  } else if (p.grid_m * p.grid_n <= c->n_cu) {             // one tile per CU at most: the pipelined schedule, four stages
-    if (fixed) launch_out_dma_nk<32, NKC, 4, true>(p, s); else launch_out_dma_nk<32, 0, 4, true>(p, s);
+  if (plan.bk64) {                                         // (variant: three 64-deep stages)
+    if (plan.fixed) launch_out_dma_nk<64, 5, 3, true>(p, s); else launch_out_dma_nk<64, 0, 3, true>(p, s);
+  } else if (plan.own_cu) {                                // one tile per CU at most: the pipelined schedule, four stages
+    if (plan.fixed) launch_out_dma_nk<32, 10, 4, true>(p, s); else launch_out_dma_nk<32, 0, 4, true>(p, s);
   } else {
     launch_out_dma_nk<32, 0, 3, false>(p, s);              // many tiles per CU: two workgroups per CU, the plain schedule
   }
 }
 
-// Output layer as six bf16 products (payne_dense_dma3_kernel): equal hidden widths.
-static bool out_dma3_ok(const payne_ctx* c, int, int) {
-  return c->w_out_p3 && c->hid_p3 && c->dma_ok && c->ld_hid >= c->w_out_kp && !(c->opts.variant & (PAYNE_V_OUT_F32 | PAYNE_V_OUT_GENERIC | PAYNE_V_OUT_BK64));
-}
-// ... as three fp16-pair products: many whole 128 x 256 tiles (payne_dense_big3_kernel<true>), else 64 x 128 tiles (payne_dense_dma2h_kernel)
-static bool out_big_tiles(const payne_ctx* c, int B, int N, bool sel) {
-  return B % B3_TM == 0 && N % B3_TN == 0 && (B / B3_TM) * (N / B3_TN) >= 2 * c->n_cu && !(c->opts.variant & PAYNE_V_OUT_SMALL_TILES) && !sel;
-}
-static bool out_dma2h_ok(const payne_ctx* c, int B, int N, bool sel = false) {
-  // (whatever the batch: a candidate's rows do not depend on how many others share its batch -- many whole 128 x 256 tiles take
-  //  payne_dense_big3_kernel<true>, everything else payne_dense_dma2h_kernel, one tile a workgroup, same products in the same order)
-  (void)sel;
-  // (payne_dense_dma2h_kernel addresses an operand plane by 32-bit byte offsets: rows x pitch x 2 bytes below 2^31)
-  const unsigned long long plane_w = 2ull * (unsigned long long)std::max(N, c->T.n1) * (unsigned long long)c->w_out_kp;
-  const unsigned long long plane_x = 2ull * (unsigned long long)c->opts.b_max * (unsigned long long)c->ld_hid;
-  if (plane_w >= (1ull << 31) || plane_x >= (1ull << 31)) return false;
-  return out_dma3_ok(c, B, N) && c->w_out_h2 && c->act_scale > 0.f && !(c->opts.variant & (PAYNE_V_OUT_BF16X3 | PAYNE_V_OUT_PLANES));
-}
-static void launch_out_dma2h(payne_ctx* c, DenseParams& p, hipStream_t s, bool freq) {
+// Bf16x3 and H2: operand planes.  Many whole 128 x 256 tiles (C5) take payne_dense_big3_kernel's persistent workgroups, everything else one
+// 64 x 128 tile a workgroup -- whatever the batch, the same products in the same order: a candidate's rows do not depend on how many
+// others share its batch.
+static void launch_out_planes(payne_ctx* c, DenseParams& p, hipStream_t s, const OutPlan& plan, bool freq) {
+  const bool h2 = plan.form == OutForm::H2;
   p.k_real = p.K;
   p.K = c->w_out_kp;
-  p.Wp = freq ? c->w_out_h2z : c->w_out_h2; p.plane_w = (size_t)p.N * c->w_out_kp;
-  p.rscale = freq ? c->rscalez : c->rscale;
+  p.Wp = h2 ? (freq ? c->w_out_h2z : c->w_out_h2) : (freq ? c->w_out_p3z : c->w_out_p3); p.plane_w = (size_t)p.N * c->w_out_kp;
+  if (h2) p.rscale = freq ? c->rscalez : c->rscale;
   if (freq) { p.bias = c->bias_z; p.bias_shift = 0.f; }
   p.Xp = c->hid_p3; p.plane_x = (size_t)c->opts.b_max * c->ld_hid; p.ldp = c->ld_hid;
-  if (out_big_tiles(c, p.B, p.N, p.sel != nullptr)) {      // many whole 128 x 256 tiles per CU (C5): persistent workgroups
-    p.grid_m = p.B / B3_TM; p.grid_n = p.N / B3_TN;
-    PAYNE_LAUNCH(payne_dense_big3_kernel<true>, dim3(c->n_cu), dim3(512), b3_lds_bytes(true), s, p);
-    return;
-  }
-  p.grid_m = (p.B + 63) / 64;
-  p.grid_n = (p.N + 127) / 128;
+  p.grid_m = plan.grid_m; p.grid_n = plan.grid_n;
 #ifdef PAYNE_STAMPS
-  p.stamps = g_dense_stamps;
+  if (!(h2 && plan.big)) p.stamps = g_dense_stamps;
 #endif
   const dim3 grid(p.grid_m * p.grid_n), block(512);
-  // 300-wide nets: five 64-deep steps when every tile has a compute unit to itself (C2: 144 KB of LDS a workgroup), ten 32-deep ones
+  if (plan.big && h2) PAYNE_LAUNCH_DENSE(payne_dense_big3_kernel<true>, dim3(c->n_cu), dim3(512), s, p);
+  else if (plan.big) PAYNE_LAUNCH_DENSE(payne_dense_big3_kernel<false>, dim3(c->n_cu), block, s, p);       // half the operand bytes per product
+  // H2, 300-wide nets: five 64-deep steps when every tile has a compute unit to itself (C2: 144 KB of LDS a workgroup), ten 32-deep ones
   // otherwise; other widths, and PAYNE_V_OUT_ROLLED: 32-deep steps counted at run time.  Same products in the same order in all three.
-  const bool k320 = p.K == 320 && !(c->opts.variant & PAYNE_V_OUT_ROLLED);
-  const bool deep = (int)grid.x <= c->n_cu;
   // (... finished in two halves: the left half's rows leave under the right half's products -- payne_dense_dma2hh_kernel, same rows to the bit)
-  if (k320 && deep && !(c->opts.variant & PAYNE_V_OUT_WHOLE_TILE))
-    PAYNE_LAUNCH((payne_dense_dma2hh_kernel<5>), grid, block, d2hh_lds_bytes<5>(), s, PAYNE_D3_LEAD_ARGS(p), p);
-  else if (k320 && deep) PAYNE_LAUNCH((payne_dense_dma2h_kernel<5, 64>), grid, block, d2_lds_bytes<64>(), s, PAYNE_D3_LEAD_ARGS(p), p);
-  else if (k320) PAYNE_LAUNCH((payne_dense_dma2h_kernel<10, 32>), grid, block, d2_lds_bytes<32>(), s, PAYNE_D3_LEAD_ARGS(p), p);
-  else PAYNE_LAUNCH((payne_dense_dma2h_kernel<0, 32>), grid, block, d2_lds_bytes<32>(), s, PAYNE_D3_LEAD_ARGS(p), p);
-}
-static void launch_out_dma3(payne_ctx* c, DenseParams& p, hipStream_t s, bool freq) {
-  p.k_real = p.K;
-  p.K = c->w_out_kp;
-  p.Wp = freq ? c->w_out_p3z : c->w_out_p3; p.plane_w = (size_t)p.N * c->w_out_kp;
-  if (freq) { p.bias = c->bias_z; p.bias_shift = 0.f; }
-  p.Xp = c->hid_p3; p.plane_x = (size_t)c->opts.b_max * c->ld_hid; p.ldp = c->ld_hid;
-  p.grid_m = (p.B + 63) / 64;
-  p.grid_n = (p.N + 127) / 128;
-#ifdef PAYNE_STAMPS
-  p.stamps = g_dense_stamps;
-#endif
-  const dim3 block(512);
-  if (out_big_tiles(c, p.B, p.N, p.sel != nullptr)) {
-    // many whole 128 x 256 tiles per CU (C5): persistent workgroups, half the operand bytes per product
-    p.grid_m = p.B / B3_TM; p.grid_n = p.N / B3_TN;
-    PAYNE_LAUNCH(payne_dense_big3_kernel<false>, dim3(c->n_cu), block, b3_lds_bytes(false), s, p);
-    return;
+  else if (plan.halves) PAYNE_LAUNCH_DENSE((payne_dense_dma2hh_kernel<5>), grid, block, s, PAYNE_D3_LEAD_ARGS(p), p);
+  else if (h2 && plan.fixed && plan.own_cu) PAYNE_LAUNCH_DENSE((payne_dense_dma2h_kernel<5, 64>), grid, block, s, PAYNE_D3_LEAD_ARGS(p), p);
+  else if (h2 && plan.fixed) PAYNE_LAUNCH_DENSE((payne_dense_dma2h_kernel<10, 32>), grid, block, s, PAYNE_D3_LEAD_ARGS(p), p);
+  else if (h2) PAYNE_LAUNCH_DENSE((payne_dense_dma2h_kernel<0, 32>), grid, block, s, PAYNE_D3_LEAD_ARGS(p), p);
+  else if (!plan.own_cu) PAYNE_LAUNCH_DENSE((payne_dense_dma3_kernel<0, 2, false>), grid, block, s, PAYNE_D3_LEAD_ARGS(p), p);   // many tiles per CU
+  else if (plan.split_w) {
+    // the weights as fp32 through the port, split into the planes on their way into LDS (28 instead of 36 KB a step)
+    p.W_alt = c->w_out_pad;
+    const unsigned short* keep = p.Wp;
+    p.Wp = reinterpret_cast<const unsigned short*>(freq ? c->w_out_padz : c->w_out_pad);
+    PAYNE_LAUNCH_DENSE((payne_dense_dma3f_kernel<10>), grid, block, s, PAYNE_D3_LEAD_ARGS(p), p);
+    p.Wp = keep;
   }
-  const dim3 grid(p.grid_m * p.grid_n);
-  if ((int)grid.x > c->n_cu) PAYNE_LAUNCH((payne_dense_dma3_kernel<0, 2, false>), grid, block, d3_lds_bytes<2>(), s, PAYNE_D3_LEAD_ARGS(p), p);   // many tiles per CU
-  else if (p.K == 320 && !(c->opts.variant & PAYNE_V_OUT_ROLLED)) {
-    const float* wf = freq ? c->w_out_padz : c->w_out_pad;
-    if (wf && !(c->opts.variant & PAYNE_V_OUT_PLANES) && (!p.sel || c->w_out_pad)) {
-      // the weights as fp32 through the port, split into the planes on their way into LDS (28 instead of 36 KB a step)
-      p.W_alt = c->w_out_pad;
-      const unsigned short* keep = p.Wp;
-      p.Wp = reinterpret_cast<const unsigned short*>(wf);
-      PAYNE_LAUNCH((payne_dense_dma3f_kernel<10>), grid, block, d3_lds_bytes<4>(), s, PAYNE_D3_LEAD_ARGS(p), p);
-      p.Wp = keep;
-    }
-    else PAYNE_LAUNCH((payne_dense_dma3_kernel<10, 4, true>), grid, block, d3_lds_bytes<4>(), s, PAYNE_D3_LEAD_ARGS(p), p);
-  }
-  else PAYNE_LAUNCH((payne_dense_dma3_kernel<0, 4, true>), grid, block, d3_lds_bytes<4>(), s, PAYNE_D3_LEAD_ARGS(p), p);
+  else if (plan.fixed) PAYNE_LAUNCH_DENSE((payne_dense_dma3_kernel<10, 4, true>), grid, block, s, PAYNE_D3_LEAD_ARGS(p), p);
+  else PAYNE_LAUNCH_DENSE((payne_dense_dma3_kernel<0, 4, true>), grid, block, s, PAYNE_D3_LEAD_ARGS(p), p);
 }
 
 // The hidden-layer kernel's leading arguments carry two 16-bit values a dword (n_prep: 15 bits): what does not fit is refused
@@ -998,14 +972,16 @@ static void launch_hidden(DenseParams& p, PrepArgs& pa, hipStream_t s, int n_cu 
   const unsigned i4 = (unsigned)p.K | ((unsigned)(FUSE ? p.K0 : 0) << 16) | ((!FUSE && p.h2_tiles) ? 0x80000000u : 0u);
   const void* p0 = FUSE ? static_cast<const void*>(p.theta) : static_cast<const void*>(p.X);
   const float* p1 = FUSE ? p.W0 : p.Wd;
-  if (!FUSE) PAYNE_LAUNCH((payne_dense_hidden_kernel<false, 4>), grid, block, HK_LDS_BYTES, s, p0, p1, p.b0, p.bias, i0, i1, i2, p.B, i4, p.N, p, pa);
+#define PAYNE_HK_ARGS p0, p1, p.b0, p.bias, i0, i1, i2, p.B, i4, p.N, p, pa
+  if (!FUSE) PAYNE_LAUNCH_DENSE((payne_dense_hidden_kernel<false, 4>), grid, block, s, PAYNE_HK_ARGS);
   else if (p.n_labels <= 4) {
-    if (wide) PAYNE_LAUNCH((payne_dense_hidden_kernel<true, 4, 8>), grid, block, HK_LDS_BYTES, s, p0, p1, p.b0, p.bias, i0, i1, i2, p.B, i4, p.N, p, pa);
-    else PAYNE_LAUNCH((payne_dense_hidden_kernel<true, 4>), grid, block, HK_LDS_BYTES, s, p0, p1, p.b0, p.bias, i0, i1, i2, p.B, i4, p.N, p, pa);
+    if (wide) PAYNE_LAUNCH_DENSE((payne_dense_hidden_kernel<true, 4, 8>), grid, block, s, PAYNE_HK_ARGS);
+    else PAYNE_LAUNCH_DENSE((payne_dense_hidden_kernel<true, 4>), grid, block, s, PAYNE_HK_ARGS);
   } else {
-    if (wide) PAYNE_LAUNCH((payne_dense_hidden_kernel<true, PAYNE_MAX_LABELS, 8>), grid, block, HK_LDS_BYTES, s, p0, p1, p.b0, p.bias, i0, i1, i2, p.B, i4, p.N, p, pa);
-    else PAYNE_LAUNCH((payne_dense_hidden_kernel<true, PAYNE_MAX_LABELS>), grid, block, HK_LDS_BYTES, s, p0, p1, p.b0, p.bias, i0, i1, i2, p.B, i4, p.N, p, pa);
+    if (wide) PAYNE_LAUNCH_DENSE((payne_dense_hidden_kernel<true, PAYNE_MAX_LABELS, 8>), grid, block, s, PAYNE_HK_ARGS);
+    else PAYNE_LAUNCH_DENSE((payne_dense_hidden_kernel<true, PAYNE_MAX_LABELS>), grid, block, s, PAYNE_HK_ARGS);
   }
+#undef PAYNE_HK_ARGS
 }
 
 // ANN forward for the batch -> c->raw [B][npix] (shifted by -1)
@@ -1016,9 +992,41 @@ struct NetRef {
   bool spectral;                      // the spectral net owns the DMA / bf16x3 operand copies and the prep records
   bool freq = false;                  // spectral net: rows written in the frequency domain (c->w_out_p3z)
 };
+// The output layer's kernel for a batch of B through net N (N.freq: the rows go out transformed): every variant bit and every shape
+// that bears on it is tested here.  DESIGN section 1 has the table.
+static OutPlan plan_out(const payne_ctx* c, const NetRef& N, int B) {
+  const unsigned v = c->opts.variant;
+  const int kp = c->w_out_kp, n_out = N.layers[N.n_layers - 1].n_out;
+  OutPlan o;
+  o.sel = N.freq && c->freq_rs_now;
+  const int n_launch = o.sel ? c->T.n1 : n_out;             // (rows of the resampled grid: T.n1 values)
+  o.form = wanted_out_form(v);
+  if (!(N.spectral && c->dma_ok && c->ld_hid >= kp)) o.form = OutForm::Generic;     // hidden widths differ, the continuum network
+  if (o.form >= OutForm::Bf16x3 && !(c->w_out_p3 && c->hid_p3)) o.form = OutForm::F32Dma;
+  if (o.form == OutForm::H2) {
+    // (payne_dense_dma2h_kernel addresses an operand plane by 32-bit byte offsets: rows x pitch x 2 bytes below 2^31)
+    const unsigned long long plane_w = 2ull * (unsigned long long)std::max(n_out, c->T.n1) * (unsigned long long)kp;
+    const unsigned long long plane_x = 2ull * (unsigned long long)c->opts.b_max * (unsigned long long)c->ld_hid;
+    if (plane_w >= (1ull << 31) || plane_x >= (1ull << 31) || !c->w_out_h2 || !(c->act_scale > 0.f) || (N.freq && !c->w_out_h2z)) o.form = OutForm::Bf16x3;
+  }
+  if (o.form == OutForm::Generic) return o;
+  o.grid_m = (B + 63) / 64; o.grid_n = (n_launch + 127) / 128;
+  o.own_cu = o.grid_m * o.grid_n <= c->n_cu;
+  o.fixed = kp == 320 && !(v & PAYNE_V_OUT_ROLLED);        // H = 300 -> 320 columns
+  if (o.form == OutForm::F32Dma) { o.bk64 = kp % 64 == 0 && (v & PAYNE_V_OUT_BK64); return o; }
+  if (B % B3_TM == 0 && n_launch % B3_TN == 0 && (B / B3_TM) * (n_launch / B3_TN) >= 2 * c->n_cu && !(v & PAYNE_V_OUT_SMALL_TILES) && !o.sel) {
+    o.big = true; o.grid_m = B / B3_TM; o.grid_n = n_launch / B3_TN;
+    return o;
+  }
+  if (o.form == OutForm::H2) o.halves = o.fixed && o.own_cu && !(v & PAYNE_V_OUT_WHOLE_TILE);
+  else o.split_w = o.fixed && o.own_cu && (N.freq ? c->w_out_padz : c->w_out_pad) && !(v & PAYNE_V_OUT_PLANES) && (!o.sel || c->w_out_pad);
+  return o;
+}
 // `sed`: a joint likelihood's photometric nets ride in the first hidden-layer launch (sed_tile); *sed is cleared when they did.
 static int run_net(payne_ctx* c, const NetRef& N, const double* theta, int B, double instr_factor, hipStream_t s, bool* sed = nullptr) {
   const int n = N.n_layers;
+  const OutPlan plan = plan_out(c, N, B);
+  const bool use3 = plan.form >= OutForm::Bf16x3, use2h = plan.form == OutForm::H2;   // (the last hidden layer writes that form's planes)
   for (int l = 1; l < n; ++l) {
     DenseParams p{};
     const payne_layer& L = N.layers[l];
@@ -1027,10 +1035,6 @@ static int run_net(payne_ctx* c, const NetRef& N, const double* theta, int B, do
     p.bias_shift = last ? N.out_shift : 0.f;
     p.Y = last ? N.out : N.hid[(l - 1) & 1];
     p.ldy = last ? N.ld_out : N.ld_hid;
-    const bool use3 = N.spectral && out_dma3_ok(c, B, N.layers[n - 1].n_out);
-    // (rows of the resampled grid: the wider of the two output layers sizes the grid)
-    const int n_out_launch = (N.freq && c->freq_rs_now) ? std::max(c->T.n1, N.layers[n - 1].n_out) : N.layers[n - 1].n_out;
-    const bool use2h = use3 && out_dma2h_ok(c, B, n_out_launch, N.freq && c->freq_rs_now) && (!N.freq || c->w_out_h2z);
     if (use3 && l == n - 2) {
       p.Yp = c->hid_p3; p.plane_y = (size_t)c->opts.b_max * c->ld_hid; p.ldp = c->ld_hid;
       if (use2h) { p.yp_half = 1; p.yp_scale = c->act_scale; }
@@ -1088,7 +1092,7 @@ static int run_net(payne_ctx* c, const NetRef& N, const double* theta, int B, do
       cp.target0 = c->chain_calls * (unsigned long long)cp.grid_n;
       cp.B = B; cp.N = N.layers[2].n_out; cp.grid_m = (B + 31) / 32; cp.grid_m_max = (c->opts.b_max + 31) / 32;
       ++c->chain_calls;
-      PAYNE_LAUNCH(payne_dense_chain_kernel, dim3(cp.grid_m_max * cp.grid_n), dim3(256), HK_LDS_BYTES, s, cp);
+      PAYNE_LAUNCH_DENSE(payne_dense_chain_kernel, dim3(cp.grid_m_max * cp.grid_n), dim3(256), s, cp);
       l = n - 2;                                            // (the loop goes on with the output layer)
     } else {
       p.X = N.hid[(l - 2) & 1]; p.ldx = N.ld_hid;
@@ -1102,20 +1106,16 @@ static int run_net(payne_ctx* c, const NetRef& N, const double* theta, int B, do
         return fail(c, PAYNE_E_UNSUPPORTED, "batch x hidden width beyond what the hidden-layer kernel's packed arguments hold (65 535 tiles of 32 x 32)");
       if (!last) launch_hidden<false>(p, pa, s);
       else if (use3) {
-        if (N.freq && c->freq_rs_now) {                      // rows of the resampled grid; pixels if the batch's records say so
+        if (plan.sel) {                                      // rows of the resampled grid; pixels if the batch's records say so
           p.sel = c->rot_flag; p.sel_seq = c->rot_seq;
           p.Wp_alt = c->w_out_p3; p.plane_w_alt = (size_t)p.N * c->w_out_kp; p.bias_alt = p.bias; p.bias_shift_alt = p.bias_shift;
           p.N_alt = p.N; p.ldy_alt = p.ldy;
           p.N = c->T.n1; p.ldy = c->T.n1;
           if (use2h) { p.Wp_alt = c->w_out_h2; p.rscale_alt = c->rscale; }
         }
-        if (use2h) launch_out_dma2h(c, p, s, N.freq);
-        else launch_out_dma3(c, p, s, N.freq);
+        launch_out_planes(c, p, s, plan, N.freq);
       }
-      else if (N.spectral && c->dma_ok && c->ld_hid >= c->w_out_kp && !(c->opts.variant & PAYNE_V_OUT_GENERIC)) {
-        if ((c->w_out_kp % 64) == 0 && (c->opts.variant & PAYNE_V_OUT_BK64)) launch_out_dma<64>(c, p, s);
-        else launch_out_dma<32>(c, p, s);
-      }
+      else if (plan.form == OutForm::F32Dma) launch_out_dma(c, p, s, plan);
       else launch_dense<64, 64, 32, false>(p, s);            // nets whose hidden widths differ, the continuum network
     }
   }
@@ -1203,8 +1203,8 @@ static int run_ann(payne_ctx* c, const double* theta, int B, double instr_factor
                    bool pixels = false) {
   c->prep_valid = false;
   NetRef N{c->layers, c->n_layers, c->n_labels, c->xmin, c->xden, c->hid, c->ld_hid, c->raw, c->T.npix, kBase, true};
-  // (the continuum multiplies pixel by pixel; out_dma3_ok: the launch that reads the restated weights is the one that runs)
-  N.freq = c->freq_ok && !pixels && !(c->has_cont && with_cont) && out_dma3_ok(c, B, c->T.npix);
+  // (the continuum multiplies pixel by pixel; the plan's form: the launch that reads the restated weights is the one that runs)
+  N.freq = c->freq_ok && !pixels && !(c->has_cont && with_cont) && plan_out(c, N, B).form >= OutForm::Bf16x3;
   // rows of a resampled grid need this batch's records (their writers report a candidate that does not rotate) and a first layer
   // fused into the hidden-layer launch (>= 3 layers), and the plain post kernel behind them
   if (N.freq && c->freq_rs && !(c->prep && c->obs_bound && !(c->opts.variant & PAYNE_V_NO_PREP) && c->n_layers >= 3 && !c->has_lsf)) N.freq = false;

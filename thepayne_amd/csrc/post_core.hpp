@@ -1254,7 +1254,7 @@ PAYNE_HD void prep_candidate(const PostTables& T, const double* th, double instr
     // Geometric grids (ln lam_i = ln0 + i dln to 1e-12, verified at set-up): the two counts by ARITHMETIC.  lam_i (1 + rv/c) <= wl
     // <=> i <= (ln wl - dop - ln0) / dln =: t, and ln wl = ln(obs_min) + ln(1 - pad) with the first term the context's and the
     // second a short series: no logarithm, no table value, i.e. no second memory round trip in the hidden-layer launch's last
-    // workgroups (0.8 us of that launch: the twin PAYNE_EXP_PREP=1).  t is good to ~1e-9 pixel (rounding) + 1e-12 / dln (the grid's
+    // workgroups (0.8 us of that launch: NOTES R6.11).  t is good to ~1e-9 pixel (rounding) + 1e-12 / dln (the grid's
     // own deviation, < 3e-7 pixel): where its fraction is more than 1e-5 from an integer the count floor(t) + 1 is THE count the
     // table gives; the rest (one candidate in 50 000) and every other grid take the table as before.
     bool have = false;
@@ -1281,22 +1281,14 @@ PAYNE_HD void prep_candidate(const PostTables& T, const double* th, double instr
     const bool ina = ga >= 1 && ga < n, inb = gb >= 1 && gb < n;
     const double a0 = T.lam[ina ? ga - 1 : 0] * S.one_plus, a1 = T.lam[ina ? ga : 0] * S.one_plus;
     const double b0 = T.lam[inb ? gb - 1 : 0] * S.one_plus, b1 = T.lam[inb ? gb : 0] * S.one_plus;
-#if defined(PAYNE_EXP_PREP) && (PAYNE_EXP_PREP & 1)      /* timing twin: the guesses taken on trust (no second memory round trip) */
-    const bool oka = ina && a0 == a0 + 0.0 * a1, okb = inb && b0 == b0 + 0.0 * b1;
-#else
     const bool oka = ina && !(a0 > S.wl) && (a1 > S.wl);          // pred true at ga-1, false at ga
     const bool okb = inb && (b0 < S.wh) && !(b1 < S.wh);
-#endif
     S.win_below = oka ? ga : count_search<false>(T, S.one_plus, S.wl, ga);
     S.win_notabove = okb ? gb : count_search<true>(T, S.one_plus, S.wh, gb);
     }
     S.win_ready = 1;
-#if defined(PAYNE_EXP_PREP) && (PAYNE_EXP_PREP & 2)      /* timing twin: the window left to the post kernel */
-    S.w_ready = 0;
-#else
     W = window_from_counts(T, S.dop, S.g_a, S.win_below, S.win_notabove);
     S.w_ready = 1;
-#endif
   }
   S.W = W;
 }
