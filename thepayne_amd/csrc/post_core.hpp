@@ -1761,10 +1761,17 @@ PAYNE_HD bool obs_fast_ok(const PostTables& T, int blk) {
   return 2 * (npad - T.nobs) <= T.nobs && blk <= kObsPad;
 }
 // the OU records of one block of the thread, requested (one 16-byte load each; the table is padded past nobs)
-template <int OU>
+// (IN_ORDER, for a block requested long before its loop: the requests leave in the order the loop consumes the records -- loads come
+//  back in order, and left to itself the compiler asks for record 0 seventh)
+template <int OU, bool IN_ORDER = false>
 PAYNE_HD void obs_fast_issue(int nthr, const PostTables& T, int base, ObsRec (&rec)[OU]) {
 #pragma unroll
-  for (int q = 0; q < OU; ++q) rec[q] = T.obs_rec[(unsigned)(base + q * nthr)];
+  for (int q = 0; q < OU; ++q) {
+    rec[q] = T.obs_rec[(unsigned)(base + q * nthr)];
+#ifdef __HIP_DEVICE_COMPILE__
+    if constexpr (IN_ORDER) asm volatile("" ::: "memory");
+#endif
+  }
 }
 template <int OU>
 PAYNE_HD void obs_fast_block(const ObsRec (&rec)[OU], const ObsFastConsts& c, const float* __restrict__ conv, float& acc, unsigned& worst) {

@@ -120,8 +120,9 @@ template <class Ex> struct ex_lds_tail { static constexpr bool value = false; };
 #ifdef __HIP_DEVICE_COMPILE__
 // a barrier that waits for the wave's LDS traffic only: global loads stay in flight across it (__syncthreads() drains them)
 __device__ __forceinline__ void post_lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
-template <int M, int P, int NT, class BP, class TP>
-__device__ __forceinline__ BP fft_fixed_passes_lds(int tid, BP src, BP dst, TP twf, unsigned sign_last) {
+// (MARK: the diagnostic build's cycle stamp behind every pass, as Ex::par leaves one -- the stamped phases keep their numbers)
+template <int M, int P, int NT, bool MARK, class Ex, class BP, class TP>
+__device__ __forceinline__ BP fft_fixed_passes_lds(Ex& ex, int tid, BP src, BP dst, TP twf, unsigned sign_last) {
   if constexpr (P >= M) {
     return src;
   } else {
@@ -129,7 +130,8 @@ __device__ __forceinline__ BP fft_fixed_passes_lds(int tid, BP src, BP dst, TP t
     constexpr bool last = (P * R >= M);
     fft_pass_fixed<R, M, P, NT>(tid, src, dst, twf, last ? sign_last : 0u, false);
     post_lds_barrier();
-    return fft_fixed_passes_lds<M, P * R, NT>(tid, dst, src, twf, sign_last);
+    if constexpr (MARK) ex.mark(0);
+    return fft_fixed_passes_lds<M, P * R, NT, MARK>(ex, tid, dst, src, twf, sign_last);
   }
 }
 // The tail of a likelihood evaluation as ONE phase: the records of the observed pixels (16 bytes a pixel, 58 KB per candidate at
@@ -138,12 +140,37 @@ __device__ __forceinline__ BP fft_fixed_passes_lds(int tid, BP src, BP dst, TP t
 // __syncthreads(), waits for every outstanding load); the loop then finds them in registers.  z: the tapered spectrum (Y of
 // rfft_taper_phase), zo: the other buffer.  Returns the thread's chi^2 partial.
 template <int M, int NT, int OU, class Ex>
-__device__ __forceinline__ double inverse_and_obs(int tid, const PostTables& T, const CandState& S, const Window& W, const c32* twf,
+__device__ __forceinline__ double inverse_and_obs(Ex& ex, int tid, const PostTables& T, const CandState& S, const Window& W, const c32* twf,
                                                   c32* z, c32* zo) {
   ObsRec rec[OU];
   obs_fast_issue<OU>(NT, T, tid, rec);
-  auto r = fft_fixed_passes_lds<M, 1, NT>(tid, Ex::buf(z), Ex::buf(zo), Ex::twid(twf), 0x80000000u);
+  auto r = fft_fixed_passes_lds<M, 1, NT, false>(ex, tid, Ex::buf(z), Ex::buf(zo), Ex::twid(twf), 0x80000000u);
   const float* conv = (r == Ex::buf(z)) ? (const float*)z : (const float*)zo;
+  return phase_obs<OU>(tid, NT, T, S, W, conv, nullptr, -1, false, &rec);
+}
+// ... and, where the twiddle table is in LDS too, the WHOLE instrumental stage as that one phase: the records are requested one
+// transform earlier, in front of the FORWARD passes.  From the resampling on nothing the stage does leaves the compute unit (passes,
+// Gaussian product, passes: LDS and arithmetic), so the port from L2 is idle for nine barrier intervals in front of the loop that
+// needs 58 KB through it -- twice, for the two workgroups of a compute unit.  Same values in the same order as conv_stage +
+// inverse_and_obs; the forward passes and the product run behind LDS-only barriers like the inverse ones (the vector-memory counter
+// is never waited for between the request and the loop: a CPU test reads that off the assembly).  x: the resampled spectrum, xo: the
+// other buffer.  (With the table in global memory a pass's own loads would queue behind the records, in order: such kernels keep
+// inverse_and_obs.)
+template <int M, int NT, int OU, class Ex>
+__device__ __forceinline__ double stage_and_obs(Ex& ex, int tid, const PostTables& T, const CandState& S, const Window& W, const c32* twf,
+                                                c32* x, c32* xo) {
+  ObsRec rec[OU];
+  obs_fast_issue<OU, true>(NT, T, tid, rec);
+  auto tw = Ex::twid(twf);
+  auto z = fft_fixed_passes_lds<M, 1, NT, true>(ex, tid, Ex::buf(x), Ex::buf(xo), tw, 0u);
+  auto zo = (z == Ex::buf(x)) ? Ex::buf(xo) : Ex::buf(x);
+  TaperArgs ta{};
+  ta.g_c2 = W.g_c2;
+  rfft_taper_phase<false, unroll_for(2 * M / NT) / 4>(tid, NT, z, M, Ex::twid(twf + plan_total(M)), 1, ta);
+  post_lds_barrier();
+  ex.mark(0);
+  auto r = fft_fixed_passes_lds<M, 1, NT, false>(ex, tid, z, zo, tw, 0x80000000u);
+  const float* conv = (r == Ex::buf(x)) ? (const float*)x : (const float*)xo;
   return phase_obs<OU>(tid, NT, T, S, W, conv, nullptr, -1, false, &rec);
 }
 #endif
@@ -337,23 +364,38 @@ PAYNE_SEQ void run_candidate(Ex& ex, const PostTables& T, const c32* twf, const 
       // (a stage that gathers its input itself has all of it in registers before it stores anything: its output goes where its
       //  input was -- one 256 KB buffer per workgroup in flight instead of two, 67 MB for the 256 workgroups of a C5 launch)
       // chi^2 alone from a window of the fixed geometry's own length, whole blocks of records: the inverse transform and the
-      // observed-grid loop as one phase, the records requested ahead of the transform (inverse_and_obs)
+      // observed-grid loop as one phase, the records requested ahead of the transform (inverse_and_obs) -- ahead of the FORWARD
+      // transform, the whole stage one phase, where the passes' table is in LDS (stage_and_obs)
       bool fused_tail = false;
-      if constexpr (ex_lds_tail<Ex>::value && LOG2N > 0 && UX <= 8) {    // (a thread's block of records stays in registers: 4 x UX of them)
+      constexpr bool kTail = ex_lds_tail<Ex>::value && LOG2N > 0 && UX <= 8;    // (a thread's block of records stays in registers: 4 x UX of them)
+      constexpr bool kAhead = kTail && Ex::kTwLds;                              // ... across the forward transform too: stage_and_obs
+      if constexpr (kTail) {
         fused_tail = !gather && out == nullptr && T.obs_f1 != nullptr && T.npoly == 0 && W.n2 == (1 << LOG2N) && obs_fast_ok(T, UX * NT);
       }
-      on_grid = conv_stage<LOG2N, NT, false>(ex, T, twf, gather ? spec : work, spec, W.n2, ta, no_edge, gather ? spec : nullptr, gather ? &W : nullptr,
-                                             false, false, true, fused_tail);
 #ifdef __HIP_DEVICE_COMPILE__
-      if constexpr (ex_lds_tail<Ex>::value && LOG2N > 0 && UX <= 8) {
+      if constexpr (kAhead) {
         if (fused_tail) {
-          c32* z = (c32*)const_cast<float*>(on_grid);
-          c32* zo = (on_grid == work) ? (c32*)spec : (c32*)work;
-          ex.par([&](int t, int) { store_partial(t, inverse_and_obs<(1 << LOG2N) / 2, NT, UX, Ex>(t, T, S, W, twf, z, zo), red); });
+          ex.par([&](int t, int) {
+            store_partial(t, stage_and_obs<(1 << LOG2N) / 2, NT, UX, Ex>(ex, t, T, S, W, twf, (c32*)work, (c32*)spec), red);
+          });
           tail_done = true;
         }
       }
 #endif
+      if (!tail_done) {
+        on_grid = conv_stage<LOG2N, NT, false>(ex, T, twf, gather ? spec : work, spec, W.n2, ta, no_edge, gather ? spec : nullptr, gather ? &W : nullptr,
+                                               false, false, true, fused_tail && !kAhead);
+#ifdef __HIP_DEVICE_COMPILE__
+        if constexpr (kTail && !kAhead) {
+          if (fused_tail) {
+            c32* z = (c32*)const_cast<float*>(on_grid);
+            c32* zo = (on_grid == work) ? (c32*)spec : (c32*)work;
+            ex.par([&](int t, int) { store_partial(t, inverse_and_obs<(1 << LOG2N) / 2, NT, UX, Ex>(ex, t, T, S, W, twf, z, zo), red); });
+            tail_done = true;
+          }
+        }
+#endif
+      }
     }
   }
   const Window& W = *Wp;
