@@ -952,3 +952,57 @@ def test_row_domains_switch_within_one_context(Engine):
     assert eng.kernels_used()["rows"] == "pixels" and not np.array_equal(with_c, ref_l, equal_nan=True)
     eng.set_continuum(None)
     assert np.array_equal(eng.lnlike_batch(th).cpu().numpy(), ref_l, equal_nan=True) and eng.kernels_used()["rows"] == "frequency"
+
+
+def _lsf_vector(obs):
+    return 0.075 * (1.0 + 0.3 * (obs - obs.mean()) / (obs.max() - obs.min()))
+
+
+def test_lsf_chunks_are_the_batch_row_for_row(Engine):
+    """The global-memory LSF form takes 256 candidates a launch, so a batch of 300 is two launches, the second over rows, records and
+    theta at an offset: every row is what it is as a batch of its own on a fresh context, to the bit; removing the vector leaves the
+    context as one that never had it (frequency rows again), and binding it again gives the first result again."""
+    raw, obs, flux, eflux = yst_problem("small", H=64)
+    lsf = _lsf_vector(obs)
+    th = theta_full(synth.draw_candidates(300, seed=12))
+    th[7, 5] = 0.0; th[290, 5] = 0.0                                # one candidate that does not rotate in each chunk
+
+    def fresh(bound=True):
+        eng = Engine(_net(raw), obs=(obs, flux, eflux), b_max=320, variant=128)       # PAYNE_V_LSF_GLOBAL
+        if bound:
+            eng.set_lsf(lsf)
+        return eng
+
+    def both(eng, t):
+        return eng.lnlike_batch(t).cpu().numpy(), eng.predict_batch(t, stage=2).cpu().numpy()
+    parts = [both(fresh(), th[:256]), both(fresh(), th[256:])]
+    ref_l, ref_2 = (np.concatenate([p[k] for p in parts]) for k in (0, 1))
+    assert np.isfinite(ref_l).sum() > 150                           # (the comparison below is not one of NaN with NaN)
+    eng = fresh()
+    for _ in range(2):
+        lnl, sp = both(eng, th)
+        assert np.array_equal(lnl, ref_l, equal_nan=True) and np.array_equal(sp, ref_2, equal_nan=True)
+        eng.set_lsf(None)
+        assert np.array_equal(eng.lnlike_batch(th).cpu().numpy(), fresh(bound=False).lnlike_batch(th).cpu().numpy(), equal_nan=True)
+        assert eng.kernels_used()["rows"] == "frequency"
+        eng.set_lsf(lsf)
+
+
+def test_lsf_chunks_with_photometry_are_the_batch_row_for_row(Engine):
+    """The same split with a photometric model bound (joint likelihood): the second launch reads the magnitudes at its offset too."""
+    raw, obs, flux, eflux = yst_problem("small", H=64)
+    phot = synth.make_phot_nets()
+    th9 = synth.draw_candidates_c3(300, seed=12)
+
+    def fresh():
+        eng = Engine(_net(raw), obs=(obs, flux, eflux), phot=phot, obs_phot=synth.c3_obs_phot(phot["filters"]), photscale=True,
+                     b_max=320, variant=128)
+        eng.set_lsf(_lsf_vector(obs))
+        return eng
+    eng = fresh()
+    th = np.full((300, eng.ncols), np.nan)
+    th[:, 0:6] = th9[:, 0:6]; th[:, 7] = th9[:, 6]; th[:, eng.phot_off] = th9[:, 7]; th[:, eng.phot_off + 2] = th9[:, 8]
+    th[7, 5] = 0.0; th[290, 5] = 0.0
+    ref = np.concatenate([fresh().lnlike_batch(th[:256]).cpu().numpy(), fresh().lnlike_batch(th[256:]).cpu().numpy()])
+    assert np.isfinite(ref).sum() > 150
+    assert np.array_equal(eng.lnlike_batch(th).cpu().numpy(), ref, equal_nan=True)

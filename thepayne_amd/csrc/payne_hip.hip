@@ -76,8 +76,8 @@ struct payne_ctx {
   // [3][b_max][ld_hid] (written by the hidden-layer kernel's epilogue; zero beyond the hidden width)
   unsigned short* w_out_p3 = nullptr; unsigned short* hid_p3 = nullptr;
   // the same output layer restated for rows in the frequency domain (host_tables.hpp freq_rows): what the likelihood and the
-  // predictions past stage 0 run when the post kernel can start from the transform (freq_ok); raw_freq: the rows now in c->raw
-  unsigned short* w_out_p3z = nullptr; const float* bias_z = nullptr; bool freq_ok = false, raw_freq = false;
+  // predictions past stage 0 run when the post kernel can start from the transform (freq_ok)
+  unsigned short* w_out_p3z = nullptr; const float* bias_z = nullptr; bool freq_ok = false;
   const float* w_out_padz = nullptr;    // the restated layer as fp32 [n][w_out_kp] (payne_dense_dma3f_kernel splits it on the way into LDS)
   // two fp16 planes an operand (payne_dense_dma2h_kernel): the weights' planes [2][n][w_out_kp] with row n scaled by 2^e[n], rscale[n] =
   // 2^-e[n] / act_scale; act_scale: the power of two the last hidden layer is written with (calibrated on the label box; 0 = not available)
@@ -93,16 +93,13 @@ struct payne_ctx {
   unsigned long long* chain_flags = nullptr; unsigned long long chain_calls = 0;
   // freq_rs: the restated layer is that of the RESAMPLED spectrum (model grids that are not a power of two long: n1 rows of n1
   // values); a batch with a candidate that does not rotate falls back to pixels ON THE DEVICE (rot_flag: a word the records'
-  // writers set to rot_seq, read by the output layer and the post kernel of the same batch; freq_rs_now: this batch was launched so)
-  bool freq_rs = false, freq_rs_now = false; unsigned long long* rot_flag = nullptr; unsigned long long rot_seq = 0;
+  // writers set to rot_seq, read by the output layer and the post kernel of the same batch; rot_seq: the last number issued)
+  bool freq_rs = false; unsigned long long* rot_flag = nullptr; unsigned long long rot_seq = 0;
   size_t post_lds = 0;
   void (*post_fn_lean)(PAYNE_POST_SIG) = nullptr;   // likelihood-only instantiation (same LDS)
   bool post_tw_lds = false;
   int n_cu = 256;                       // compute units of the device (MI355X: 256)
   bool lean_available = false;          // a likelihood-only instantiation exists for this spectrum length (it can carry a walk's tail)
-  // a sampler's walk in progress asks the likelihood batch being enqueued to make the next step's proposals ahead (rwalk_spec_wave,
-  // in the hidden-layer launch): set by lnlike_impl for the duration of the call; spec_launched: that launch carried them
-  const void* spec_walk = nullptr; const void* spec_w = nullptr; int spec_step = 0, spec_K = 0; bool spec_launched = false;
   PostTables* d_T = nullptr;          // device copy of T
   post_kernel_fn post_fn = nullptr;
   float* big_ws = nullptr;            // global spectrum buffers of payne_post_big_kernel (n1 > 16384)
@@ -135,7 +132,6 @@ struct payne_ctx {
   std::vector<void*> lsf_owned;
   bool obs_bound = false;
   CandState* prep = nullptr;      // [b_max] per-candidate records of the post kernel (written by the first dense launch)
-  bool prep_valid = false;        // ... as of the last run_ann
   // photometry
   bool has_phot = false, has_obs_phot = false;
   PhotTables P{};
@@ -151,6 +147,7 @@ struct payne_ctx {
   double prof_ms[4] = {0, 0, 0, 0};
   long long prof_n[4] = {0, 0, 0, 0};
   const char* last_kernel[4] = {"", "", "", ""};   // what the last call launched, per kind (payne_last_kernel)
+  bool last_rows_freq = false;                     // ... and whether its post kernel was handed rows in the frequency domain (kind 4)
 };
 
 // RAII bracket of one timed launch.  The event pair is handed to the launch itself (hipExtLaunchKernelGGL:
@@ -228,6 +225,37 @@ static int fail(payne_ctx* c, int code, const std::string& msg) {
   return code;
 }
 
+// A context being reconfigured: on its own device, with nothing in flight (no kernel may still read what is about to be freed or
+// re-bound); the caller's device again on the way out.
+struct DeviceScope {
+  int prev = 0, dev;
+  explicit DeviceScope(const payne_ctx* c) : dev(c->device) { (void)hipGetDevice(&prev); if (prev != dev) (void)hipSetDevice(dev); (void)hipDeviceSynchronize(); }
+  ~DeviceScope() { if (prev != dev) (void)hipSetDevice(prev); }
+};
+
+// A network's layers into the context's own list `dst`: shapes checked (`who`: what the messages call the network), weights whose K
+// is no multiple of 4 replaced by a zero-padded copy in `bag` (float4 tile loads).  *maxh: the widest hidden layer.
+static int adopt_layers(payne_ctx* c, const payne_model_desc* m, payne_layer* dst, std::vector<void*>& bag, const std::string& who, int* maxh) {
+  *maxh = 0;
+  for (int l = 0; l < m->n_layers; ++l) {
+    const payne_layer& L = m->layers[l];
+    if (!L.w || !L.b || L.n_in <= 0 || L.n_out <= 0) return fail(c, PAYNE_E_INVALID, who + "layer with null weights or bad shape");
+    if (l > 0 && L.n_in != m->layers[l - 1].n_out) return fail(c, PAYNE_E_INVALID, who + "layer shapes do not chain");
+    dst[l] = L;
+    if (l > 0 && (L.n_in & 3)) {
+      const int Kp = (L.n_in + 3) & ~3;
+      float* wp = nullptr;
+      if (int rc = dev_alloc(c, (size_t)L.n_out * Kp, &wp, bag)) return rc;
+      const hipError_t he = hipMemcpy2D(wp, (size_t)Kp * 4, L.w, (size_t)L.n_in * 4, (size_t)L.n_in * 4, L.n_out, hipMemcpyDeviceToDevice);
+      if (he != hipSuccess) return fail(c, PAYNE_E_HIP, std::string("hipMemcpy2D: ") + hipGetErrorString(he));
+      dst[l].w = wp;
+      dst[l].n_in = Kp;             // padded K (extra columns are zero)
+    }
+    if (l + 1 < m->n_layers) *maxh = std::max(*maxh, L.n_out);
+  }
+  return PAYNE_OK;
+}
+
 static int sync_tables(payne_ctx* c) {
   if (!c->d_T) return PAYNE_OK;
   HIPCHK(c, hipMemcpy(c->d_T, &c->T, sizeof(PostTables), hipMemcpyHostToDevice));
@@ -291,7 +319,7 @@ extern "C" int payne_activation_batch(const float* z, int n, int act, float* out
   return hipGetLastError() == hipSuccess ? PAYNE_OK : PAYNE_E_HIP;
 }
 extern "C" const char* payne_last_kernel(const payne_ctx* c, int kind) {
-  if (c && kind == 4) return c->raw_freq ? "frequency" : "pixels";        // what the output layer handed to the post kernel
+  if (c && kind == 4) return c->last_rows_freq ? "frequency" : "pixels";        // what the output layer handed to the post kernel
   return (c && kind >= 0 && kind < 4) ? c->last_kernel[kind] : "";
 }
 
@@ -604,22 +632,7 @@ extern "C" int payne_ctx_create(const payne_model_desc* model, const payne_obs_d
     if (model->layers[0].n_in != model->n_labels) return bail(fail(c, PAYNE_E_INVALID, "first layer n_in != n_labels"));
     if (model->layers[model->n_layers - 1].n_out != model->npix) return bail(fail(c, PAYNE_E_INVALID, "last layer n_out != npix"));
     int maxh = 0;
-    for (int l = 0; l < model->n_layers; ++l) {
-      const payne_layer& L = model->layers[l];
-      if (!L.w || !L.b || L.n_in <= 0 || L.n_out <= 0) return bail(fail(c, PAYNE_E_INVALID, "layer with null weights or bad shape"));
-      if (l > 0 && L.n_in != model->layers[l - 1].n_out) return bail(fail(c, PAYNE_E_INVALID, "layer shapes do not chain"));
-      c->layers[l] = L;
-      if (l > 0 && (L.n_in & 3)) {   // float4 tile loads need K % 4 == 0: keep a zero-padded copy
-        const int Kp = (L.n_in + 3) & ~3;
-        float* wp = nullptr;
-        if ((rc = dev_alloc(c, (size_t)L.n_out * Kp, &wp, c->owned))) return bail(rc);
-        he = hipMemcpy2D(wp, (size_t)Kp * 4, L.w, (size_t)L.n_in * 4, (size_t)L.n_in * 4, L.n_out, hipMemcpyDeviceToDevice);
-        if (he != hipSuccess) return bail(fail(c, PAYNE_E_HIP, std::string("hipMemcpy2D: ") + hipGetErrorString(he)));
-        c->layers[l].w = wp;
-        c->layers[l].n_in = Kp;     // padded K (extra columns are zero)
-      }
-      if (l + 1 < model->n_layers) maxh = std::max(maxh, L.n_out);
-    }
+    if ((rc = adopt_layers(c, model, c->layers, c->owned, "", &maxh))) return bail(rc);
     if ((rc = create_dense_operands(c, model, opts, maxh))) return bail(rc);
     c->n_layers = model->n_layers;
     c->n_labels = model->n_labels;
@@ -704,13 +717,8 @@ extern "C" int payne_ctx_create(const payne_model_desc* model, const payne_obs_d
 extern "C" int payne_ctx_set_obs(payne_ctx* c, const payne_obs_desc* obs) {
   if (!c) return PAYNE_E_INVALID;
   if (!c->has_model) return fail(c, PAYNE_E_INVALID, "context has no spectral model");
-  int prev = 0;
-  (void)hipGetDevice(&prev);
-  if (prev != c->device) (void)hipSetDevice(c->device);
-  (void)hipDeviceSynchronize();           // no kernel may still read the old tables
-  int rc = bind_obs(c, obs);
-  if (prev != c->device) (void)hipSetDevice(prev);
-  return rc;
+  DeviceScope ds(c);
+  return bind_obs(c, obs);
 }
 
 // Continuum network (ystpred.PayneSpecPredict(Cnnpath=...)): weights as for the spectral model; the label
@@ -718,49 +726,31 @@ extern "C" int payne_ctx_set_obs(payne_ctx* c, const payne_obs_desc* obs) {
 extern "C" int payne_ctx_set_continuum(payne_ctx* c, const payne_model_desc* cont) {
   if (!c) return PAYNE_E_INVALID;
   if (!c->has_model) return fail(c, PAYNE_E_INVALID, "context has no spectral model");
-  int prev = 0;
-  (void)hipGetDevice(&prev);
-  if (prev != c->device) (void)hipSetDevice(c->device);
-  (void)hipDeviceSynchronize();
+  DeviceScope ds(c);
   for (void* p : c->cont_owned) (void)hipFree(p);
   c->cont_owned.clear();
   c->has_cont = false;
-  auto done = [&](int rc) { if (prev != c->device) (void)hipSetDevice(prev); return rc; };
-  if (!cont) return done(PAYNE_OK);
-  if (cont->n_layers < 3 || cont->n_layers > PAYNE_MAX_LAYERS) return done(fail(c, PAYNE_E_INVALID, "continuum.n_layers must be 3..8"));
-  if (cont->n_labels != c->n_labels) return done(fail(c, PAYNE_E_INVALID, "continuum.n_labels != model.n_labels"));
+  if (!cont) return PAYNE_OK;
+  if (cont->n_layers < 3 || cont->n_layers > PAYNE_MAX_LAYERS) return fail(c, PAYNE_E_INVALID, "continuum.n_layers must be 3..8");
+  if (cont->n_labels != c->n_labels) return fail(c, PAYNE_E_INVALID, "continuum.n_labels != model.n_labels");
   if (!cont->xmin || !cont->xmax || !cont->wavelength || cont->npix < 2)
-    return done(fail(c, PAYNE_E_INVALID, "continuum.xmin/xmax/wavelength missing or npix < 2"));
+    return fail(c, PAYNE_E_INVALID, "continuum.xmin/xmax/wavelength missing or npix < 2");
   if (cont->layers[0].n_in != cont->n_labels || cont->layers[cont->n_layers - 1].n_out != cont->npix)
-    return done(fail(c, PAYNE_E_INVALID, "continuum layer shapes do not match n_labels / npix"));
+    return fail(c, PAYNE_E_INVALID, "continuum layer shapes do not match n_labels / npix");
   int rc = PAYNE_OK, maxh = 0;
-  for (int l = 0; l < cont->n_layers; ++l) {
-    const payne_layer& L = cont->layers[l];
-    if (!L.w || !L.b || L.n_in <= 0 || L.n_out <= 0) return done(fail(c, PAYNE_E_INVALID, "continuum layer with null weights or bad shape"));
-    if (l > 0 && L.n_in != cont->layers[l - 1].n_out) return done(fail(c, PAYNE_E_INVALID, "continuum layer shapes do not chain"));
-    c->clayers[l] = L;
-    if (l > 0 && (L.n_in & 3)) {            // float4 tile loads need K % 4 == 0: zero-padded copy
-      const int Kp = (L.n_in + 3) & ~3;
-      float* wp = nullptr;
-      if ((rc = dev_alloc(c, (size_t)L.n_out * Kp, &wp, c->cont_owned))) return done(rc);
-      hipError_t he = hipMemcpy2D(wp, (size_t)Kp * 4, L.w, (size_t)L.n_in * 4, (size_t)L.n_in * 4, L.n_out, hipMemcpyDeviceToDevice);
-      if (he != hipSuccess) return done(fail(c, PAYNE_E_HIP, std::string("hipMemcpy2D: ") + hipGetErrorString(he)));
-      c->clayers[l].w = wp; c->clayers[l].n_in = Kp;
-    }
-    if (l + 1 < cont->n_layers) maxh = std::max(maxh, L.n_out);
-  }
+  if ((rc = adopt_layers(c, cont, c->clayers, c->cont_owned, "continuum ", &maxh))) return rc;
   c->cn_layers = cont->n_layers; c->cn_npix = cont->npix; c->cn_ld_hid = (maxh + 31) & ~31;
   for (int d = 0; d < cont->n_labels; ++d) { c->cxmin[d] = cont->xmin[d]; c->cxden[d] = cont->xmax[d] - cont->xmin[d]; }
-  if ((rc = dev_alloc(c, (size_t)c->opts.b_max * c->cn_ld_hid, &c->chid[0], c->cont_owned))) return done(rc);
-  if ((rc = dev_alloc(c, (size_t)c->opts.b_max * c->cn_ld_hid, &c->chid[1], c->cont_owned))) return done(rc);
-  if ((rc = dev_alloc(c, (size_t)c->opts.b_max * cont->npix, &c->cont_raw, c->cont_owned, false))) return done(rc);
+  if ((rc = dev_alloc(c, (size_t)c->opts.b_max * c->cn_ld_hid, &c->chid[0], c->cont_owned))) return rc;
+  if ((rc = dev_alloc(c, (size_t)c->opts.b_max * c->cn_ld_hid, &c->chid[1], c->cont_owned))) return rc;
+  if ((rc = dev_alloc(c, (size_t)c->opts.b_max * cont->npix, &c->cont_raw, c->cont_owned, false))) return rc;
   // host tables: F_nu -> F_lambda factor (constants cancel in the median normalisation) and the np.interp map
   const int npc = cont->npix, npix = c->T.npix;
   std::vector<double> scale(npc), frac(npix);
   std::vector<int> idx(npix);
   const double* wc = cont->wavelength;
   for (int i = 1; i < npc; ++i)
-    if (!(wc[i] > wc[i - 1])) return done(fail(c, PAYNE_E_INVALID, "continuum.wavelength must be strictly increasing"));
+    if (!(wc[i] > wc[i - 1])) return fail(c, PAYNE_E_INVALID, "continuum.wavelength must be strictly increasing");
   const double lref = wc[npc / 2];
   for (int i = 0; i < npc; ++i) { const double r = lref / wc[i]; scale[i] = r * r; }
   for (int i = 0; i < npix; ++i) {
@@ -771,11 +761,11 @@ extern "C" int payne_ctx_set_continuum(payne_ctx* c, const payne_model_desc* con
     idx[i] = k;
     frac[i] = (x - wc[k]) / (wc[k + 1] - wc[k]);
   }
-  if ((rc = upload(c, scale, &c->cont_scale, c->cont_owned))) return done(rc);
-  if ((rc = upload(c, idx, &c->cont_idx, c->cont_owned))) return done(rc);
-  if ((rc = upload(c, frac, &c->cont_frac, c->cont_owned))) return done(rc);
+  if ((rc = upload(c, scale, &c->cont_scale, c->cont_owned))) return rc;
+  if ((rc = upload(c, idx, &c->cont_idx, c->cont_owned))) return rc;
+  if ((rc = upload(c, frac, &c->cont_frac, c->cont_owned))) return rc;
   c->has_cont = true;
-  return done(PAYNE_OK);
+  return PAYNE_OK;
 }
 
 // LSF vector for the instrumental broadening: `lsf[n]` = Gaussian dispersion (AA) at each pixel of the bound
@@ -784,45 +774,41 @@ extern "C" int payne_ctx_set_continuum(payne_ctx* c, const payne_model_desc* con
 static int set_lsf_impl(payne_ctx* c, const double* lsf_wave, const double* lsf, int n) {
   if (!c) return PAYNE_E_INVALID;
   if (!c->has_model) return fail(c, PAYNE_E_INVALID, "context has no spectral model");
-  int prev = 0;
-  (void)hipGetDevice(&prev);
-  if (prev != c->device) (void)hipSetDevice(c->device);
-  (void)hipDeviceSynchronize();
+  DeviceScope ds(c);
   for (void* p : c->lsf_owned) (void)hipFree(p);
   c->lsf_owned.clear();
   c->has_lsf = false;
-  auto done = [&](int rc) { if (prev != c->device) (void)hipSetDevice(prev); return rc; };
-  if (!lsf) return done(PAYNE_OK);
-  if (!c->obs_bound) return done(fail(c, PAYNE_E_INVALID, "bind the observed grid before its LSF vector"));
-  if (!lsf_wave && n != c->T.nobs) return done(fail(c, PAYNE_E_INVALID, "the LSF vector must have one entry per observed pixel"));
-  if (lsf_wave && n < 2) return done(fail(c, PAYNE_E_INVALID, "an LSF vector on its own wavelengths needs at least two entries"));
+  if (!lsf) return PAYNE_OK;
+  if (!c->obs_bound) return fail(c, PAYNE_E_INVALID, "bind the observed grid before its LSF vector");
+  if (!lsf_wave && n != c->T.nobs) return fail(c, PAYNE_E_INVALID, "the LSF vector must have one entry per observed pixel");
+  if (lsf_wave && n < 2) return fail(c, PAYNE_E_INVALID, "an LSF vector on its own wavelengths needs at least two entries");
   for (int i = 0; i < n; ++i)
-    if (!(lsf[i] > 0.0)) return done(fail(c, PAYNE_E_INVALID, "LSF dispersions must be positive"));
+    if (!(lsf[i] > 0.0)) return fail(c, PAYNE_E_INVALID, "LSF dispersions must be positive");
   if (lsf_wave)
     for (int i = 1; i < n; ++i)
-      if (!(lsf_wave[i] > lsf_wave[i - 1])) return done(fail(c, PAYNE_E_INVALID, "the LSF vector's wavelengths must be strictly increasing"));
+      if (!(lsf_wave[i] > lsf_wave[i - 1])) return fail(c, PAYNE_E_INVALID, "the LSF vector's wavelengths must be strictly increasing");
   std::vector<double> v(lsf, lsf + n);
   int rc;
-  if ((rc = upload(c, v, &c->lsf, c->lsf_owned))) return done(rc);
+  if ((rc = upload(c, v, &c->lsf, c->lsf_owned))) return rc;
   c->n_lsf = n;
   c->lsf_wave = c->d_obs_wave;
   if (lsf_wave) {
     std::vector<double> w(lsf_wave, lsf_wave + n);
-    if ((rc = upload(c, w, &c->lsf_wave, c->lsf_owned))) return done(rc);
+    if ((rc = upload(c, w, &c->lsf_wave, c->lsf_owned))) return rc;
   }
   c->lsf_global = c->T.n1 > 8192 || (c->opts.variant & PAYNE_V_LSF_GLOBAL);
   c->lsf_chunk = c->lsf_global ? std::min(c->opts.b_max, 256) : c->opts.b_max;
-  if ((rc = dev_alloc(c, (size_t)c->lsf_chunk * c->T.npix, &c->lsf_spec, c->lsf_owned, false))) return done(rc);
-  if ((rc = dev_alloc(c, (size_t)c->lsf_chunk * (2 * (size_t)c->T.npix + c->T.n1), &c->lsf_ws, c->lsf_owned, false))) return done(rc);
+  if ((rc = dev_alloc(c, (size_t)c->lsf_chunk * c->T.npix, &c->lsf_spec, c->lsf_owned, false))) return rc;
+  if ((rc = dev_alloc(c, (size_t)c->lsf_chunk * (2 * (size_t)c->T.npix + c->T.n1), &c->lsf_ws, c->lsf_owned, false))) return rc;
   if (c->lsf_global) {
-    if ((rc = dev_alloc(c, (size_t)c->lsf_chunk * 2 * fft_buf_floats(c->T.n1), &c->lsf_fws, c->lsf_owned, false))) return done(rc);
+    if ((rc = dev_alloc(c, (size_t)c->lsf_chunk * 2 * fft_buf_floats(c->T.n1), &c->lsf_fws, c->lsf_owned, false))) return rc;
   } else {
     const size_t lds = (size_t)c->T.n1 * 8 + 2 * (size_t)fft_buf_floats(c->T.n1) * 4 + (256 + 8) * 8;
     hipError_t he = hipFuncSetAttribute(reinterpret_cast<const void*>(payne_lsf_kernel<false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (he != hipSuccess) return done(fail(c, PAYNE_E_HIP, std::string("hipFuncSetAttribute: ") + hipGetErrorString(he)));
+    if (he != hipSuccess) return fail(c, PAYNE_E_HIP, std::string("hipFuncSetAttribute: ") + hipGetErrorString(he));
   }
   c->has_lsf = true;
-  return done(PAYNE_OK);
+  return PAYNE_OK;
 }
 extern "C" int payne_ctx_set_lsf(payne_ctx* c, const double* lsf, int n) { return set_lsf_impl(c, nullptr, lsf, n); }
 extern "C" int payne_ctx_set_lsf_on(payne_ctx* c, const double* lsf_wave, const double* lsf, int n) {
@@ -991,24 +977,49 @@ struct NetRef {
   float* const* hid; int ld_hid; float* out; int ld_out; float out_shift;
   bool spectral;                      // the spectral net owns the DMA / bf16x3 operand copies and the prep records
   bool freq = false;                  // spectral net: rows written in the frequency domain (c->w_out_p3z)
+  bool sel = false;                   // ... as rows of the resampled grid, or pixel rows if the batch's records say so (freq_rs)
 };
-// The output layer's kernel for a batch of B through net N (N.freq: the rows go out transformed): every variant bit and every shape
-// that bears on it is tested here.  DESIGN section 1 has the table.
+static NetRef spectral_net(const payne_ctx* c) {
+  return NetRef{c->layers, c->n_layers, c->n_labels, c->xmin, c->xden, c->hid, c->ld_hid, c->raw, c->T.npix, kBase, true};
+}
+static NetRef continuum_net(const payne_ctx* c) {
+  return NetRef{c->clayers, c->cn_layers, c->n_labels, c->cxmin, c->cxden, c->chid, c->cn_ld_hid, c->cont_raw, c->cn_npix, 0.f, false};
+}
+// What one forward pass left for the post stage: filled by run_ann (payne_smooth_batch: the caller's pixels), read by run_post and
+// everything below it.  A value of the call, not of the context: a view of some of the rows is a copy with the pointers moved on.
+struct BatchRows {
+  const float* rows = nullptr; int ld = 0;   // [B][ld]: the spectra shifted by -1, or their transforms
+  bool freq = false;                  // the rows are in the frequency domain (PostTables::raw_freq of the launches that read them)
+  // sel: ... rows of the resampled grid (pitch n1) that fall back to pixels (pitch npix) on the device if a candidate does not rotate;
+  // rot_seq: the sequence number issued for them (c->rot_flag)
+  bool sel = false; unsigned long long rot_seq = 0;
+  const CandState* prep = nullptr;    // the batch's records; null: no dense launch wrote any for these rows
+  bool spec = false;                  // the hidden-layer launch carried the walk's proposals (SpecReq)
+};
+// A sampler's walk in progress asks the likelihood batch being enqueued to make the next step's proposals ahead (rwalk_spec_wave).
+struct SpecReq { const WalkTail* walk; const WalkState* w; int step, K; };      // (walk == null: no request)
+// The output layer's form for net N whatever domain its rows go out in (rows in the frequency domain need Bf16x3 or better).
+static OutForm out_form(const payne_ctx* c, const NetRef& N) {
+  OutForm f = wanted_out_form(c->opts.variant);
+  if (!(N.spectral && c->dma_ok && c->ld_hid >= c->w_out_kp)) return OutForm::Generic;       // hidden widths differ, the continuum network
+  if (f >= OutForm::Bf16x3 && !(c->w_out_p3 && c->hid_p3)) f = OutForm::F32Dma;
+  if (f == OutForm::H2) {
+    // (payne_dense_dma2h_kernel addresses an operand plane by 32-bit byte offsets: rows x pitch x 2 bytes below 2^31)
+    const unsigned long long plane_w = 2ull * (unsigned long long)std::max(N.layers[N.n_layers - 1].n_out, c->T.n1) * (unsigned long long)c->w_out_kp;
+    const unsigned long long plane_x = 2ull * (unsigned long long)c->opts.b_max * (unsigned long long)c->ld_hid;
+    if (plane_w >= (1ull << 31) || plane_x >= (1ull << 31) || !c->w_out_h2 || !(c->act_scale > 0.f)) f = OutForm::Bf16x3;
+  }
+  return f;
+}
+// The output layer's kernel for a batch of B through net N (N.freq: the rows go out transformed; N.sel: ... of the resampled grid):
+// every variant bit and every shape that bears on it is tested here and in out_form.  DESIGN section 1 has the table.
 static OutPlan plan_out(const payne_ctx* c, const NetRef& N, int B) {
   const unsigned v = c->opts.variant;
   const int kp = c->w_out_kp, n_out = N.layers[N.n_layers - 1].n_out;
-  OutPlan o;
-  o.sel = N.freq && c->freq_rs_now;
+  OutPlan o; o.sel = N.sel;
   const int n_launch = o.sel ? c->T.n1 : n_out;             // (rows of the resampled grid: T.n1 values)
-  o.form = wanted_out_form(v);
-  if (!(N.spectral && c->dma_ok && c->ld_hid >= kp)) o.form = OutForm::Generic;     // hidden widths differ, the continuum network
-  if (o.form >= OutForm::Bf16x3 && !(c->w_out_p3 && c->hid_p3)) o.form = OutForm::F32Dma;
-  if (o.form == OutForm::H2) {
-    // (payne_dense_dma2h_kernel addresses an operand plane by 32-bit byte offsets: rows x pitch x 2 bytes below 2^31)
-    const unsigned long long plane_w = 2ull * (unsigned long long)std::max(n_out, c->T.n1) * (unsigned long long)kp;
-    const unsigned long long plane_x = 2ull * (unsigned long long)c->opts.b_max * (unsigned long long)c->ld_hid;
-    if (plane_w >= (1ull << 31) || plane_x >= (1ull << 31) || !c->w_out_h2 || !(c->act_scale > 0.f) || (N.freq && !c->w_out_h2z)) o.form = OutForm::Bf16x3;
-  }
+  o.form = out_form(c, N);
+  if (o.form == OutForm::H2 && N.freq && !c->w_out_h2z) o.form = OutForm::Bf16x3;
   if (o.form == OutForm::Generic) return o;
   o.grid_m = (B + 63) / 64; o.grid_n = (n_launch + 127) / 128;
   o.own_cu = o.grid_m * o.grid_n <= c->n_cu;
@@ -1023,9 +1034,10 @@ static OutPlan plan_out(const payne_ctx* c, const NetRef& N, int B) {
   return o;
 }
 // `sed`: a joint likelihood's photometric nets ride in the first hidden-layer launch (sed_tile); *sed is cleared when they did.
-static int run_net(payne_ctx* c, const NetRef& N, const double* theta, int B, double instr_factor, hipStream_t s, bool* sed = nullptr) {
+// `R` (the spectral net's): gets the records and whether the walk's proposals `spec` went along; R->rot_seq is read where plan.sel.
+static int run_net(payne_ctx* c, const NetRef& N, const OutPlan& plan, const double* theta, int B, double instr_factor, hipStream_t s,
+                   BatchRows* R = nullptr, bool* sed = nullptr, const SpecReq& spec = SpecReq{}) {
   const int n = N.n_layers;
-  const OutPlan plan = plan_out(c, N, B);
   const bool use3 = plan.form >= OutForm::Bf16x3, use2h = plan.form == OutForm::H2;   // (the last hidden layer writes that form's planes)
   for (int l = 1; l < n; ++l) {
     DenseParams p{};
@@ -1051,28 +1063,26 @@ static int run_net(payne_ctx* c, const NetRef& N, const double* theta, int B, do
       p.W0 = L0.w; p.b0 = L0.b; p.n_labels = N.n_labels; p.act0 = L0.act; p.K0 = L0.n_out;
       for (int d = 0; d < N.n_labels; ++d) { p.xmin[d] = N.xmin[d]; p.xden[d] = N.xden[d]; }
       PrepArgs pa{};
-      pa.T = c->T; pa.instr_factor = instr_factor;
+      pa.T = c->T; pa.T.raw_freq = N.freq ? 1 : 0; pa.instr_factor = instr_factor;      // (the tables are read by the records' writers only)
       pa.out = (N.spectral && c->prep && c->obs_bound && !(c->opts.variant & PAYNE_V_NO_PREP)) ? c->prep : nullptr;
-      if (N.freq && c->freq_rs_now) { pa.rot_flag = c->rot_flag; pa.rot_seq = c->rot_seq; }
+      if (plan.sel) { pa.rot_flag = c->rot_flag; pa.rot_seq = R->rot_seq; }
       if (!last && sed && *sed && N.spectral && sed_tile_ok(c->P.H) && !(c->opts.variant & PAYNE_V_SED_OWN_LAUNCH)) {
         pa.P = c->P; pa.sed_mags = c->mags_ws; pa.sed_off = 8 + c->opts.npoly; pa.sed_photscale = c->opts.photscale;
         *sed = false;
       }
       // the walk's next proposals ride along when this batch's post kernel will run the chain step at its tail (run_post)
-      const bool spec = !last && N.spectral && c->spec_walk && pa.out && c->lean_available && !c->big_ws;
-      if (spec) {
-        pa.spec_walk = static_cast<const WalkTail*>(c->spec_walk); pa.spec_w = *static_cast<const WalkState*>(c->spec_w);
-        pa.spec_step = c->spec_step; c->spec_launched = true;
-      }
+      const int spec_K = (!last && N.spectral && spec.walk && pa.out && c->lean_available && !c->big_ws) ? spec.K : 0;
+      if (spec_K) { pa.spec_walk = spec.walk; pa.spec_w = *spec.w; pa.spec_step = spec.step; }
       if (!last && N.spectral && c->w_hid_pad[1] && N.ld_hid >= HK_PITCH) { p.Wd = c->w_hid_pad[1]; p.ldwd = N.ld_hid; }
       if (!last && N.spectral && p.Wd && c->w1_h2 && c->w1_rows == p.N && p.K <= 304 &&
           (unsigned long long)B * (unsigned)c->ncols * 8ull < (1ull << 31)) {                // the second layer on fp16 pairs (hk_tile_h2: 32-bit byte offsets into theta)
         p.h2_tiles = 1; p.Wh = c->w1_h2; p.plane_wh = (size_t)c->w1_rows * 304; p.rs1 = c->rs1; p.a0_scale = c->a0_scale;
       }
-      if (!last && !hk_lead_fits(p.B, p.N, p.K, p.K0, 0, p.ldwd, p.ld_theta, spec ? c->spec_K : 0))
+      if (!last && !hk_lead_fits(p.B, p.N, p.K, p.K0, 0, p.ldwd, p.ld_theta, spec_K))
         return fail(c, PAYNE_E_UNSUPPORTED, "batch x hidden width beyond what the hidden-layer kernel's packed arguments hold (65 535 tiles of 32 x 32)");
       if (last) launch_dense<64, 64, 32, true>(p, s);
-      else { launch_hidden<true>(p, pa, s, c->n_cu, spec ? c->spec_K : 0, (c->opts.variant & PAYNE_V_HID_WAVES4) != 0); if (N.spectral) c->prep_valid = pa.out != nullptr; }
+      else launch_hidden<true>(p, pa, s, c->n_cu, spec_K, (c->opts.variant & PAYNE_V_HID_WAVES4) != 0);
+      if (!last && R) { R->prep = pa.out; R->spec = spec_K != 0; }
     } else if (!last && chain && use3 && l == 2 && n - 2 >= 3 && c->chain_flags && (c->opts.variant & PAYNE_V_HID_CHAIN) &&
                ((c->opts.b_max + 31) / 32) * ((N.layers[2].n_out + 31) / 32) <= 2 * c->n_cu && n - 3 <= kChainMax &&
                [&] { for (int q = 2; q <= n - 2; ++q) if (!c->wl_h2[q]) return false; return true; }()) {
@@ -1107,7 +1117,7 @@ static int run_net(payne_ctx* c, const NetRef& N, const double* theta, int B, do
       if (!last) launch_hidden<false>(p, pa, s);
       else if (use3) {
         if (plan.sel) {                                      // rows of the resampled grid; pixels if the batch's records say so
-          p.sel = c->rot_flag; p.sel_seq = c->rot_seq;
+          p.sel = c->rot_flag; p.sel_seq = R->rot_seq;
           p.Wp_alt = c->w_out_p3; p.plane_w_alt = (size_t)p.N * c->w_out_kp; p.bias_alt = p.bias; p.bias_shift_alt = p.bias_shift;
           p.N_alt = p.N; p.ldy_alt = p.ldy;
           p.N = c->T.n1; p.ldy = c->T.n1;
@@ -1199,22 +1209,23 @@ __global__ void __launch_bounds__(256) payne_cont_kernel(const float* __restrict
 // `instr_factor`: what Inst_R is multiplied by (2.355 in the likelihood / genspec, 1 in getspec): the
 // first-layer launch also writes the post kernel's per-candidate records (c->prep) for that factor.
 // `pixels`: the caller reads the rows themselves (stage 0); otherwise they may be handed to the post kernel already transformed.
-static int run_ann(payne_ctx* c, const double* theta, int B, double instr_factor, hipStream_t s, bool with_cont = true, bool* sed = nullptr,
-                   bool pixels = false) {
-  c->prep_valid = false;
-  NetRef N{c->layers, c->n_layers, c->n_labels, c->xmin, c->xden, c->hid, c->ld_hid, c->raw, c->T.npix, kBase, true};
-  // (the continuum multiplies pixel by pixel; the plan's form: the launch that reads the restated weights is the one that runs)
-  N.freq = c->freq_ok && !pixels && !(c->has_cont && with_cont) && plan_out(c, N, B).form >= OutForm::Bf16x3;
+// *R: what the post stage finds (run_post).
+static int run_ann(payne_ctx* c, const double* theta, int B, double instr_factor, hipStream_t s, BatchRows* R, bool with_cont = true,
+                   bool* sed = nullptr, bool pixels = false, const SpecReq& spec = SpecReq{}) {
+  NetRef N = spectral_net(c);
+  // (the continuum multiplies pixel by pixel; the form: the launch that reads the restated weights is the one that runs)
+  N.freq = c->freq_ok && !pixels && !(c->has_cont && with_cont) && out_form(c, N) >= OutForm::Bf16x3;
   // rows of a resampled grid need this batch's records (their writers report a candidate that does not rotate) and a first layer
   // fused into the hidden-layer launch (>= 3 layers), and the plain post kernel behind them
   if (N.freq && c->freq_rs && !(c->prep && c->obs_bound && !(c->opts.variant & PAYNE_V_NO_PREP) && c->n_layers >= 3 && !c->has_lsf)) N.freq = false;
-  c->freq_rs_now = N.freq && c->freq_rs;
-  if (c->freq_rs_now) ++c->rot_seq;
-  c->raw_freq = N.freq; c->T.raw_freq = N.freq ? 1 : 0;
-  int rc = run_net(c, N, theta, B, instr_factor, s, sed);
+  N.sel = N.freq && c->freq_rs;
+  *R = BatchRows{};
+  R->rows = c->raw; R->ld = N.sel ? c->T.n1 : c->T.npix; R->freq = N.freq; R->sel = N.sel;
+  if (N.sel) R->rot_seq = ++c->rot_seq;
+  int rc = run_net(c, N, plan_out(c, N, B), theta, B, instr_factor, s, R, sed, spec);
   if (rc || !c->has_cont || !with_cont) return rc;
-  NetRef C{c->clayers, c->cn_layers, c->n_labels, c->cxmin, c->cxden, c->chid, c->cn_ld_hid, c->cont_raw, c->cn_npix, 0.f, false};
-  if ((rc = run_net(c, C, theta, B, instr_factor, s))) return rc;
+  const NetRef C = continuum_net(c);
+  if ((rc = run_net(c, C, plan_out(c, C, B), theta, B, instr_factor, s))) return rc;
   int npc2 = 1;
   while (npc2 < c->cn_npix) npc2 <<= 1;
   if (npc2 > 4096 || (c->opts.variant & PAYNE_V_SELECT_MEDIAN)) npc2 = 0;     // median by selection instead of an LDS sort
@@ -1250,43 +1261,39 @@ static int run_sed(payne_ctx* c, const double* in, int ld, int mode, int B, doub
   return PAYNE_OK;
 }
 
-static int run_post_lsf(payne_ctx* c, const double* theta, int B, int stage, float* out, int ld_out, double* lnl,
-                        bool with_phot, hipStream_t s);
-
 struct TailReq { const WalkTail* dev; int step, propose; bool done; const WalkState* spec; };   // spec: the walk (host copy) when proposals can be made ahead
-static int run_post(payne_ctx* c, const double* theta, int B, double instr_factor, int stage, float* out, int ld_out,
-                    double* lnl, bool with_phot, hipStream_t s, TailReq* tail = nullptr) {
-  if (c->has_lsf && (stage < 0 || stage == 2 || stage == 3)) return run_post_lsf(c, theta, B, stage, out, ld_out, lnl, with_phot, s);
-  PostArgs a{};
-  a.theta = theta; a.ld_theta = c->ncols; a.instr_factor = instr_factor;
-  a.raw = c->raw; a.ld_raw = c->T.npix;
-  if (c->raw_freq && c->freq_rs_now) { a.ld_raw = c->T.n1; a.ld_raw_alt = c->T.npix; a.rot_flag = c->rot_flag; a.rot_seq = c->rot_seq; }
-  a.out = out; a.ld_out = ld_out; a.out_stage = stage; a.lnl = lnl;
-  if (with_phot) { a.mags = c->mags_ws; a.n_filters = c->P.F; a.obs_mag = c->obs_mag; a.obs_err = c->obs_err; }
-  a.prep = c->prep_valid ? c->prep : nullptr;
-  const bool lean = stage < 0 && !out && a.prep && !c->big_ws;
+// One launch of the post kernel this context was built with, over the B candidates whose rows R describes.  `a` arrives with the
+// caller's part (theta, instr_factor, stage and outputs, photometry; the diagnostic build's stamps); the rows' part is filled in here.
+static int launch_post(payne_ctx* c, const BatchRows& R, PostArgs a, int B, hipStream_t s, TailReq* tail = nullptr) {
+  PostTables T = c->T; T.raw_freq = R.freq ? 1 : 0;
+  a.ld_theta = c->ncols;
+  a.raw = R.rows; a.ld_raw = R.ld; a.prep = R.prep;
+  if (R.sel) { a.ld_raw_alt = T.npix; a.rot_flag = c->rot_flag; a.rot_seq = R.rot_seq; }
+  // (stamps are written by the full instantiations only, and not by payne_post_chip2_kernel: such a context's stamps are the big kernel's)
+  const bool lean = a.out_stage < 0 && !a.out && a.prep && !c->big_ws && !a.stamps;
   if (tail && lean && c->lean_available) {
     a.tail = tail->dev; a.tail_step = tail->step; a.tail_propose = tail->propose; tail->done = true;
-    a.tail_spec = (c->spec_launched && tail->propose && tail->spec) ? 1 : 0;
+    a.tail_spec = (R.spec && tail->propose && tail->spec) ? 1 : 0;
   }
+  c->last_rows_freq = R.freq;
   {
     ProfScope ps(c, s, 1);
     if (c->big_ws && c->big_chip) {
       const int grid = B < c->big_grid ? B : c->big_grid;
-      PAYNE_LAUNCH(payne_post_chip_kernel, dim3(grid), dim3(kChipThreads), kChipLdsBytes, s, c->T, a, c->big_ws, B);
-    } else if (c->big_ws && c->big_chip2) {
+      PAYNE_LAUNCH(payne_post_chip_kernel, dim3(grid), dim3(kChipThreads), kChipLdsBytes, s, T, a, c->big_ws, B);
+    } else if (c->big_ws && c->big_chip2 && !a.stamps) {
       const int pairs = (B + 1) / 2, grid = pairs < c->big_grid ? pairs : c->big_grid;
-      PAYNE_LAUNCH(payne_post_chip2_kernel, dim3(grid), dim3(kChipThreads), kChipLdsBytes, s, c->T, a, c->big_ws, B);
+      PAYNE_LAUNCH(payne_post_chip2_kernel, dim3(grid), dim3(kChipThreads), kChipLdsBytes, s, T, a, c->big_ws, B);
     } else if (c->big_ws) {
       const int grid = B < c->big_grid ? B : c->big_grid;
       const int tiled = c->big_tiled ? 1 : 0;
       const size_t lds = (tiled & 1) ? 2 * (size_t)fft_tile_complex() * sizeof(c32) : 0;
-      PAYNE_LAUNCH(payne_post_big_kernel, dim3(grid), dim3(kBigThreads), lds, s, c->T, a, c->big_ws, B, tiled);
+      PAYNE_LAUNCH(payne_post_big_kernel, dim3(grid), dim3(kBigThreads), lds, s, T, a, c->big_ws, B, tiled);
     } else {
       if (!post_lead_fits(a.ld_raw, a.ld_theta, a.n_filters)) return fail(c, PAYNE_E_INVALID, "row pitch / theta columns / filters beyond what the post kernel's packed arguments hold");
-      PAYNE_LAUNCH(lean ? c->post_fn_lean : c->post_fn, dim3(B), dim3(kPostThreads), c->post_lds, s, c->T.twf, a.raw, a.prep, a.theta,
-                   a.rot_flag, a.mags, post_lead_ints(a.ld_raw, a.ld_theta, a.n_filters, c->T.raw_freq), (unsigned)a.rot_seq, c->T, a);
-      c->last_kernel[1] = post_kernel_label((c->opts.variant & PAYNE_V_POST_GENERIC) ? 0 : c->T.n1, c->post_tw_lds, lean && c->lean_available);
+      PAYNE_LAUNCH(lean ? c->post_fn_lean : c->post_fn, dim3(B), dim3(kPostThreads), c->post_lds, s, T.twf, a.raw, a.prep, a.theta,
+                   a.rot_flag, a.mags, post_lead_ints(a.ld_raw, a.ld_theta, a.n_filters, T.raw_freq), (unsigned)a.rot_seq, T, a);
+      c->last_kernel[1] = post_kernel_label((c->opts.variant & PAYNE_V_POST_GENERIC) ? 0 : T.n1, c->post_tw_lds, lean && c->lean_available);
     }
   }
   hipError_t e = hipGetLastError();
@@ -1295,21 +1302,16 @@ static int run_post(payne_ctx* c, const double* theta, int B, double instr_facto
 }
 
 // LSF path: spectra after rotational broadening (post kernel, stage 5) -> payne_lsf_kernel, a chunk of the batch at a time
-static int run_post_lsf(payne_ctx* c, const double* theta, int B, int stage, float* out, int ld_out, double* lnl,
+static int run_post_lsf(payne_ctx* c, const BatchRows& R, const double* theta, int B, int stage, float* out, int ld_out, double* lnl,
                         bool with_phot, hipStream_t s) {
-  const bool had = c->has_lsf;
   for (int off = 0; off < B; off += c->lsf_chunk) {
     const int nb = std::min(c->lsf_chunk, B - off);
     const double* th = theta + (size_t)off * c->ncols;
-    c->has_lsf = false;                                    // (the stage-5 pass below goes through run_post)
-    const float* raw_all = c->raw;
-    const CandState* prep_all = c->prep;
-    c->raw = const_cast<float*>(raw_all) + (size_t)off * c->T.npix;              // this chunk's rows of the ANN output
-    c->prep = const_cast<CandState*>(prep_all) + off;
-    int rc = run_post(c, th, nb, 1.0, 5, c->lsf_spec, c->T.npix, nullptr, false, s);
-    c->raw = const_cast<float*>(raw_all); c->prep = const_cast<CandState*>(prep_all);
-    c->has_lsf = had;
-    if (rc) return rc;
+    BatchRows v = R;                                        // this chunk's rows of the ANN output and their records
+    v.rows += (size_t)off * R.ld; if (v.prep) v.prep += off;
+    PostArgs p5{};
+    p5.theta = th; p5.instr_factor = 1.0; p5.out = c->lsf_spec; p5.ld_out = c->T.npix; p5.out_stage = 5;
+    if (int rc = launch_post(c, v, p5, nb, s)) return rc;
     LsfArgs a{};
     a.theta = th; a.ld_theta = c->ncols; a.spec = c->lsf_spec; a.ld_spec = c->T.npix;
     a.obs_wave = c->d_obs_wave; a.lsf = c->lsf; a.lsf_wave = c->lsf_wave; a.n_lsf = c->n_lsf;
@@ -1332,31 +1334,38 @@ static int run_post_lsf(payne_ctx* c, const double* theta, int B, int stage, flo
   return PAYNE_OK;
 }
 
-static int lnlike_impl(payne_ctx* c, const double* theta, int B, double* lnl, void* stream, TailReq* tail);
-extern "C" int payne_lnlike_batch(payne_ctx* c, const double* theta, int B, double* lnl, void* stream) {
-  return lnlike_impl(c, theta, B, lnl, stream, nullptr);
+// The post stage of a batch: with an LSF vector bound the stages that reach the observed grid take the LSF path, all else is one launch.
+static int run_post(payne_ctx* c, const BatchRows& R, const double* theta, int B, double instr_factor, int stage, float* out, int ld_out,
+                    double* lnl, bool with_phot, hipStream_t s, TailReq* tail = nullptr) {
+  if (c->has_lsf && (stage < 0 || stage == 2 || stage == 3)) return run_post_lsf(c, R, theta, B, stage, out, ld_out, lnl, with_phot, s);
+  PostArgs a{};
+  a.theta = theta; a.instr_factor = instr_factor;
+  a.out = out; a.ld_out = ld_out; a.out_stage = stage; a.lnl = lnl;
+  if (with_phot) { a.mags = c->mags_ws; a.n_filters = c->P.F; a.obs_mag = c->obs_mag; a.obs_err = c->obs_err; }
+  return launch_post(c, R, a, B, s, tail);
 }
+
 static int lnlike_impl(payne_ctx* c, const double* theta, int B, double* lnl, void* stream, TailReq* tail) {
   int rc = check_call(c, theta, B, lnl);
   if (rc) return rc;
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
   if (c->has_phot && !c->has_obs_phot) return fail(c, PAYNE_E_INVALID, "photometric model without observed magnitudes");
-  if (c->has_model) {
-    if (!c->obs_bound || !c->T.obs_f1) return fail(c, PAYNE_E_INVALID, "no observed spectrum (flux, eflux) bound");
-  }
+  if (c->has_model && (!c->obs_bound || !c->T.obs_f1)) return fail(c, PAYNE_E_INVALID, "no observed spectrum (flux, eflux) bound");
   bool sed_pending = c->has_phot;                           // the photometric nets: in the hidden-layer launch when there is one
   TailReq* const tl = (c->has_lsf || (c->opts.variant & PAYNE_V_NO_WALK_TAIL)) ? nullptr : tail;
-  c->spec_launched = false;
-  if (tl && tl->propose && tl->spec && !(c->opts.variant & PAYNE_V_NO_WALK_SPEC)) { c->spec_walk = tl->dev; c->spec_w = tl->spec; c->spec_step = tl->step; c->spec_K = B; }
-  if (c->has_model) rc = run_ann(c, theta, B, 2.355, s, true, &sed_pending);
-  c->spec_walk = nullptr;
-  if (rc) return rc;
+  SpecReq spec{};
+  if (tl && tl->propose && tl->spec && !(c->opts.variant & PAYNE_V_NO_WALK_SPEC)) spec = SpecReq{tl->dev, tl->spec, tl->step, B};
+  BatchRows R;
+  if (c->has_model && (rc = run_ann(c, theta, B, 2.355, s, &R, true, &sed_pending, false, spec))) return rc;
   if (sed_pending && (rc = run_sed(c, theta, c->ncols, 1, B, c->mags_ws, s))) return rc;
-  if (c->has_model) return run_post(c, theta, B, 2.355, -1, nullptr, 0, lnl, c->has_phot, s, tl);
+  if (c->has_model) return run_post(c, R, theta, B, 2.355, -1, nullptr, 0, lnl, c->has_phot, s, tl);
   hipLaunchKernelGGL(payne_photonly_kernel, dim3((B + 127) / 128), dim3(128), 0, s, c->mags_ws, c->obs_mag, c->obs_err, c->P.F, B, lnl);
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) return fail(c, PAYNE_E_HIP, std::string("photonly launch: ") + hipGetErrorString(e));
   return PAYNE_OK;
+}
+extern "C" int payne_lnlike_batch(payne_ctx* c, const double* theta, int B, double* lnl, void* stream) {
+  return lnlike_impl(c, theta, B, lnl, stream, nullptr);
 }
 
 extern "C" int payne_predict_batch(payne_ctx* c, const double* theta, int B, int stage, unsigned flags, float* out,
@@ -1369,8 +1378,8 @@ extern "C" int payne_predict_batch(payne_ctx* c, const double* theta, int B, int
   if (stage == PAYNE_STAGE_CONT) {                       // predictcont: the continuum network's own output
     if (!c->has_cont) return fail(c, PAYNE_E_INVALID, "no continuum network bound");
     if (ld_out < c->cn_npix) return fail(c, PAYNE_E_INVALID, "ld_out too small");
-    NetRef C{c->clayers, c->cn_layers, c->n_labels, c->cxmin, c->cxden, c->chid, c->cn_ld_hid, c->cont_raw, c->cn_npix, 0.f, false};
-    if ((rc = run_net(c, C, theta, B, 1.0, s))) return rc;
+    const NetRef C = continuum_net(c);
+    if ((rc = run_net(c, C, plan_out(c, C, B), theta, B, 1.0, s))) return rc;
     hipError_t he = hipMemcpy2DAsync(out, (size_t)ld_out * 4, c->cont_raw, (size_t)c->cn_npix * 4, (size_t)c->cn_npix * 4, B,
                                      hipMemcpyDeviceToDevice, s);
     if (he != hipSuccess) return fail(c, PAYNE_E_HIP, std::string("hipMemcpy2DAsync: ") + hipGetErrorString(he));
@@ -1378,8 +1387,9 @@ extern "C" int payne_predict_batch(payne_ctx* c, const double* theta, int B, int
   }
   if (stage >= 2 && !c->obs_bound) return fail(c, PAYNE_E_INVALID, "no observed grid bound");
   if (ld_out < (stage >= 2 ? c->T.nobs : c->T.npix)) return fail(c, PAYNE_E_INVALID, "ld_out too small");
-  if ((rc = run_ann(c, theta, B, (flags & PAYNE_F_FWHM_R) ? 2.355 : 1.0, s, stage != 0, nullptr, stage == 0))) return rc;   // stage 0 = predictspec: no continuum
-  return run_post(c, theta, B, (flags & PAYNE_F_FWHM_R) ? 2.355 : 1.0, stage, out, ld_out, nullptr, false, s);
+  BatchRows R;
+  if ((rc = run_ann(c, theta, B, (flags & PAYNE_F_FWHM_R) ? 2.355 : 1.0, s, &R, stage != 0, nullptr, stage == 0))) return rc;   // stage 0 = predictspec: no continuum
+  return run_post(c, R, theta, B, (flags & PAYNE_F_FWHM_R) ? 2.355 : 1.0, stage, out, ld_out, nullptr, false, s);
 }
 
 // smoothspec on caller-supplied spectra (PayneSpecPredict.smoothspec, ystpred.py:279-281 -> utils.smoothing.smoothspec):
@@ -1404,11 +1414,11 @@ extern "C" int payne_smooth_batch(payne_ctx* c, const float* spectra, int ld_spe
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
   const size_t n = (size_t)B * c->T.npix;
   hipLaunchKernelGGL(payne_shift_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, spectra, ld_spec, c->raw, c->T.npix, B);
-  c->prep_valid = false;                                   // no dense launch wrote records for these rows
-  c->raw_freq = false; c->T.raw_freq = 0;                  // ... and they are pixels
+  BatchRows R;                                             // the caller's pixels: no dense launch wrote records for these rows
+  R.rows = c->raw; R.ld = c->T.npix;
   // stage 1 here is smoothspec('vsini') itself: getspec's edge rule (ystpred.py:223-224) is not part of it
   // stage 4: ... interpolated from the stage's own resampled grid onto the bound observed grid (smoothspec('vsini', outwave=...))
-  return run_post(c, theta, B, (flags & PAYNE_F_FWHM_R) ? 2.355 : 1.0, stage == 1 ? 6 : (stage == PAYNE_SMOOTH_VSINI_TO_OBS ? 7 : stage), out, ld_out,
+  return run_post(c, R, theta, B, (flags & PAYNE_F_FWHM_R) ? 2.355 : 1.0, stage == 1 ? 6 : (stage == PAYNE_SMOOTH_VSINI_TO_OBS ? 7 : stage), out, ld_out,
                   nullptr, false, s);
 }
 
@@ -2396,7 +2406,8 @@ extern "C" int payne_diag_hidden_stamps(payne_ctx* c, const double* theta, int B
   HIPCHK(c, hipMemset(d, 0, nb_ * 16 * 8));
   if (max_blocks < 0) { max_blocks = -max_blocks; g_dense_stamps = d; } else g_hidden_stamps = d;   // negative: the output layer
   bool sed = c->has_phot;
-  rc = run_ann(c, theta, B, 2.355, nullptr, true, &sed);
+  BatchRows R;
+  rc = run_ann(c, theta, B, 2.355, nullptr, &R, true, &sed);
   g_hidden_stamps = nullptr; g_dense_stamps = nullptr;
   HIPCHK(c, hipDeviceSynchronize());
   HIPCHK(c, hipMemcpy(host, d, (size_t)max_blocks * 16 * 8, hipMemcpyDeviceToHost));
@@ -2409,34 +2420,21 @@ extern "C" int payne_diag_stamp_row(void) { return kStampRow; }
 extern "C" int payne_diag_post_stamps(payne_ctx* c, const double* theta, int B, unsigned long long* stamps_host) {
   int rc = check_call(c, theta, B, stamps_host);
   if (rc) return rc;
-  unsigned long long* d = nullptr;
-  double* lnl = nullptr;
-  HIPCHK(c, hipMalloc(&d, (size_t)B * kStampRow * 8));
-  HIPCHK(c, hipMalloc(&lnl, (size_t)B * 8));
-  HIPCHK(c, hipMemset(d, 0, (size_t)B * kStampRow * 8));
-  if ((rc = run_ann(c, theta, B, 2.355, nullptr))) return rc;
-  PostArgs a{};
-  a.theta = theta; a.ld_theta = c->ncols; a.instr_factor = 2.355; a.raw = c->raw; a.ld_raw = c->T.npix;
-  if (c->raw_freq && c->freq_rs_now) { a.ld_raw = c->T.n1; a.ld_raw_alt = c->T.npix; a.rot_flag = c->rot_flag; a.rot_seq = c->rot_seq; }
-  a.out_stage = -1; a.lnl = lnl; a.stamps = d; a.prep = c->prep_valid ? c->prep : nullptr;
-  a.stamp_sparse = getenv("PAYNE_DIAG_SPARSE") ? 1 : 0;
-  if (c->big_ws && c->big_chip) {
-    const int grid = B < c->big_grid ? B : c->big_grid;
-    hipLaunchKernelGGL(payne_post_chip_kernel, dim3(grid), dim3(kChipThreads), kChipLdsBytes, nullptr, c->T, a, c->big_ws, B);
-  } else if (c->big_ws) {                                  // spectra larger than LDS (PAYNE_BIG_TILED=0: plain passes)
-    const int grid = B < c->big_grid ? B : c->big_grid;
-    const int tiled = c->big_tiled ? 1 : 0;
-    const size_t lds = tiled ? 2 * (size_t)fft_tile_complex() * sizeof(c32) : 0;
-    if (tiled) (void)hipFuncSetAttribute(reinterpret_cast<const void*>(payne_post_big_kernel),
-                                         hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    hipLaunchKernelGGL(payne_post_big_kernel, dim3(grid), dim3(kBigThreads), lds, nullptr, c->T, a, c->big_ws, B, tiled);
-  } else {
-    hipLaunchKernelGGL(c->post_fn, dim3(B), dim3(kPostThreads), c->post_lds, nullptr, c->T.twf, a.raw, a.prep, a.theta, a.rot_flag, a.mags,
-                       post_lead_ints(a.ld_raw, a.ld_theta, a.n_filters, c->T.raw_freq), (unsigned)a.rot_seq, c->T, a);
+  unsigned long long* d = nullptr; double* lnl = nullptr;
+  hipError_t e = hipMalloc(&d, (size_t)B * kStampRow * 8);
+  if (e == hipSuccess) e = hipMalloc(&lnl, (size_t)B * 8);
+  if (e == hipSuccess) e = hipMemset(d, 0, (size_t)B * kStampRow * 8);
+  BatchRows R;
+  if (e == hipSuccess) rc = run_ann(c, theta, B, 2.355, nullptr, &R);
+  if (e == hipSuccess && !rc) {
+    PostArgs a{};
+    a.theta = theta; a.instr_factor = 2.355; a.out_stage = -1; a.lnl = lnl;
+    a.stamps = d; a.stamp_sparse = getenv("PAYNE_DIAG_SPARSE") ? 1 : 0;
+    rc = launch_post(c, R, a, B, nullptr);
   }
-  HIPCHK(c, hipDeviceSynchronize());
-  HIPCHK(c, hipMemcpy(stamps_host, d, (size_t)B * kStampRow * 8, hipMemcpyDeviceToHost));
+  if (e == hipSuccess && !rc) e = hipDeviceSynchronize();
+  if (e == hipSuccess && !rc) e = hipMemcpy(stamps_host, d, (size_t)B * kStampRow * 8, hipMemcpyDeviceToHost);
   (void)hipFree(d); (void)hipFree(lnl);
-  return PAYNE_OK;
+  return e != hipSuccess ? fail(c, PAYNE_E_HIP, std::string("post stamps: ") + hipGetErrorString(e)) : rc;
 }
 #endif
