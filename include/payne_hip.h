@@ -445,8 +445,40 @@ int payne_ns_rwalk_queue_turn(payne_sampler* s, double* qu, double* qv, double* 
  * candidate k settles chain k's proposal as soon as it has the likelihood and takes the next one from the two that idle workgroups
  * of the batch's hidden-layer launch made ahead, one per outcome -- or draws it there: PAYNE_V_NO_WALK_SPEC), out[1] as launches of
  * their own (the first step of every walk; every step under PAYNE_V_NO_WALK_TAIL, with an LSF, or when the spectrum length
- * has no likelihood-only kernel).  Measurement / test aid, no reference counterpart. */
+ * has no likelihood-only kernel; every round of a slice walk).  Measurement / test aid, no reference counterpart. */
 int payne_sampler_counters(const payne_sampler* s, long long out[2]);
+
+/* Slice sampling ('slice' / 'rslice' of Payne/fitting/fitstar.py:292-295, samplemethod / slices=) for K lock-step chains under
+ * lnprob > loglstar, the chain on the device.  dynesty proposes one point at a time; here every chain is a state machine that
+ * asks for one likelihood per ROUND -- an end of its window while it steps out, a point of the window while it shrinks --, a
+ * round is one small kernel and one likelihood batch, and the host enqueues rounds without looking at the chains.  Per
+ * direction: the window left = u - r axis, right = u + (1 - r) axis (r uniform), stepped out by one axis length while an end
+ * beats the threshold, then sampled uniformly and shrunk towards u until a point beats it (given up after 200 shrinks: the point
+ * stays).  A point outside the open unit cube is -inf without a likelihood call.  Directions: random_dirs = 0 ('slice') `slices`
+ * sweeps over the ndim columns of the chain's ellipsoid matrix, each sweep in an order of its own; random_dirs = 1 ('rslice')
+ * `slices` directions axes . z with z a random unit vector; all scaled by `scale`.  Draws are counter-based on (seed, chain,
+ * direction, draw), so a chain does not depend on how its rounds are grouped into calls.
+ * u, v: device fp64 [K][ndim] in/out; lnprob: device fp64 [K] in/out; axes: HOST fp64 [n_ell][ndim][ndim] row-major, COLUMNS =
+ * axes; ell: HOST int32 [K] naming each chain's matrix (NULL with n_ell == 1); ncall, nexpand, ncontract: device int32 [K]
+ * (values asked for -- in the cube or not --, of which window ends, of which points of the window), overwritten: the walk's
+ * first round starts them at zero.  `begin` enqueues the uploads only; it fails with PAYNE_E_INVALID while a random walk or a
+ * queue is open on the sampler (the two share the pending proposal's buffers), as payne_rwalk_begin does while a slice walk is. */
+int payne_slice_begin(payne_sampler* s, double* u, double* v, double* lnprob, int K, const double* axes, int n_ell,
+                      const int* ell, double scale, double loglstar, int slices, int random_dirs, unsigned long long seed,
+                      int* ncall, int* nexpand, int* ncontract, void* stream);
+
+/* n >= 1 rounds of the walk begun (fitstar.py:292-295; dynesty proposes one point at a time, a round is one point for EVERY
+ * chain), then one closing launch that settles what is pending, then a wait for the stream: *n_active = the chains that have not
+ * finished -- the one word the host reads.  A later call continues the same walk; it is closed when *n_active == 0 (or by the
+ * next payne_slice_begin).  An unfinished chain's point is its start point or a point that beat the threshold. */
+int payne_slice_rounds(payne_sampler* s, int n, int* n_active);
+
+/* begin + rounds(chunk) until no chain is active or max_rounds rounds are spent (fitstar.py:292-295 as above; dynesty proposes
+ * one point at a time): PAYNE_OK with *n_active > 0 in the second case, the walk closed either way.  `chunk` trades rounds run
+ * with every chain finished (at most chunk - 1) for host turns. */
+int payne_slice_batch(payne_sampler* s, double* u, double* v, double* lnprob, int K, const double* axes, int n_ell,
+                      const int* ell, double scale, double loglstar, int slices, int random_dirs, unsigned long long seed,
+                      int* ncall, int* nexpand, int* ncontract, void* stream, int chunk, int max_rounds, int* n_active);
 
 /* The proposal queue's TURN on the device.  payne_ns_rwalk_queue_turn collects a queue, adapts the scale, predicts the live set and
  * launches the next queue from the host -- the GPU idles meanwhile (~100 us of a 1 ms cycle at C2).  Here the live set lives on the

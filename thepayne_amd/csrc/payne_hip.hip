@@ -1471,6 +1471,12 @@ struct payne_sampler {
   std::vector<void*> owned;
   // a walk in progress (payne_rwalk_begin / payne_rwalk_step)
   struct { double *u, *v, *lnprob; int K, walks; double scale, loglstar; unsigned long long seed; int *nacc, *ncall; void* stream; bool open; bool multi; int* nredraw; } run{};
+  // a slice walk in progress (payne_slice_begin / payne_slice_rounds): the windows (left | right | axis), the chains' scalars
+  // (phase | dir | attempt | nshrink) and the word the closing launch counts the unfinished chains in; its pinned landing place
+  double* sl_win = nullptr; int* sl_int = nullptr; int* sl_active_host = nullptr;
+  SliceState slice{};
+  struct { bool open, pending, first; void* stream; } srun{};
+  long long n_slice = 0;                  // slice rounds (launches of their own)
 };
 
 // doubles of the queue's staging block (device and pinned host): chains (u | v | lnprob) and the walk's three counters (what
@@ -1485,6 +1491,7 @@ extern "C" void payne_sampler_destroy(payne_sampler* s) {
   (void)hipSetDevice(s->ctx->device);
   for (void* p : s->owned) (void)hipFree(p);
   if (s->q_host) (void)hipHostFree(s->q_host);
+  if (s->sl_active_host) (void)hipHostFree(s->sl_active_host);
   for (int b = 0; b < 2; ++b) { if (s->dq_host[b]) (void)hipHostFree(s->dq_host[b]); if (s->dax_host[b]) (void)hipHostFree(s->dax_host[b]); }
   (void)hipSetDevice(prev);
   delete s;
@@ -1536,6 +1543,7 @@ extern "C" int payne_sampler_create(payne_ctx* c, const payne_sampler_desc* d, i
       (rc = alloc(K * 4, (void**)&s->inside)) || (rc = alloc(K * 4, (void**)&s->ell)) || (rc = alloc(K * 4, (void**)&s->nredraw)) ||
       (rc = alloc(std::max<size_t>(q_doubles(K, nd), 2 * PAYNE_MAX_DIM) * 8, (void**)&s->q_dev)) ||
       (rc = alloc(sizeof(WalkTail), (void**)&s->tail_dev)) ||
+      (rc = alloc(3 * K * nd * 8, (void**)&s->sl_win)) || (rc = alloc((4 * K + 1) * 4, (void**)&s->sl_int)) ||
       (spec_fits(d->ndim, c->ncols) && (rc = alloc(K * 2 * kSpecStride * 8, (void**)&s->spec)))) {
     payne_sampler_destroy(s);
     return rc;
@@ -1567,7 +1575,8 @@ extern "C" int payne_sampler_create(payne_ctx* c, const payne_sampler_desc* d, i
     return fail(c, PAYNE_E_HIP, "upload of the sampler descriptor");
   }
   (void)hipMemset(s->inside, 0, K * 4);
-  if (hipHostMalloc((void**)&s->q_host, (q_doubles(K, nd) + 8) * 8, hipHostMallocMapped) != hipSuccess) {
+  if (hipHostMalloc((void**)&s->q_host, (q_doubles(K, nd) + 8) * 8, hipHostMallocMapped) != hipSuccess ||
+      hipHostMalloc((void**)&s->sl_active_host, 8, hipHostMallocDefault) != hipSuccess) {
     payne_sampler_destroy(s);
     return fail(c, PAYNE_E_HIP, "hipHostMalloc(sampler staging)");
   }
@@ -1640,6 +1649,7 @@ extern "C" int payne_rwalk_begin_ell(payne_sampler* s, double* u, double* v, dou
   int rc = sampler_check(s, u, K, v);
   if (rc) return rc;
   if (!lnprob || !axes || !nacc || !ncall || walks <= 0) return fail(s->ctx, PAYNE_E_INVALID, "bad rwalk arguments");
+  if (s->srun.open) return fail(s->ctx, PAYNE_E_INVALID, "a slice walk is open on this sampler");
   if (n_ell < 1 || n_ell > PAYNE_MAX_ELL || (n_ell > 1 && !ell)) return fail(s->ctx, PAYNE_E_INVALID, "bad ellipsoid list");
   if (ell)
     for (int i = 0; i < K; ++i)
@@ -1683,7 +1693,7 @@ extern "C" int payne_rwalk_step(payne_sampler* s, int w) {
 }
 extern "C" int payne_sampler_counters(const payne_sampler* s, long long out[2]) {
   if (!s || !out) return PAYNE_E_INVALID;
-  out[0] = s->n_tail; out[1] = s->n_own;
+  out[0] = s->n_tail; out[1] = s->n_own + s->n_slice;
   return PAYNE_OK;
 }
 extern "C" int payne_rwalk_batch(payne_sampler* s, double* u, double* v, double* lnprob, int K, const double* axes,
@@ -1691,6 +1701,85 @@ extern "C" int payne_rwalk_batch(payne_sampler* s, double* u, double* v, double*
                                  void* stream) {
   int rc = payne_rwalk_begin(s, u, v, lnprob, K, axes, scale, loglstar, walks, seed, nacc, ncall, stream);
   for (int w = 0; !rc && w <= walks; ++w) rc = payne_rwalk_step(s, w);
+  return rc;
+}
+
+// Slice sampling as lock-step chains on the device (header: payne_slice_begin).  A round is payne_slice_kernel -- settle the value
+// that came back, go on to the chain's next in-cube point -- and one likelihood batch over the rows it wrote; the host enqueues
+// rounds and reads ONE word per call (the chains not finished), nothing per chain.
+extern "C" int payne_slice_begin(payne_sampler* s, double* u, double* v, double* lnprob, int K, const double* axes, int n_ell,
+                                 const int* ell, double scale, double loglstar, int slices, int random_dirs,
+                                 unsigned long long seed, int* ncall, int* nexpand, int* ncontract, void* stream) {
+  int rc = sampler_check(s, u, K, v);
+  if (rc) return rc;
+  payne_ctx* c = s->ctx;
+  if (!lnprob || !axes || !ncall || !nexpand || !ncontract) return fail(c, PAYNE_E_INVALID, "bad slice arguments");
+  if (slices <= 0) return fail(c, PAYNE_E_INVALID, "slices must be > 0");
+  if (n_ell < 1 || n_ell > PAYNE_MAX_ELL || (n_ell > 1 && !ell)) return fail(c, PAYNE_E_INVALID, "bad ellipsoid list");
+  if (ell)
+    for (int i = 0; i < K; ++i)
+      if (ell[i] < 0 || ell[i] >= n_ell) return fail(c, PAYNE_E_INVALID, "ellipsoid index out of range");
+  if (s->run.open || s->queue_open || s->dq_launched != s->dq_collected)
+    return fail(c, PAYNE_E_INVALID, "a random walk is open on this sampler");
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  const int nd = s->sd.ndim;
+  HIPCHK(c, hipMemcpyAsync(s->axes, axes, (size_t)n_ell * nd * nd * 8, hipMemcpyHostToDevice, st));
+  if (ell) HIPCHK(c, hipMemcpyAsync(s->ell, ell, (size_t)K * 4, hipMemcpyHostToDevice, st));
+  const size_t kn = (size_t)s->k_max * nd, km = (size_t)s->k_max;
+  s->slice = SliceState{u, v, lnprob, s->sl_win, s->sl_win + kn, s->sl_win + 2 * kn,
+                        s->sl_int, s->sl_int + km, s->sl_int + 2 * km, s->sl_int + 3 * km, ncall, nexpand, ncontract,
+                        s->u_prop, s->v_prop, s->lnprior, s->inside, s->rows, s->axes, ell ? s->ell : (const int*)nullptr,
+                        s->sl_int + 4 * km, scale, loglstar, seed, K, nd, s->sd.ncols,
+                        (s->sd.adv.imf || s->sd.adv.vrot || s->sd.adv.plx_dim >= 0) ? 1 : 0,
+                        random_dirs ? slices : slices * nd, random_dirs ? 1 : 0};
+  s->srun = {true, false, true, stream};
+  return PAYNE_OK;
+}
+extern "C" int payne_slice_rounds(payne_sampler* s, int n, int* n_active) {
+  if (!s || !s->ctx) return PAYNE_E_INVALID;
+  payne_ctx* c = s->ctx;
+  if (!s->srun.open) return fail(c, PAYNE_E_INVALID, "payne_slice_rounds outside a walk");
+  if (n <= 0 || !n_active) return fail(c, PAYNE_E_INVALID, "bad payne_slice_rounds arguments");
+  int dev = 0;
+  (void)hipGetDevice(&dev);
+  if (dev != c->device) (void)hipSetDevice(c->device);
+  hipStream_t st = reinterpret_cast<hipStream_t>(s->srun.stream);
+  const int K = s->slice.K;
+  const dim3 grid((K + 3) / 4), block(256);                     // one wave per chain
+  int rc = PAYNE_OK;
+  for (int r = 0; r < n && !rc; ++r) {
+    hipLaunchKernelGGL(payne_slice_kernel, grid, block, 0, st, s->sd, s->slice, s->lnl, s->srun.pending ? 1 : 0, 1, s->srun.first ? 1 : 0);
+    s->srun.pending = true; s->srun.first = false;
+    s->n_slice += 1;
+    rc = lnlike_impl(c, s->rows, K, s->lnl, s->srun.stream, nullptr);
+  }
+  if (rc) { s->srun.open = false; return rc; }
+  // the closing launch settles what is pending and counts the chains that have not finished: one word for the host
+  hipLaunchKernelGGL(payne_slice_kernel, grid, block, 0, st, s->sd, s->slice, s->lnl, 1, 0, 0);
+  s->srun.pending = false;
+  hipError_t e = hipGetLastError();
+  if (e == hipSuccess) e = hipMemcpyAsync(s->sl_active_host, s->slice.n_active, 4, hipMemcpyDeviceToHost, st);
+  if (e == hipSuccess) e = hipStreamSynchronize(st);
+  if (e != hipSuccess) { s->srun.open = false; return fail(c, PAYNE_E_HIP, std::string("slice rounds: ") + hipGetErrorString(e)); }
+  *n_active = *s->sl_active_host;
+  if (*n_active == 0) s->srun.open = false;
+  return PAYNE_OK;
+}
+extern "C" int payne_slice_batch(payne_sampler* s, double* u, double* v, double* lnprob, int K, const double* axes, int n_ell,
+                                 const int* ell, double scale, double loglstar, int slices, int random_dirs,
+                                 unsigned long long seed, int* ncall, int* nexpand, int* ncontract, void* stream, int chunk,
+                                 int max_rounds, int* n_active) {
+  if (s && (chunk <= 0 || max_rounds <= 0 || !n_active)) return fail(s->ctx, PAYNE_E_INVALID, "bad payne_slice_batch arguments");
+  int rc = payne_slice_begin(s, u, v, lnprob, K, axes, n_ell, ell, scale, loglstar, slices, random_dirs, seed, ncall, nexpand,
+                             ncontract, stream);
+  if (rc) return rc;
+  *n_active = K;
+  for (int done = 0; !rc && *n_active > 0 && done < max_rounds; ) {
+    const int n = std::min(chunk, max_rounds - done);
+    rc = payne_slice_rounds(s, n, n_active);
+    done += n;
+  }
+  s->srun.open = false;                                         // (max_rounds reached: the unfinished chains stay where they are)
   return rc;
 }
 

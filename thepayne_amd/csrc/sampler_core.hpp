@@ -579,4 +579,169 @@ __device__ __forceinline__ void rwalk_settle_spec(const WalkState& W, int c, int
   }
   if (lane < ncols) W.rows[(size_t)c * ncols + lane] = accept ? rowB : rowA;
 }
+
+// ----------------------------------------------------------------------------------------------------------------------
+// Slice sampling (Neal 2003) as dynesty's 'slice' / 'rslice' apply it (Payne/fitting/fitstar.py:292-295, samplemethod / slices=):
+// per direction a window of one axis length placed at random around the point, stepped out while its ends beat the threshold,
+// then sampled and shrunk until a point beats it.  Every value the chain asks for is one likelihood, so the chain is a STATE
+// MACHINE advanced one likelihood batch per round (slice_round_wave): settle the value that came back, then go on until the
+// chain needs exactly one more in-cube point, or has finished.  One wave per chain, lane d = sampled dimension d.
+// The draws are u01(seed, chain, direction, draw within the direction): indexed by the chain's own progress, never by the round,
+// so the chain is a function of seed, start point, bound and the likelihood values alone.  Everything that makes left, right
+// and the candidate is fp64 without contraction: thepayne_amd/sampler/slice_ref.py restates it and gets the same bits.
+// ----------------------------------------------------------------------------------------------------------------------
+constexpr int kSliceMaxShrink = 200;                             // shrink steps after which a direction is given up (the host loop's cap)
+enum { kSliceNew = 0, kSliceLeft = 1, kSliceRight = 2, kSliceShrink = 3, kSliceDone = 4 };
+struct SliceState {
+  double *u, *v, *lnprob;                                        // [K][nd], [K]: the chain's point (the caller's, in/out)
+  double *left, *right, *axis;                                   // [K][nd]: the window's ends and the direction, scaled
+  int *phase, *dir, *attempt, *nshrink;                          // [K]
+  int *ncall, *nexpand, *ncontract;                              // [K] (the caller's)
+  double *u_prop, *v_prop, *lnprior_prop; int* inside; double* rows;   // the pending proposal: the sampler's buffers, as a random walk's
+  const double* axes; const int* ell;                            // [n_ell][nd][nd], columns = axes; [K] or null
+  int* n_active;                                                 // one word: chains not finished, left by the closing launch
+  double scale, loglstar;
+  unsigned long long seed;
+  int K, nd, ncols, adv_on, n_dir, random_dirs;
+};
+// the key lane d sorts by in sweep `sweep` of chain c ('slice': the order of the axes is the order of their keys, ties by index)
+__device__ __forceinline__ unsigned long long slice_key(unsigned long long seed, unsigned chain, unsigned sweep, unsigned d) {
+  return mix64(mix64(~seed ^ ((unsigned long long)chain << 32 | sweep)) + d);
+}
+struct SliceLoads {
+  double uc, vc, left, right, axis, u_p, v_p, lpr, lnl_p;
+  int phase, dir, attempt, nshrink, ncall, nexpand, ncontract, was_in, my_ell;
+  int col_src; double col_val;
+};
+__device__ __forceinline__ SliceLoads slice_loads(const SamplerDev& sd, const SliceState& S, const double* lnl_prop, int c, int lane) {
+  SliceLoads L;                                                  // (valid addresses whatever the flags say)
+  const int dl = lane < S.nd ? lane : 0, colc = lane < S.ncols ? lane : 0;
+  const size_t off = (size_t)c * S.nd + dl;
+  L.col_src = sd.col_src[colc]; L.col_val = sd.col_val[colc];
+  L.uc = S.u[off]; L.vc = S.v[off];
+  L.left = S.left[off]; L.right = S.right[off]; L.axis = S.axis[off];
+  L.u_p = S.u_prop[off]; L.v_p = S.v_prop[off];
+  L.lpr = S.lnprior_prop[c]; L.lnl_p = lnl_prop[c]; L.was_in = S.inside[c];
+  L.phase = S.phase[c]; L.dir = S.dir[c]; L.attempt = S.attempt[c]; L.nshrink = S.nshrink[c];
+  L.ncall = S.ncall[c]; L.nexpand = S.nexpand[c]; L.ncontract = S.ncontract[c];
+  L.my_ell = S.ell ? S.ell[c] : 0;
+  return L;
+}
+// One round of chain c.  `first`: the walk's first round (the chain's state and counters start here: no memsets before it);
+// `settle`: a proposal is pending; `propose` = 0 on the closing launch, which counts the unfinished chains.
+__device__ __forceinline__ void slice_round_wave(const SamplerDev& sd, const SliceState& S, const SliceLoads& L, int c, int lane,
+                                                 int first, int settle, int propose) {
+#pragma clang fp contract(off)
+  const int nd = S.nd, n_dir = S.n_dir;
+  const bool act = lane < nd;
+  const int dl = act ? lane : 0;
+  const size_t off = (size_t)c * nd + dl;
+  const double scale = S.scale, loglstar = S.loglstar;
+  const unsigned long long seed = S.seed;
+  const double* ax = S.axes + (size_t)L.my_ell * nd * nd;
+  double uc = L.uc, vc = L.vc;
+  double left = first ? 0.0 : L.left, right = first ? 0.0 : L.right, axis = first ? 0.0 : L.axis;
+  // (the chain's scalars are the same in every lane: kept in scalar registers, the branches below are the wave's)
+  int phase = first ? (int)kSliceNew : __builtin_amdgcn_readfirstlane(L.phase);
+  int dir = first ? 0 : __builtin_amdgcn_readfirstlane(L.dir);
+  int attempt = first ? 0 : __builtin_amdgcn_readfirstlane(L.attempt);
+  int nshrink = first ? 0 : __builtin_amdgcn_readfirstlane(L.nshrink);
+  int ncall = first ? 0 : __builtin_amdgcn_readfirstlane(L.ncall);
+  int nexpand = first ? 0 : __builtin_amdgcn_readfirstlane(L.nexpand);
+  int ncontract = first ? 0 : __builtin_amdgcn_readfirstlane(L.ncontract);
+  bool moved = false;
+  double lp_new = 0.0;
+  // the window shrunk to `p` (a point on it that failed): the end on p's side of the chain's point moves to p; after
+  // kSliceMaxShrink of them the direction is given up and the point stays
+  auto shrink = [&](double p) {
+#pragma clang fp contract(off)
+    const double side = wave_sum(act ? (p - uc) * (right - left) : 0.0);
+    if (side < 0.0) left = p; else right = p;
+    if (++nshrink >= kSliceMaxShrink) { ++dir; attempt = 0; nshrink = 0; phase = dir >= n_dir ? kSliceDone : kSliceNew; }
+  };
+  if (settle && __builtin_amdgcn_readfirstlane(L.was_in) && phase != kSliceDone) {
+    const double lp = (L.lpr == -INFINITY) ? -INFINITY : L.lpr + L.lnl_p;
+    const bool above = __builtin_amdgcn_readfirstlane(lp > loglstar ? 1 : 0) != 0;     // false for NaN
+    if (phase == kSliceLeft) { if (above) left -= axis; else phase = kSliceRight; }
+    else if (phase == kSliceRight) { if (above) right += axis; else phase = kSliceShrink; }
+    else if (phase == kSliceShrink) {
+      if (above) {
+        uc = L.u_p; vc = L.v_p; lp_new = lp; moved = true;
+        ++dir; attempt = 0; nshrink = 0; phase = dir >= n_dir ? kSliceDone : kSliceNew;
+      } else shrink(L.u_p);
+    }
+  }
+  if (moved) {
+    if (act) { S.u[off] = uc; S.v[off] = vc; }
+    if (lane == 0) S.lnprob[c] = lp_new;
+  }
+  bool emit = false;
+  double cand = uc;
+  while (propose && phase != kSliceDone) {
+    if (phase == kSliceNew) {
+      if (!S.random_dirs) {
+        // the axes of the ellipsoid in a random order per sweep: lane d's place is its key's rank, the axis at place j is next
+        const int sweep = dir / nd, j = dir - sweep * nd;
+        const unsigned long long mine = slice_key(seed, c, sweep, dl);
+        int rank = 0;
+        for (int e = 0; e < nd; ++e) {
+          const unsigned long long k = slice_key(seed, c, sweep, e);
+          rank += (k < mine || (k == mine && e < dl)) ? 1 : 0;
+        }
+        const unsigned long long at = __ballot(act && rank == j);
+        const int col = at ? (int)__builtin_ctzll(at) : 0;
+        axis = scale * ax[dl * nd + col];
+      } else {
+        // a unit vector from Box-Muller draws, one per lane, through the ellipsoid's axes (sums in index order)
+        const double a = u01(seed, c, dir, attempt + 2 * dl), b = u01(seed, c, dir, attempt + 2 * dl + 1);
+        attempt += 2 * nd;
+        double z = act ? sqrt(-2.0 * log(a)) * cospi(2.0 * b) : 0.0;
+        z = z / sqrt(wave_sum(z * z));
+        double s = 0.0;
+        for (int k = 0; k < nd; ++k) s += ax[dl * nd + k] * __shfl(z, k);
+        axis = scale * s;
+      }
+      const double r = u01(seed, c, dir, attempt++);
+      left = uc - r * axis; right = uc + (1.0 - r) * axis;
+      phase = kSliceLeft;
+    }
+    if (phase == kSliceShrink) {
+      ++ncall; ++ncontract;
+      const double t = u01(seed, c, dir, attempt++);
+      cand = left + t * (right - left);
+    } else {
+      ++ncall; ++nexpand;
+      cand = phase == kSliceLeft ? left : right;
+    }
+    if (__ballot(act && !((cand > 0.0) && (cand < 1.0))) == 0ull) { emit = true; break; }
+    // outside the open unit cube: -inf without a call
+    if (phase == kSliceShrink) shrink(cand); else ++phase;
+  }
+  if (propose) {
+    // the candidate's transform, ln-prior and theta row: what the tail of rwalk_step_core writes (a finished chain: its own point as
+    // a harmless valid row, inside = 0)
+    const payne_prior_dim dim = sd.dims[dl];
+    const double vp = emit ? prior_ppf(dim, sd.q0[dl], sd.q1[dl], cand, sd.adv) : vc;
+    double lp = wave_sum(act ? prior_ln(dim, vp) : 0.0);
+    if (S.adv_on) {
+      const payne_adv_priors& a = sd.adv;
+      const double g_ = __shfl(vp, a.dim_logg >= 0 ? a.dim_logg : 0), r_ = __shfl(vp, a.dim_logr >= 0 ? a.dim_logr : 0);
+      const double v_ = __shfl(vp, a.dim_vrot >= 0 ? a.dim_vrot : 0), d_ = __shfl(vp, a.plx_dim >= 0 ? a.plx_dim : 0);
+      const double add = adv_lnprior(a, a.dim_logg >= 0 ? g_ : a.val_logg, a.dim_logr >= 0 ? r_ : a.val_logr,
+                                     a.dim_vrot >= 0 ? v_ : a.val_vrot, a.plx_dim >= 0 ? d_ : 1.0);
+      lp = (lp == -INFINITY || add == -INFINITY) ? -INFINITY : lp + add;
+    }
+    if (act) { S.u_prop[off] = cand; S.v_prop[off] = vp; }
+    if (lane == 0) S.lnprior_prop[c] = lp;
+    const double vs = __shfl(vp, L.col_src >= 0 ? L.col_src : 0);
+    if (lane < S.ncols) S.rows[(size_t)c * S.ncols + lane] = L.col_src >= 0 ? vs : L.col_val;
+  }
+  if (act) { S.left[off] = left; S.right[off] = right; S.axis[off] = axis; }
+  if (lane == 0) {
+    S.inside[c] = emit ? 1 : 0;
+    S.phase[c] = phase; S.dir[c] = dir; S.attempt[c] = attempt; S.nshrink[c] = nshrink;
+    S.ncall[c] = ncall; S.nexpand[c] = nexpand; S.ncontract[c] = ncontract;
+    if (!propose && phase != kSliceDone) atomicAdd(S.n_active, 1);
+  }
+}
 #endif

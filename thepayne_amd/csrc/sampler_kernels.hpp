@@ -60,3 +60,15 @@ __global__ void __launch_bounds__(256) payne_rwalk_kernel(SamplerDev sd, WalkSta
   if (c >= W.K) return;                                         // the whole wave leaves together
   rwalk_step_wave(sd, W, c, lane, lnl_prop[c], step, settle, propose);
 }
+
+// One slice-sampling round for every chain, one wave per chain (slice_round_wave).  `first`: the walk's first round; `propose` = 0 on
+// the closing launch, which leaves the number of unfinished chains in S.n_active (zeroed by every proposing launch before it).
+__global__ void __launch_bounds__(256) payne_slice_kernel(SamplerDev sd, SliceState S, const double* lnl_prop, int settle, int propose,
+                                                             int first) {
+  const int lane = threadIdx.x & 63;
+  const int c = (int)((blockIdx.x * blockDim.x + threadIdx.x) >> 6);
+  if (propose && blockIdx.x == 0 && threadIdx.x == 0) *S.n_active = 0;
+  if (c >= S.K) return;                                         // the whole wave leaves together
+  const SliceLoads L = slice_loads(sd, S, lnl_prop, c, lane);
+  slice_round_wave(sd, S, L, c, lane, first, settle, propose);
+}

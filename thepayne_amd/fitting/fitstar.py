@@ -287,6 +287,7 @@ class FitPayne(object):
             bootstrap=samplerdict.get('bootstrap', 0), walks=numwalks, slices=samplerdict.get('slices', 5),
             batched=True, queue_size=samplerdict.get('queue_size', npoints),
             pipeline=samplerdict.get('pipeline'),      # None: with device proposals the turn between two queues on the device ('device'), else queues launched ahead from the host's turn
+            slice_device=bool(samplerdict.get('slice_device', False)) and samplemethod in ('slice', 'rslice'),   # the slice chain on the device (payne_slice_batch)
             rstate=np.random.default_rng(seed))
         self.parnames = list(self.likeobj.fitpars_i) + list(self.fitargs['fixedpars'].keys())
         self.fitargs_fixed = dict(self.fitargs['fixedpars'])

@@ -385,6 +385,81 @@ class DeviceProposer(object):
         return (h[:K * nd].reshape(K, nd).copy(), h[K * nd:2 * K * nd].reshape(K, nd).copy(), h[2 * K * nd:n].copy(),
                 ih[:K].astype(np.int64), ih[K:2 * K].astype(np.int64))
 
+    # ---- slice sampling on the device (payne_slice_*): the chain is a state machine there, a round is one likelihood batch
+    def _slice_args(self, U, V, lnprob, axes, scale, loglstar, slices, random_dirs, seed, ell, stream):
+        """Upload the chains (one packed pinned transfer) and build the argument list payne_slice_begin / _batch share."""
+        K, nd = len(U), self.ndim
+        if K > self.k_max:
+            raise ValueError("K > k_max")
+        t = self.torch
+        if getattr(self, "_sl_pack_h", None) is None:
+            n = self.k_max * (2 * nd + 1)
+            self._sl_pack_h = t.empty(n, dtype=t.float64).pin_memory()
+            self._sl_pack_d = t.empty(n, dtype=t.float64, device=self.eng.device)
+            self._sl_ipack_h = t.empty(3 * self.k_max, dtype=t.int32).pin_memory()
+            self._sl_ipack_d = t.empty(3 * self.k_max, dtype=t.int32, device=self.eng.device)
+        self._sl_stream = stream if stream is not None else t.cuda.current_stream(self.eng.device)
+        n = K * (2 * nd + 1)
+        h = self._sl_pack_h.numpy()
+        h[:K * nd] = np.asarray(U, dtype=np.float64).reshape(-1)
+        h[K * nd:2 * K * nd] = np.asarray(V, dtype=np.float64).reshape(-1)
+        h[2 * K * nd:n] = lnprob
+        d = self._sl_pack_d
+        with t.cuda.stream(self._sl_stream):
+            d[:n].copy_(self._sl_pack_h[:n], non_blocking=True)
+        ax = np.ascontiguousarray(axes, dtype=np.float64)
+        n_ell, ell_p = 1, None
+        if ax.ndim == 3:
+            n_ell = ax.shape[0]
+            if n_ell > 1:
+                self._sl_ell_h = np.ascontiguousarray(ell, dtype=np.int32)
+                if self._sl_ell_h.shape != (K,):
+                    raise ValueError("ell must name one ellipsoid per chain")
+                ell_p = self._sl_ell_h.ctypes.data
+        self._sl_ax, self._sl_K = ax, K
+        ip = self._sl_ipack_d.data_ptr()
+        return (self._handle, d.data_ptr(), d.data_ptr() + 8 * K * nd, d.data_ptr() + 16 * K * nd, K, ax.ctypes.data, n_ell, ell_p,
+                float(scale), float(loglstar), int(slices), 1 if random_dirs else 0, int(seed) & 0xFFFFFFFFFFFFFFFF,
+                ip, ip + 4 * K, ip + 8 * K, C.c_void_p(self._sl_stream.cuda_stream))
+
+    def slice_begin(self, U, V, lnprob, axes, scale, loglstar, slices, random_dirs, seed, ell=None, stream=None):
+        """payne_slice_begin: K lock-step slice-sampling chains under lnprob > loglstar ('slice': `slices` sweeps over the columns
+        of `axes`; random_dirs: `slices` random directions).  ``axes``: [ndim, ndim] or [n_ell, ndim, ndim] with ``ell[K]``."""
+        rc = self.lib.payne_slice_begin(*self._slice_args(U, V, lnprob, axes, scale, loglstar, slices, random_dirs, seed, ell, stream))
+        if rc != 0:
+            self.eng._err(rc, "payne_slice_begin")
+
+    def slice_rounds(self, n):
+        """payne_slice_rounds: n more rounds of the walk begun; returns the number of chains that have not finished."""
+        na = C.c_int(0)
+        rc = self.lib.payne_slice_rounds(self._handle, int(n), C.byref(na))
+        if rc != 0:
+            self.eng._err(rc, "payne_slice_rounds")
+        return na.value
+
+    def slice_finish(self):
+        """The chains and their counters back: (U, V, lnprob, ncall, nexpand, ncontract)."""
+        K, nd, t = self._sl_K, self.ndim, self.torch
+        n = K * (2 * nd + 1)
+        with t.cuda.stream(self._sl_stream):
+            self._sl_pack_h[:n].copy_(self._sl_pack_d[:n], non_blocking=True)
+            self._sl_ipack_h[:3 * K].copy_(self._sl_ipack_d[:3 * K], non_blocking=True)
+        self._sl_stream.synchronize()
+        h = self._sl_pack_h.numpy()
+        ih = self._sl_ipack_h.numpy()
+        return (h[:K * nd].reshape(K, nd).copy(), h[K * nd:2 * K * nd].reshape(K, nd).copy(), h[2 * K * nd:n].copy(),
+                ih[:K].astype(np.int64), ih[K:2 * K].astype(np.int64), ih[2 * K:3 * K].astype(np.int64))
+
+    def slice_walk(self, U, V, lnprob, axes, scale, loglstar, slices, random_dirs, seed, ell=None, chunk=16, max_rounds=None):
+        """One whole slice walk in one native call (payne_slice_batch): one upload, rounds enqueued `chunk` at a time until no
+        chain is active (or `max_rounds` are spent), one download.  Returns (U, V, lnprob, ncall, nexpand, ncontract, n_active)."""
+        args = self._slice_args(U, V, lnprob, axes, scale, loglstar, slices, random_dirs, seed, ell, None)
+        na = C.c_int(0)
+        rc = self.lib.payne_slice_batch(*args, int(chunk), int(max_rounds) if max_rounds is not None else 2 ** 31 - 1, C.byref(na))
+        if rc != 0:
+            self.eng._err(rc, "payne_slice_batch")
+        return self.slice_finish() + (na.value,)
+
     def step_counters(self):
         """(chain steps run at the likelihood-only post kernel's tail, chain steps launched on their own) so far."""
         out = (C.c_longlong * 2)()

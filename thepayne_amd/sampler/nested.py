@@ -118,7 +118,8 @@ class NestedSampler(object):
     def __init__(self, loglikelihood, prior_transform, ndim, nlive=500, bound='multi', sample='unif',
                  logl_args=None, bootstrap=0, walks=25, slices=5, enlarge=None, rstate=None,
                  batched=False, queue_size=None, update_interval=None, first_update=None, proposer=None,
-                 native=True, live_points=None, loglstar=None, overlap_bound=None, pipeline=None, **ignored):
+                 native=True, live_points=None, loglstar=None, overlap_bound=None, pipeline=None, slice_device=False,
+                 slice_chunk=16, **ignored):
         if sample not in ('unif', 'rwalk', 'slice', 'rslice'):
             raise NotImplementedError("sample=%r: this driver provides 'unif', 'rwalk', 'slice' and 'rslice'" % (sample,))
         if bound not in ('none', 'single', 'multi'):
@@ -185,6 +186,13 @@ class NestedSampler(object):
         # sampling region) never uses it.  Default: on when the proposer can run the walk in two parts.
         self.overlap_bound = (sample == 'rwalk' and hasattr(proposer, "rwalk_queue")) if overlap_bound is None else bool(overlap_bound)
         self._bound_next = None
+        # slice_device: 'slice' / 'rslice' queues as ONE call of the proposer's slice_walk (the chain a state machine on the device, a
+        # round one likelihood batch, the host out of the loop: payne_slice_batch) instead of the numpy loop of _fill_queue_slice,
+        # which makes a host turn per round.  Off by default: the draws are the device's, so a seed gives another run.
+        self.slice_device = bool(slice_device)
+        self.slice_chunk = int(slice_chunk)
+        if self.slice_device and not hasattr(proposer, "slice_walk"):
+            raise ValueError("slice_device=True needs a proposer with slice_walk (thepayne_amd.sampler.device.DeviceProposer)")
         # pipeline: with the whole queue made on the device, the NEXT queue is launched before the current one is consumed, from
         # the live set and the threshold the consumption will leave (payne_ns_peek: the replacements only, no evidence
         # arithmetic) -- the GPU walks while the host does the bookkeeping of the queue before, fits the bound and yields the
@@ -554,7 +562,20 @@ class NestedSampler(object):
             ell = np.where((d2 <= 1.0).any(axis=0), np.argmax(d2 <= 1.0, axis=0), np.argmin(d2, axis=0))
             A = np.stack([e.axes for e in self._ells])[ell]                       # [K, nd, nd], columns = axes
         else:
+            ell = None
             A = np.broadcast_to(self._axes, (K, nd, nd))
+        if self.slice_device and self.method in ('slice', 'rslice'):
+            # the whole walk in one device call: same start points, same ellipsoid per chain, same scale rule
+            axes = self._axes if ell is None else np.stack([e.axes for e in self._ells])
+            kw = {} if ell is None else {"ell": ell}
+            U, V, ll, ncalls, nexp, ncon, _ = self.proposer.slice_walk(
+                U, V, ll, axes, self.scale, lstar, self.slices, self.method == 'rslice', int(rng.integers(0, 2 ** 62)),
+                chunk=self.slice_chunk, **kw)
+            ll = np.where(np.isnan(ll), -np.inf, ll)
+            self.ncall += int(ncalls.sum())
+            self.scale = min(max(self.scale * float(nexp.sum()) / max(1.0, 2.0 * float(ncon.sum())), 1e-4), 8.0)
+            self._set_queue(U, V, ll, np.maximum(1, ncalls))
+            return
         ncalls = np.zeros(K, dtype=np.int64)
         nexpand = ncontract = 0
         n_dir = self.slices * nd if self.method == 'slice' else self.slices

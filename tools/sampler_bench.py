@@ -2,6 +2,7 @@
 likelihood calls per second as the sampler sees them, host proposals vs device proposals.
 
   python tools/sampler_bench.py [--maxcall 400000] [--nlive 512] [--walks 25]
+  python tools/sampler_bench.py --method slice --slices 5 --modes slice_host,slice_device [--slice-chunk 16]
 
 The synthetic spectrum is produced with the engine itself (no oracle: this is a timing tool).
 """
@@ -67,14 +68,17 @@ def make_problem(config="C2", nlive=512, variant=0):
 
 
 def run(config="C2", maxcall=300000, nlive=512, walks=25, modes=("host", "device", "device_chunks", "device2_chunks"),
-        verbose=False, bound='multi', variant=0, seed=1, dlogz=0.01, complete=False):
+        verbose=False, bound='multi', variant=0, seed=1, dlogz=0.01, complete=False, method='rwalk', slices=5, slice_chunk=16):
     """Likelihood calls per second as the nested sampler sees them (prior transform, proposals, transfers,
     bookkeeping included).  Returns {mode: {...}}.  config 'C3' = C2 + photometry in seven filters (joint fit, photscale).
     `seed`: the sampler's random stream; `dlogz`: stopping threshold (tiny: the run ends at `maxcall`); `complete`: the run is a whole
     fit (maxcall=None, dlogz as the reference's delta_logz_final) and the remaining live points are added inside the timed region.
     Modes: "device_chunks" = proposals on the device, the sampler's default loop (the turn between two queues on the device where the
     proposer offers it); "..._hostturn" = the turn made on the host, queues launched ahead; "..._serial" = every queue launched after
-    the one before is consumed; "..._devturn" = pipeline='device' asked for by name."""
+    the one before is consumed; "..._devturn" = pipeline='device' asked for by name.  With method 'slice' / 'rslice': "slice_host" = the lock-step rounds driven
+    from numpy (one payne_lnprob_u_batch call and two host turns per round), "slice_device" = the chain on the device
+    (NestedSampler(slice_device=True): one payne_slice_batch call per queue, `slice_chunk` rounds per host turn); both report
+    calls per iteration and the rounds (likelihood batches) per queue."""
     L, P = make_problem(config, nlive, variant)
     out = {}
     for mode in modes:
@@ -92,7 +96,22 @@ def run(config="C2", maxcall=300000, nlive=512, walks=25, modes=("host", "device
             mode_ = mode[:-len("_hostturn")]
         else:
             mode_ = mode
-        if mode.startswith("device2"):                      # two chain populations in flight
+        if mode in ("slice_host", "slice_device"):
+            from thepayne_amd.sampler.device import DeviceProposer
+            if method not in ("slice", "rslice"):
+                raise ValueError("mode %s needs --method slice or rslice" % mode)
+            proposer = DeviceProposer(L, P, k_max=nlive)
+            kw.update(slice_device=mode == "slice_device", slice_chunk=slice_chunk, slices=slices)
+            mode_ = "device_chunks"
+            batches = [0]                                   # likelihood batches: lnprob_u calls (host) / rounds (device, step_counters)
+            if mode == "slice_host":
+                inner = proposer.lnprob_u
+
+                def counted(U, inner=inner, batches=batches):
+                    batches[0] += 1
+                    return inner(U)
+                proposer.lnprob_u = counted
+        elif mode.startswith("device2"):                      # two chain populations in flight
             from thepayne_amd.sampler.device import MultiPopProposer
             proposer = MultiPopProposer(L, P, k_max=nlive, n_pop=2)
             queue = 2 * nlive
@@ -100,8 +119,11 @@ def run(config="C2", maxcall=300000, nlive=512, walks=25, modes=("host", "device
             from thepayne_amd.sampler.device import DeviceProposer
             proposer = DeviceProposer(L, P, k_max=nlive)
         S = NestedSampler(lnprob_batch, P.priortrans_batch, L.ndim, logl_args=[L, P], nlive=nlive, bound=bound,
-                          sample='rwalk', walks=walks, batched=True, queue_size=queue,
+                          sample=method, walks=walks, batched=True, queue_size=queue,
                           rstate=np.random.default_rng(seed), proposer=proposer, **kw)
+        if mode.startswith("slice_"):
+            batches[0] = 0
+            r0 = proposer.step_counters()[1]
         t0 = time.perf_counter()
         c0 = S.ncall
         nell = 1
@@ -119,6 +141,12 @@ def run(config="C2", maxcall=300000, nlive=512, walks=25, modes=("host", "device
                      "logzerr": float(np.sqrt(max(S.logzvar, 0.0))),
                      "evals_per_s": round((S.ncall - c0) / dt), "logz": float(S.logz), "scale": float(S.scale), "max_ellipsoids": nell,
                      **({"resyncs": int(S._dev_desync)} if getattr(S, "_dev_turn", False) else {})}
+        if mode.startswith("slice_"):
+            rounds = batches[0] if mode == "slice_host" else proposer.step_counters()[1] - r0
+            out[mode].update({"method": method, "slices": slices, "queues": int(S._cycle), "rounds": int(rounds),
+                              "rounds_per_queue": round(rounds / max(1, S._cycle), 1),
+                              "calls_per_iteration": round((S.ncall - c0) / max(1, S.it - 1), 2),
+                              **({"chunk": slice_chunk} if mode == "slice_device" else {})})
         if verbose:
             print(mode, json.dumps(out[mode]), flush=True)
         if proposer is not None:
@@ -137,9 +165,14 @@ def main():
     ap.add_argument("--bound", default="multi")
     ap.add_argument("--variant", type=int, default=0, help="payne_opts.variant (PAYNE_V_* bits)")
     ap.add_argument("--dlogz", type=float, default=0.01, help="stopping threshold (tiny: the run ends at --maxcall)")
+    ap.add_argument("--method", default="rwalk", choices=["rwalk", "slice", "rslice"])
+    ap.add_argument("--slices", type=int, default=5)
+    ap.add_argument("--slice-chunk", type=int, default=16, help="slice_device: rounds enqueued per host turn")
+    ap.add_argument("--seed", type=int, default=1)
     a = ap.parse_args()
-    out = run(a.config, a.maxcall, a.nlive, a.walks, tuple(a.modes.split(",")), verbose=True, bound=a.bound, variant=a.variant, dlogz=a.dlogz)
-    print(json.dumps({"sampler_bench": out, "config": a.config, "nlive": a.nlive, "walks": a.walks}))
+    out = run(a.config, a.maxcall, a.nlive, a.walks, tuple(a.modes.split(",")), verbose=True, bound=a.bound, variant=a.variant, dlogz=a.dlogz,
+              seed=a.seed, method=a.method, slices=a.slices, slice_chunk=a.slice_chunk)
+    print(json.dumps({"sampler_bench": out, "config": a.config, "nlive": a.nlive, "walks": a.walks, "method": a.method}))
 
 
 if __name__ == "__main__":
