@@ -247,6 +247,27 @@ int payne_smooth_batch(payne_ctx* ctx, const float* spectra, int ld_spec, const 
 int payne_smooth_direct(int device, int kind, const double* wave, const double* spec, int n, const double* outwave, int nout,
                         const double* sigma, int nsig, double inres, int in_vel, double nsigma, double* out);
 
+/* The velocity scan of RVcalc (Payne/fitting/fitutils.py:79-94, scanned by scipy.optimize.brute at :64-69) for G velocities
+ * at once, on caller-supplied HOST arrays, synchronous, no context (like payne_smooth_direct):
+ *   chisq[g] = sum_i (m_gi - flux_i)^2 / eflux_i^2,
+ * m_gi = interp1d(modwave * (1 + rv_g / 299792.458), modflux, kind='linear', bounds_error=False, fill_value=1.0)(wave_i):
+ * bracket by searchsorted (side left, clipped to [1, nm - 1]), both end points inside, 1.0 outside.  NaN in modflux or flux
+ * makes chisq[g] NaN wherever it is reached (no pixel is skipped, as in the reference).  fp64 throughout; the sum is formed in
+ * a fixed order, so the same call returns the same bits.
+ * PAYNE_E_INVALID: null pointers, nm < 2, nobs < 1, G < 1, modwave not strictly increasing. */
+int payne_rv_scan(int device, const double* modwave, const double* modflux, int nm, const double* wave, const double* flux,
+                  const double* eflux, int nobs, const double* rv, int G, double* chisq);
+
+/* The masked chi^2 that ends BROADcalc.chisq_broad (Payne/fitting/fitutils.py:148-154) for G rows: rows is device fp32
+ * [G][ld] as payne_smooth_batch writes them, n valid pixels per row; flux, eflux: HOST fp64 [n]; chisq: HOST fp64 [G];
+ * n_kept: HOST int32 [G].  The pixels with rows[g][i] < threshold are kept (NaN compares false), compacted in order; the j-th
+ * kept model value is paired with the j-th kept flux and with eflux[j], the first n_kept entries of the UNMASKED error vector
+ * -- the reference's line `eflux[cond]` discards its result and zip() truncates: its arithmetic is reproduced, not its intent.
+ * The kernel is enqueued on `stream` (behind whatever wrote the rows there) and the call synchronises it before returning.
+ * PAYNE_E_INVALID: null pointers, n < 1, n > ld, G < 1. */
+int payne_chisq_below(int device, const float* rows, int ld, int n, int G, const double* flux, const double* eflux,
+                      double threshold, double* chisq, int* n_kept, void* stream);
+
 /* Magnitudes for B parameter vectors: FastPayneSEDPredict.sed
  * (Payne/predict/predictsed.py:75-103).  pars: device fp64 [B][9] =
  * logt, logg, feh, afe, av, rv, logl, dist, logA  (NaN = kwarg absent; the

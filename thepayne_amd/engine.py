@@ -199,11 +199,14 @@ class PayneEngine(object):
             self._err(rc, "payne_ctx_set_obs")
 
     def smooth_batch(self, spectra, theta, stage=2, fwhm_R=False):
-        """The broadening stages on caller-supplied spectra [B, npix] (full flux on the model grid):
-        payne_smooth_batch.  Returns a fp32 device tensor [B, npix | nobs]."""
+        """The broadening stages on caller-supplied spectra [B, npix] (full flux on the model grid; a host array or a
+        device tensor): payne_smooth_batch.  Returns a fp32 device tensor [B, npix | nobs]."""
         t = self._theta(theta, self.ncols)
         B = t.shape[0]
-        sp = self.torch.as_tensor(np.ascontiguousarray(spectra, dtype=np.float32)).to(self.device).reshape(B, self.npix)
+        if isinstance(spectra, self.torch.Tensor):
+            sp = spectra.to(device=self.device, dtype=self.torch.float32).contiguous().reshape(B, self.npix)
+        else:
+            sp = self.torch.as_tensor(np.ascontiguousarray(spectra, dtype=np.float32)).to(self.device).reshape(B, self.npix)
         n_out = self.npix if stage < 2 else self.nobs          # (stage 4: rotational broadening onto the observed grid)
         out = self.torch.empty((B, n_out), dtype=self.torch.float32, device=self.device)
         for s in range(0, B, self.b_max):

@@ -342,9 +342,10 @@ class PayneSpecPredict(object):
                        nsigma=nsig)
         return run(_lib.SMOOTH_VEL_DIRECT, w, s, ow, sig, inres=inres or 0.0, nsigma=nsig)
 
-    def _smooth_engine(self, wave, r_in):
-        """A context whose model grid is ``wave`` (a two-layer dummy network: only the broadening stages run)."""
-        key = (len(wave), float(wave[0]), float(wave[-1]), hash(wave.tobytes()), float(r_in))
+    def _smooth_engine(self, wave, r_in, b_max=8):
+        """A context whose model grid is ``wave`` (a two-layer dummy network: only the broadening stages run); ``b_max`` rows
+        per call (one spectrum at a time here; fitutils.BROADcalc broadens a whole grid of resolutions)."""
+        key = (len(wave), float(wave[0]), float(wave[-1]), hash(wave.tobytes()), float(r_in), int(b_max))
         cache = self.__dict__.setdefault('_smooth_cache', {})
         if key not in cache:
             if len(cache) >= 4:
@@ -353,7 +354,7 @@ class PayneSpecPredict(object):
             net = {"layers": [(np.zeros((4, 1), np.float32), np.zeros(4, np.float32), 0),
                               (np.zeros((n, 4), np.float32), np.ones(n, np.float32), 0)],
                    "xmin": np.array([0.0]), "xmax": np.array([1.0]), "wavelength": wave, "resolution": float(r_in)}
-            cache[key] = PayneEngine(net, b_max=8, device=self._device_index())
+            cache[key] = PayneEngine(net, b_max=int(b_max), device=self._device_index())
         return cache[key]
 
     def _device_index(self):
