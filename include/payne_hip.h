@@ -268,6 +268,21 @@ int payne_rv_scan(int device, const double* modwave, const double* modflux, int 
 int payne_chisq_below(int device, const float* rows, int ld, int n, int G, const double* flux, const double* eflux,
                       double threshold, double* chisq, int* n_kept, void* stream);
 
+/* The medians TestSpec's report takes of its residual matrix (Payne/testing/testspec.py:94-108, :125-208, :227-361).  All
+ * pointers are DEVICE pointers: pred fp32 [N][ld_pred], truth fp32 [N][ld_truth] (P valid pixels per row, the padding is never
+ * read), groups uint8 [G][N] (non-zero = the row belongs to the set).  With r[i][j] = fabs((double)truth[i][j] -
+ * (double)pred[i][j]), never stored:
+ *   pix_med[g][j] = np.median of { r[i][j] : groups[g][i] != 0 }     fp64 [G][P]
+ *   row_med[i]    = np.median of r[i][0..P-1]                        fp64 [N]; NULL: not computed
+ * np.median: the elements of rank (m-1)>>1 and m>>1 averaged as 0.5 * (lo + hi); NaN if any member is NaN; NaN for an empty
+ * set.  Found by radix selection on the integer image of r (csrc/mad_core.hpp): exact, and the same bits on every call.
+ * G == 0 with row_med != NULL is valid (row medians only).  The kernels are enqueued on `stream` (behind whatever wrote the two
+ * matrices there) and the call synchronises it before returning.
+ * PAYNE_E_INVALID (nothing is written): null pred / truth / pix_med, N < 1, P < 1, ld_pred < P, ld_truth < P, G < 0,
+ * groups == NULL with G > 0.  PAYNE_E_UNSUPPORTED: G > 65535. */
+int payne_mad_stats(int device, const float* pred, int ld_pred, const float* truth, int ld_truth, int N, int P,
+                    const unsigned char* groups, int G, double* pix_med, double* row_med, void* stream);
+
 /* Magnitudes for B parameter vectors: FastPayneSEDPredict.sed
  * (Payne/predict/predictsed.py:75-103).  pars: device fp64 [B][9] =
  * logt, logg, feh, afe, av, rv, logl, dist, logA  (NaN = kwarg absent; the

@@ -34,7 +34,7 @@ SYMBOLS = ["payne_version", "payne_ctx_create", "payne_ctx_set_obs", "payne_ctx_
            "payne_rwalk_batch", "payne_rwalk_begin", "payne_rwalk_begin_ell", "payne_rwalk_step", "payne_sampler_counters", "payne_ns_rwalk_queue", "payne_ns_rwalk_queue_begin", "payne_ns_rwalk_queue_end", "payne_ns_rwalk_queue_turn", "payne_ns_consume", "payne_ns_peek", "payne_ns_bound", "payne_format_rows",
            "payne_ns_queue_dev_init", "payne_ns_queue_dev_launch", "payne_ns_queue_dev_collect",
            "payne_slice_begin", "payne_slice_rounds", "payne_slice_batch",
-           "payne_rv_scan", "payne_chisq_below"]
+           "payne_rv_scan", "payne_chisq_below", "payne_mad_stats"]
 
 PAYNE_MAX_DIM, PAYNE_MAX_FIXED = 24, 16
 PRIOR_UNIFORM, PRIOR_GAUSSIAN, PRIOR_TGAUSSIAN, PRIOR_EXP, PRIOR_TEXP, PRIOR_LOGUNIFORM, PRIOR_TABLE = range(7)
@@ -153,6 +153,9 @@ def load(path=None):
     lib.payne_chisq_below.argtypes = [C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_double,
                                       C.c_void_p, C.c_void_p, C.c_void_p]
     lib.payne_chisq_below.restype = C.c_int
+    lib.payne_mad_stats.argtypes = [C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int,
+                                    C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.payne_mad_stats.restype = C.c_int
     lib.payne_ctx_destroy.argtypes = [ctxp]
     lib.payne_ctx_destroy.restype = None
     lib.payne_last_error.argtypes = [ctxp]

@@ -106,6 +106,26 @@ def make_torch_net(kind, npix=1024, lam0=5150.0, R_fwhm=32000.0, H=(64, 48, 32),
     return net
 
 
+def add_test_set(net, forward, n=65, seed=0, labels=None, sigma=1e-3):
+    """`net` (make_torch_net / make_yst_net) with the held-out test set a training run stores beside the weights
+    (Payne/predict/predictspec.py:51-54): ``testlabels`` [n, D] drawn inside xmin..xmax (or `labels` as given) and ``testpred`` =
+    `forward(testlabels)` -- any forward pass of the network, [n, npix] -- plus fp32 noise of standard deviation `sigma`, in
+    fp32.  Returns a new dict; ``nnio.save_npz`` writes it as a network file ``TestSpec`` reads."""
+    rng = np.random.default_rng(seed)
+    xmin = np.asarray(net["xmin"] if "xmin" in net else net["x_min"], dtype=np.float64)
+    xmax = np.asarray(net["xmax"] if "xmax" in net else net["x_max"], dtype=np.float64)
+    if labels is None:
+        labels = xmin + (xmax - xmin) * rng.uniform(0.02, 0.98, (n, len(xmin)))
+    labels = np.asarray(labels, dtype=np.float64)
+    if np.any(labels < xmin) or np.any(labels > xmax):
+        raise ValueError("test labels outside the network's xmin..xmax")
+    pred = np.asarray(forward(labels), dtype=np.float32)
+    out = dict(net)
+    out["testlabels"] = labels
+    out["testpred"] = pred + rng.normal(0.0, sigma, pred.shape).astype(np.float32)
+    return out
+
+
 PHOT_FILTERS = ['Bessell_B', 'Bessell_V', 'Bessell_R', 'Bessell_I', '2MASS_J', '2MASS_H', '2MASS_Ks']
 PHOT_LABEL_MIN = np.array([2500.0, -1.0, -4.0, -0.2, 0.0, 2.0])
 PHOT_LABEL_MAX = np.array([20000.0, 5.5, 0.5, 0.6, 5.0, 5.0])
