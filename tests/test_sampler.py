@@ -380,6 +380,176 @@ int main() {
     assert res.returncode == 0 and "bad=0" in res.stdout, (res.stdout, res.stderr[-2000:])
 
 
+def test_queue_block_layout_under_address_and_ub_sanitizers(tmp_path):
+    """csrc/queue_block.hpp (the queue's staging block: host code) built with g++ -fsanitize=address,undefined.  For K in {1, 2, 3, 64},
+    nd in {1, 3, PAYNE_MAX_DIM}, n_ell in {1, 2, PAYNE_MAX_ELL}: the regions lie inside the capacity, in order, without overlap,
+    doubles 8-aligned and ints 4-aligned, at the offsets the entry points used to compute by hand (written out here); the completion
+    words and the {scale, loglstar} pair lie inside their host blocks and outside what travels.  queue_extract returns the chains
+    that moved, in order (NaN -> -inf, calls >= 1) with independently computed sums; fill_starts copies the rows a re-statement of
+    the splitmix rule selects, with and without `src`; pack_bound, check_ell_list and adapt_scale against their literal forms."""
+    import os, subprocess
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    main = tmp_path / "main.cpp"
+    main.write_text(r'''
+#include <cmath>
+#include <cstdio>
+#include <cstdlib>
+#include <cstring>
+#include <string>
+#include <vector>
+#include "thepayne_amd/csrc/queue_block.hpp"
+namespace pq = payne_queue;
+static int bad = 0;
+#define CHECK(x) do { if (!(x)) { ++bad; std::printf("line %d: %s\n", __LINE__, #x); } } while (0)
+static unsigned long long mix_ref(unsigned long long x) {
+  x += 0x9E3779B97F4A7C15ull;
+  x ^= x >> 30; x *= 0xBF58476D1CE4E5B9ull;
+  x ^= x >> 27; x *= 0x94D049BB133111EBull;
+  x ^= x >> 31;
+  return x;
+}
+static double rnd() { return rand() / (double)RAND_MAX; }
+struct Region { size_t lo, n, align; };           // bytes
+
+static void layout(int Ki, int ndi, int nei) {
+  const size_t K = Ki, nd = ndi, n_ell = nei;
+  const pq::Layout L(Ki, ndi, nei);
+  // the parent's formulas, literally
+  const size_t nq_d = K * (2 * nd + 1), n_cnt = (3 * K + 1) / 2, n_ax = n_ell * nd * nd;
+  const size_t n_as = n_ell > 1 ? n_ell * nd + n_ax : 0;
+  const size_t hv = K * nd, hl = hv + K * nd, hax = hl + K + n_cnt;
+  const size_t cap = K * (2 * nd + 1) + (3 * K + 1) / 2 + (size_t)PAYNE_MAX_ELL * (2 * nd * nd + nd) + (K + 1) / 2;
+  CHECK(pq::capacity(K, nd) == cap);
+  CHECK(pq::bound_capacity(nd) == (size_t)PAYNE_MAX_ELL * (2 * nd * nd + nd));
+  CHECK(L.u() == 0 && L.v() == hv && L.lnprob() == hl && L.counters() == hl + K && L.counters() == nq_d && L.n_counters() == n_cnt);
+  CHECK(L.axes() == hax && L.n_axes() == n_ax && L.n_bound() == n_ax + n_as);
+  CHECK(L.n_down() == nq_d + n_cnt && L.n_up() == nq_d + n_cnt + n_ax + n_as && L.dyn_pair() == nq_d + n_cnt);
+  std::vector<double> blk(cap);
+  double* b = blk.data();
+  const pq::View w = L.view(b);
+  CHECK(w.u == b && w.v == b + hv && w.lnprob == b + hl && w.axes == b + hax);
+  CHECK(w.nacc == reinterpret_cast<int*>(b + hl + K) && w.ncall == w.nacc + K && w.nredraw == w.ncall + K);
+  if (n_ell > 1) {
+    CHECK(L.ctr() == hax + n_ax && L.ainv() == hax + n_ax + n_ell * nd && L.ell() == hax + n_ax + n_as);
+    CHECK(w.ctr == b + hax + n_ax && w.ainv == b + hax + n_ax + n_ell * nd && w.ell == reinterpret_cast<int*>(b + hax + n_ax + n_as));
+  } else {
+    CHECK(!w.ctr && !w.ainv && !w.ell);
+  }
+  // in order, inside the capacity, aligned (offsets in bytes from an 8-aligned base)
+  auto off = [&](const void* p) { return (size_t)(static_cast<const char*>(p) - reinterpret_cast<const char*>(b)); };
+  std::vector<Region> R = {{off(w.u), K * nd * 8, 8}, {off(w.v), K * nd * 8, 8}, {off(w.lnprob), K * 8, 8}, {off(w.nacc), K * 4, 4},
+                           {off(w.ncall), K * 4, 4}, {off(w.nredraw), K * 4, 4}, {off(w.axes), n_ax * 8, 8}};
+  if (n_ell > 1) { R.push_back({off(w.ctr), n_ell * nd * 8, 8}); R.push_back({off(w.ainv), n_ax * 8, 8}); R.push_back({off(w.ell), K * 4, 4}); }
+  size_t end = 0;
+  for (const Region& r : R) { CHECK(r.lo >= end); CHECK(r.lo % r.align == 0); end = r.lo + r.n; }
+  CHECK(end <= cap * 8 && end <= L.end() * 8 && L.end() <= cap);
+  CHECK(off(w.nredraw) + K * 4 <= L.n_down() * 8);                       // the counters come down with the chains
+  CHECK(off(w.axes) + L.n_bound() * 8 == L.n_up() * 8);                  // the bound goes up behind them
+  // the words behind the block, on a host copy sized for k_max chains
+  for (size_t k_max : {K, (size_t)64}) {
+    const size_t capm = k_max * (2 * nd + 1) + (3 * k_max + 1) / 2 + (size_t)PAYNE_MAX_ELL * (2 * nd * nd + nd) + (k_max + 1) / 2;
+    const pq::HostBlock q = pq::q_host_block(k_max, nd), dq = pq::dq_host_block(k_max, nd);
+    CHECK(q.doubles == capm + 8 && q.flag == capm && dq.doubles == capm + 16 && dq.flag == capm + 8);
+    CHECK(q.flag >= L.n_up() && q.flag >= L.end() && q.flag + 1 <= q.doubles);
+    CHECK(L.dyn_pair() >= L.n_down() && L.dyn_pair() + 2 <= dq.flag && dq.flag + 1 <= dq.doubles);
+  }
+  // pack_bound: the three arrays where the kernels are told to find them
+  std::vector<double> ax(n_ax), ct(n_ell * nd), ai(n_ax);
+  for (auto& x : ax) x = rnd();
+  for (auto& x : ct) x = rnd();
+  for (auto& x : ai) x = rnd();
+  pq::pack_bound(L, w.axes, ax.data(), n_ell > 1 ? ct.data() : nullptr, n_ell > 1 ? ai.data() : nullptr);
+  CHECK(!std::memcmp(b + hax, ax.data(), n_ax * 8));
+  if (n_ell > 1) CHECK(!std::memcmp(b + hax + n_ax, ct.data(), n_ell * nd * 8) && !std::memcmp(b + hax + n_ax + n_ell * nd, ai.data(), n_ax * 8));
+}
+
+static void round_trip(int K, int nd) {
+  const pq::Layout L(K, nd, 1);
+  std::vector<double> blk(L.n_down());                              // exactly what comes down: a read past it is an error
+  for (auto& x : blk) x = rnd();
+  const pq::View w = L.view(blk.data());
+  int first = -1, last = -1;
+  for (int k = 0; k < K; ++k) {
+    w.nacc[k] = (k % 3 == 1) ? 0 : 1 + k % 4; w.ncall[k] = 3 + k; w.nredraw[k] = k % 5;
+    if (w.nacc[k] > 0) { if (first < 0) first = k; last = k; }
+  }
+  w.lnprob[first] = std::nan("");
+  w.ncall[last] = 0;
+  std::vector<double> eu, ev, el; std::vector<int> enc;
+  long long acc = 0, calls = 0, redraw = 0, idle = 0;
+  for (int k = 0; k < K; ++k) {
+    acc += w.nacc[k]; calls += w.ncall[k]; redraw += w.nredraw[k];
+    if (w.nacc[k] == 0) { idle += w.ncall[k]; continue; }
+    eu.insert(eu.end(), blk.begin() + (size_t)k * nd, blk.begin() + (size_t)(k + 1) * nd);
+    ev.insert(ev.end(), blk.begin() + (size_t)(K + k) * nd, blk.begin() + (size_t)(K + k + 1) * nd);
+    el.push_back(k == first ? -INFINITY : blk[(size_t)2 * K * nd + k]);
+    enc.push_back(k == last ? 1 : 3 + k);
+  }
+  const size_t m = el.size();
+  std::vector<double> qu(m * nd), qv(m * nd), ql(m); std::vector<int> qnc(m);
+  int nq = -1; long long st[4] = {-1, -1, -1, -1};
+  pq::queue_extract(blk.data(), K, nd, qu.data(), qv.data(), ql.data(), qnc.data(), &nq, st);
+  CHECK(nq == (int)m && qu == eu && qv == ev && ql == el && qnc == enc);
+  for (int q : qnc) CHECK(q >= 1);
+  CHECK(st[0] == acc && st[1] == calls && st[2] == redraw && st[3] == idle);
+}
+
+static void starts(int K, int nd, bool with_src) {
+  const int nlive = 37, nq = 11;
+  const unsigned long long seed = 0x1234567ull * (K + 3) + nd;
+  const pq::Layout L(K, nd, 1);
+  std::vector<double> blk(L.n_down(), -7.0), lu(nlive * nd), lv(nlive * nd), ll(nlive), qu(nq * nd), qv(nq * nd), lg(nlive);
+  for (auto* a : {&lu, &lv, &ll, &qu, &qv, &lg}) for (auto& x : *a) x = rnd();
+  std::vector<int> src(nlive);
+  for (int i = 0; i < nlive; ++i) src[i] = (i % 3 == 0) ? (i * 7) % nq : -1;
+  pq::fill_starts(L, blk.data(), seed, nlive, lu.data(), lv.data(), ll.data(), with_src ? src.data() : nullptr, qu.data(), qv.data(), lg.data());
+  for (int k = 0; k < K; ++k) {
+    const int i = (int)(mix_ref(seed ^ (0xA5A5A5A5ull + (unsigned long long)k * 0x100000001B3ull)) % (unsigned long long)nlive);
+    const bool q = with_src && src[i] >= 0;
+    for (int d = 0; d < nd; ++d) {
+      CHECK(blk[(size_t)k * nd + d] == (q ? qu[(size_t)src[i] * nd + d] : lu[(size_t)i * nd + d]));
+      CHECK(blk[(size_t)(K + k) * nd + d] == (q ? qv[(size_t)src[i] * nd + d] : lv[(size_t)i * nd + d]));
+    }
+    CHECK(blk[(size_t)2 * K * nd + k] == (with_src ? lg[i] : ll[i]));
+  }
+  for (size_t j = L.counters(); j < L.n_down(); ++j) CHECK(blk[j] == -7.0);     // nothing behind the chains is touched
+}
+
+int main() {
+  srand(7);
+  for (int K : {1, 2, 3, 64})
+    for (int nd : {1, 3, PAYNE_MAX_DIM}) {
+      for (int n_ell : {1, 2, PAYNE_MAX_ELL}) layout(K, nd, n_ell);
+      round_trip(K, nd);
+      starts(K, nd, false);
+      starts(K, nd, true);
+    }
+  const int ell[4] = {0, 1, 2, 1};
+  CHECK(!pq::check_ell_list(1, false) && !pq::check_ell_list(PAYNE_MAX_ELL, true) && !pq::check_ell_list(3, true, ell, 4));
+  for (int n : {0, -1, PAYNE_MAX_ELL + 1}) CHECK(std::string(pq::check_ell_list(n, true)) == "bad ellipsoid list");
+  CHECK(std::string(pq::check_ell_list(2, false)) == "bad ellipsoid list");
+  CHECK(std::string(pq::check_ell_list(2, true, ell, 4)) == "ellipsoid index out of range");
+  const int neg[1] = {-1};
+  CHECK(std::string(pq::check_ell_list(1, true, neg, 1)) == "ellipsoid index out of range");
+  for (int nd : {1, 3, PAYNE_MAX_DIM}) {
+    const long long st[5][4] = {{0, 0, 0, 0}, {10, 20, 0, 0}, {30, 25, 5, 3}, {0, 1000, 0, 0}, {1000, 1000, 0, 0}};
+    for (const auto& s4 : st)
+      for (double sc : {1e-4, 0.7, 4.0}) {
+        const double frac = (double)s4[0] / (double)(s4[1] + s4[2] > 1 ? s4[1] + s4[2] : 1);
+        const double want = std::fmin(std::fmax(sc * exp((frac - 0.5) / nd / 0.5), 1e-4), 4.0);
+        CHECK(pq::adapt_scale(sc, s4, nd) == want);
+      }
+  }
+  std::printf("bad=%d\n", bad);
+  return bad != 0;
+}''')
+    exe = tmp_path / "qb_san"
+    subprocess.run(["g++", "-O1", "-g", "-std=c++17", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-I", root,
+                    "-I", os.path.join(root, "include"), str(main), "-o", str(exe)], check=True)
+    res = subprocess.run([str(exe)], capture_output=True, text=True)
+    assert res.returncode == 0 and "bad=0" in res.stdout, (res.stdout[-2000:], res.stderr[-2000:])
+
+
 def test_fitpayne_bulk_rows_equal_single_rows(tmp_path):
     import io
     from thepayne_amd.fitting.fitstar import FitPayne

@@ -129,6 +129,21 @@ def test_grouping_of_rounds_does_not_matter(prob):
     got = p.prop.slice_finish()
     assert i > 3
     assert all(np.array_equal(a, b) for a, b in zip(got, base[:6]))
+    # ... nor does what was walked before: the random walk and the slice walk stage their chains through ONE set of buffers, and
+    # rwalk, slice_walk, rwalk on one proposer give, array for array, what each call gives on a fresh proposer
+    from thepayne_amd.sampler.device import DeviceProposer
+    calls = (lambda q: q.rwalk(p.U0, p.V0, p.lp0, p.axes, 1.0, p.lstar, 4, 101),
+             lambda q: q.slice_walk(p.U0, p.V0, p.lp0, p.axes, 1.0, p.lstar, 2, False, 102),
+             lambda q: q.rwalk(p.U0, p.V0, p.lp0, p.axes, 0.7, p.lstar, 4, 103))
+    mixed = [f(p.prop) for f in calls]
+    for f, got in zip(calls, mixed):
+        fresh = DeviceProposer(p.L, p.P, k_max=K)
+        try:
+            want = f(fresh)
+        finally:
+            fresh.close()
+        assert len(got) == len(want) and all(np.array_equal(a, b) for a, b in zip(got, want))
+        assert np.any(got[0] != p.U0)
 
 
 def test_caps(prob):

@@ -30,6 +30,7 @@
 #include "host_tables.hpp"
 #include "post_seq.hpp"
 #include "ns_core.hpp"
+#include "queue_block.hpp"
 
 using namespace payne;
 
@@ -223,6 +224,17 @@ static int dev_alloc(payne_ctx* c, size_t n, V** out, std::vector<void*>& bag, b
 static int fail(payne_ctx* c, int code, const std::string& msg) {
   if (c) c->err = msg; else g_create_error = msg;
   return code;
+}
+
+// the calls of an entry point go to the context's device (a failing hipSetDevice: the device has already failed)
+static int on_device(payne_ctx* c) {
+  int dev = 0;
+  (void)hipGetDevice(&dev);
+  if (dev != c->device) {
+    hipError_t e = hipSetDevice(c->device);
+    if (e != hipSuccess) return fail(c, PAYNE_E_HIP, std::string("hipSetDevice: ") + hipGetErrorString(e));
+  }
+  return PAYNE_OK;
 }
 
 // A context being reconfigured: on its own device, with nothing in flight (no kernel may still read what is about to be freed or
@@ -1241,13 +1253,7 @@ static int check_call(payne_ctx* c, const void* in, int B, const void* out) {
   if (!in || !out) return fail(c, PAYNE_E_INVALID, "NULL input/output pointer");
   if (B <= 0) return fail(c, PAYNE_E_INVALID, "B must be > 0");
   if (B > c->opts.b_max) return fail(c, PAYNE_E_BATCH, "B exceeds opts.b_max");
-  int dev = 0;
-  (void)hipGetDevice(&dev);
-  if (dev != c->device) {
-    hipError_t e = hipSetDevice(c->device);
-    if (e != hipSuccess) return fail(c, PAYNE_E_HIP, std::string("hipSetDevice: ") + hipGetErrorString(e));
-  }
-  return PAYNE_OK;
+  return on_device(c);
 }
 
 static int run_sed(payne_ctx* c, const double* in, int ld, int mode, int B, double* mags, hipStream_t s) {
@@ -1458,6 +1464,7 @@ struct payne_sampler {
   bool turn_lds_ok = false;  // this device lets payne_ns_turn_kernel have kTurnRowsLdsMax bytes of dynamic LDS (asked in payne_ns_queue_dev_init)
   double* dyn = nullptr;                  // device: {scale, loglstar}
   double* dq_host[2] = {nullptr, nullptr}; double* dq_host_dev[2] = {nullptr, nullptr};      // two mapped result blocks (+ flag word each)
+  volatile unsigned long long* dq_flag[2] = {nullptr, nullptr}; unsigned long long* dq_flag_dev[2] = {nullptr, nullptr};
   unsigned long long dq_seq[2] = {0, 0};
   double* dax_host[2] = {nullptr, nullptr}; double* dax_host_dev[2] = {nullptr, nullptr};    // two mapped blocks for the bound
   int dq_launched = 0, dq_collected = 0, dq_exported = 0, dq_K = 0, dq_n_ell = 0, dax_n = 0;   // (exported: queues whose results' transfer is enqueued)
@@ -1479,10 +1486,9 @@ struct payne_sampler {
   long long n_slice = 0;                  // slice rounds (launches of their own)
 };
 
-// doubles of the queue's staging block (device and pinned host): chains (u | v | lnprob) and the walk's three counters (what
-// comes back, in ONE transfer), then the ellipsoids' axes, centres and inverse axes (they travel up with the chains in one
-// transfer; the counters' slots go along unused), then (device only) the chains' ellipsoid indices
-static size_t q_doubles(size_t K, size_t nd) { return K * (2 * nd + 1) + (3 * K + 1) / 2 + (size_t)PAYNE_MAX_ELL * (2 * nd * nd + nd) + (K + 1) / 2; }
+// (the queue's staging block -- q_dev, q_host, dq_host --: its regions, sizes and the words behind it are queue_block.hpp's)
+namespace pq = payne_queue;
+static int adv_on(const SamplerDev& sd) { return (sd.adv.imf || sd.adv.vrot || sd.adv.plx_dim >= 0) ? 1 : 0; }
 
 extern "C" void payne_sampler_destroy(payne_sampler* s) {
   if (!s) return;
@@ -1516,9 +1522,8 @@ extern "C" int payne_sampler_create(payne_ctx* c, const payne_sampler_desc* d, i
     if (a.dim_logg >= d->ndim || a.dim_logr >= d->ndim || a.dim_vrot >= d->ndim || a.plx_dim >= d->ndim)
       return fail(c, PAYNE_E_INVALID, "adv.dim_* out of range");
   }
-  int dev = 0;
-  (void)hipGetDevice(&dev);
-  if (dev != c->device) (void)hipSetDevice(c->device);
+  int rc = on_device(c);
+  if (rc) return rc;
   payne_sampler* s = new payne_sampler();
   s->ctx = c; s->k_max = k_max;
   s->sd.ndim = d->ndim; s->sd.ncols = c->ncols; s->sd.nfixed = d->n_fixed;
@@ -1536,12 +1541,11 @@ extern "C" int payne_sampler_create(payne_ctx* c, const payne_sampler_desc* d, i
     return PAYNE_OK;
   };
   const size_t K = (size_t)k_max, nd = (size_t)d->ndim;
-  int rc;
   if ((rc = alloc(K * nd * 8, (void**)&s->u_prop)) || (rc = alloc(K * nd * 8, (void**)&s->v_prop)) ||
       (rc = alloc(K * 8, (void**)&s->lnprior)) || (rc = alloc(K * 8, (void**)&s->lnl)) ||
       (rc = alloc(K * c->ncols * 8, (void**)&s->rows)) || (rc = alloc((size_t)PAYNE_MAX_ELL * nd * nd * 8, (void**)&s->axes)) ||
       (rc = alloc(K * 4, (void**)&s->inside)) || (rc = alloc(K * 4, (void**)&s->ell)) || (rc = alloc(K * 4, (void**)&s->nredraw)) ||
-      (rc = alloc(std::max<size_t>(q_doubles(K, nd), 2 * PAYNE_MAX_DIM) * 8, (void**)&s->q_dev)) ||
+      (rc = alloc(std::max<size_t>(pq::capacity(K, nd), 2 * PAYNE_MAX_DIM) * 8, (void**)&s->q_dev)) ||
       (rc = alloc(sizeof(WalkTail), (void**)&s->tail_dev)) ||
       (rc = alloc(3 * K * nd * 8, (void**)&s->sl_win)) || (rc = alloc((4 * K + 1) * 4, (void**)&s->sl_int)) ||
       (spec_fits(d->ndim, c->ncols) && (rc = alloc(K * 2 * kSpecStride * 8, (void**)&s->spec)))) {
@@ -1575,7 +1579,8 @@ extern "C" int payne_sampler_create(payne_ctx* c, const payne_sampler_desc* d, i
     return fail(c, PAYNE_E_HIP, "upload of the sampler descriptor");
   }
   (void)hipMemset(s->inside, 0, K * 4);
-  if (hipHostMalloc((void**)&s->q_host, (q_doubles(K, nd) + 8) * 8, hipHostMallocMapped) != hipSuccess ||
+  const pq::HostBlock qh = pq::q_host_block(K, nd);
+  if (hipHostMalloc((void**)&s->q_host, qh.doubles * 8, hipHostMallocMapped) != hipSuccess ||
       hipHostMalloc((void**)&s->sl_active_host, 8, hipHostMallocDefault) != hipSuccess) {
     payne_sampler_destroy(s);
     return fail(c, PAYNE_E_HIP, "hipHostMalloc(sampler staging)");
@@ -1584,8 +1589,8 @@ extern "C" int payne_sampler_create(payne_ctx* c, const payne_sampler_desc* d, i
     void* dp = nullptr;
     if (hipHostGetDevicePointer(&dp, s->q_host, 0) == hipSuccess && dp) {
       s->q_host_dev = static_cast<double*>(dp);
-      s->q_flag = reinterpret_cast<volatile unsigned long long*>(s->q_host + q_doubles(K, nd));
-      s->q_flag_dev = reinterpret_cast<unsigned long long*>(s->q_host_dev + q_doubles(K, nd));
+      s->q_flag = reinterpret_cast<volatile unsigned long long*>(s->q_host + qh.flag);
+      s->q_flag_dev = reinterpret_cast<unsigned long long*>(s->q_host_dev + qh.flag);
       *s->q_flag = 0ull;
       void* ap = nullptr;
       if (hipMalloc(&ap, 8) == hipSuccess && hipMemset(ap, 0, 8) == hipSuccess) { s->owned.push_back(ap); s->q_arrivals = static_cast<unsigned*>(ap); }
@@ -1600,10 +1605,7 @@ static int sampler_check(payne_sampler* s, const void* a, int K, const void* b) 
   payne_ctx* c = s->ctx;
   if (!a || !b) return fail(c, PAYNE_E_INVALID, "NULL input/output pointer");
   if (K <= 0 || K > s->k_max) return fail(c, PAYNE_E_BATCH, "K exceeds the sampler's k_max");
-  int dev = 0;
-  (void)hipGetDevice(&dev);
-  if (dev != c->device) (void)hipSetDevice(c->device);
-  return PAYNE_OK;
+  return on_device(c);
 }
 
 extern "C" int payne_prior_transform_batch(payne_sampler* s, const double* u, int K, double* v, void* stream) {
@@ -1639,7 +1641,7 @@ static void rwalk_begin_impl(payne_sampler* s, double* u, double* v, double* lnp
   s->run = {u, v, lnprob, K, walks, scale, loglstar, seed, nacc, ncall, stream, true, ell_dev != nullptr, nredraw};
   s->walk = WalkState{u, v, lnprob, nacc, ncall, s->u_prop, s->v_prop, s->lnprior, s->inside, s->rows, axes_dev,
                       ell_dev, nredraw, scale, loglstar, seed, K,
-                      s->sd.ndim, s->sd.ncols, (s->sd.adv.imf || s->sd.adv.vrot || s->sd.adv.plx_dim >= 0) ? 1 : 0, s->spec,
+                      s->sd.ndim, s->sd.ncols, adv_on(s->sd), s->spec,
                       nullptr, nullptr, nullptr, 0, nullptr};
   s->tail_done = false;
 }
@@ -1650,10 +1652,7 @@ extern "C" int payne_rwalk_begin_ell(payne_sampler* s, double* u, double* v, dou
   if (rc) return rc;
   if (!lnprob || !axes || !nacc || !ncall || walks <= 0) return fail(s->ctx, PAYNE_E_INVALID, "bad rwalk arguments");
   if (s->srun.open) return fail(s->ctx, PAYNE_E_INVALID, "a slice walk is open on this sampler");
-  if (n_ell < 1 || n_ell > PAYNE_MAX_ELL || (n_ell > 1 && !ell)) return fail(s->ctx, PAYNE_E_INVALID, "bad ellipsoid list");
-  if (ell)
-    for (int i = 0; i < K; ++i)
-      if (ell[i] < 0 || ell[i] >= n_ell) return fail(s->ctx, PAYNE_E_INVALID, "ellipsoid index out of range");
+  if (const char* bad = pq::check_ell_list(n_ell, ell != nullptr, ell, K)) return fail(s->ctx, PAYNE_E_INVALID, bad);
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   const int nd = s->sd.ndim;
   HIPCHK(s->ctx, hipMemcpyAsync(s->axes, axes, (size_t)n_ell * nd * nd * 8, hipMemcpyHostToDevice, st));
@@ -1691,6 +1690,11 @@ extern "C" int payne_rwalk_step(payne_sampler* s, int w) {
   if (e != hipSuccess) return fail(s->ctx, PAYNE_E_HIP, std::string("rwalk launch: ") + hipGetErrorString(e));
   return rc;
 }
+static int rwalk_steps(payne_sampler* s, int walks) {
+  int rc = PAYNE_OK;
+  for (int w = 0; !rc && w <= walks; ++w) rc = payne_rwalk_step(s, w);
+  return rc;
+}
 extern "C" int payne_sampler_counters(const payne_sampler* s, long long out[2]) {
   if (!s || !out) return PAYNE_E_INVALID;
   out[0] = s->n_tail; out[1] = s->n_own + s->n_slice;
@@ -1699,9 +1703,8 @@ extern "C" int payne_sampler_counters(const payne_sampler* s, long long out[2]) 
 extern "C" int payne_rwalk_batch(payne_sampler* s, double* u, double* v, double* lnprob, int K, const double* axes,
                                  double scale, double loglstar, int walks, unsigned long long seed, int* nacc, int* ncall,
                                  void* stream) {
-  int rc = payne_rwalk_begin(s, u, v, lnprob, K, axes, scale, loglstar, walks, seed, nacc, ncall, stream);
-  for (int w = 0; !rc && w <= walks; ++w) rc = payne_rwalk_step(s, w);
-  return rc;
+  const int rc = payne_rwalk_begin(s, u, v, lnprob, K, axes, scale, loglstar, walks, seed, nacc, ncall, stream);
+  return rc ? rc : rwalk_steps(s, walks);
 }
 
 // Slice sampling as lock-step chains on the device (header: payne_slice_begin).  A round is payne_slice_kernel -- settle the value
@@ -1715,10 +1718,7 @@ extern "C" int payne_slice_begin(payne_sampler* s, double* u, double* v, double*
   payne_ctx* c = s->ctx;
   if (!lnprob || !axes || !ncall || !nexpand || !ncontract) return fail(c, PAYNE_E_INVALID, "bad slice arguments");
   if (slices <= 0) return fail(c, PAYNE_E_INVALID, "slices must be > 0");
-  if (n_ell < 1 || n_ell > PAYNE_MAX_ELL || (n_ell > 1 && !ell)) return fail(c, PAYNE_E_INVALID, "bad ellipsoid list");
-  if (ell)
-    for (int i = 0; i < K; ++i)
-      if (ell[i] < 0 || ell[i] >= n_ell) return fail(c, PAYNE_E_INVALID, "ellipsoid index out of range");
+  if (const char* bad = pq::check_ell_list(n_ell, ell != nullptr, ell, K)) return fail(c, PAYNE_E_INVALID, bad);
   if (s->run.open || s->queue_open || s->dq_launched != s->dq_collected)
     return fail(c, PAYNE_E_INVALID, "a random walk is open on this sampler");
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
@@ -1730,7 +1730,7 @@ extern "C" int payne_slice_begin(payne_sampler* s, double* u, double* v, double*
                         s->sl_int, s->sl_int + km, s->sl_int + 2 * km, s->sl_int + 3 * km, ncall, nexpand, ncontract,
                         s->u_prop, s->v_prop, s->lnprior, s->inside, s->rows, s->axes, ell ? s->ell : (const int*)nullptr,
                         s->sl_int + 4 * km, scale, loglstar, seed, K, nd, s->sd.ncols,
-                        (s->sd.adv.imf || s->sd.adv.vrot || s->sd.adv.plx_dim >= 0) ? 1 : 0,
+                        adv_on(s->sd),
                         random_dirs ? slices : slices * nd, random_dirs ? 1 : 0};
   s->srun = {true, false, true, stream};
   return PAYNE_OK;
@@ -1740,13 +1740,11 @@ extern "C" int payne_slice_rounds(payne_sampler* s, int n, int* n_active) {
   payne_ctx* c = s->ctx;
   if (!s->srun.open) return fail(c, PAYNE_E_INVALID, "payne_slice_rounds outside a walk");
   if (n <= 0 || !n_active) return fail(c, PAYNE_E_INVALID, "bad payne_slice_rounds arguments");
-  int dev = 0;
-  (void)hipGetDevice(&dev);
-  if (dev != c->device) (void)hipSetDevice(c->device);
+  int rc = on_device(c);
+  if (rc) return rc;
   hipStream_t st = reinterpret_cast<hipStream_t>(s->srun.stream);
   const int K = s->slice.K;
   const dim3 grid((K + 3) / 4), block(256);                     // one wave per chain
-  int rc = PAYNE_OK;
   for (int r = 0; r < n && !rc; ++r) {
     hipLaunchKernelGGL(payne_slice_kernel, grid, block, 0, st, s->sd, s->slice, s->lnl, s->srun.pending ? 1 : 0, 1, s->srun.first ? 1 : 0);
     s->srun.pending = true; s->srun.first = false;
@@ -1783,6 +1781,16 @@ extern "C" int payne_slice_batch(payne_sampler* s, double* u, double* v, double*
   return rc;
 }
 
+// The walk opened on the queue's device block as L lays it out, and its walks + 1 steps enqueued (dyn: the {scale, loglstar} the
+// turn kernel left on the device, or null: the ones given here)
+static int queue_walk(payne_sampler* s, const pq::Layout& L, double scale, double loglstar, int walks, unsigned long long seed,
+                      const double* dyn, void* stream) {
+  const pq::View q = L.view(s->q_dev);                      // (q.ell: device only, written by the first step)
+  rwalk_begin_impl(s, q.u, q.v, q.lnprob, (int)L.K, q.axes, q.ell, scale, loglstar, walks, seed, q.nacc, q.ncall, q.nredraw, stream);
+  s->walk.dyn = dyn;
+  if (L.n_ell > 1) { s->walk.as_ctr = q.ctr; s->walk.as_ainv = q.ainv; s->walk.ell_out = q.ell; s->walk.n_ell = (int)L.n_ell; }
+  return rwalk_steps(s, walks);
+}
 // The random-walk queue of the batched nested sampler in one call: start points, ellipsoid assignment, upload, the walk,
 // download, and the chains that moved as the proposal queue (header: payne_ns_rwalk_queue).
 // In two parts, so that the caller's host work (the next bound, bookkeeping of another fit) can run while the GPU walks:
@@ -1790,319 +1798,6 @@ extern "C" int payne_slice_batch(payne_sampler* s, double* u, double* v, double*
 // _end waits for the stream and selects the chains that moved.  payne_ns_rwalk_queue is the two back to back.
 // `src` (payne_ns_rwalk_queue_turn): live slot i holds row src[i] of (qu, qv) with lnprob lg[i] when src[i] >= 0 -- the live set a
 // queue's consumption will leave, by index (payne_ns::peek_index), never copied
-// The queue's staging block up (from mapped host memory) and down (into it; ONE workgroup, which then publishes the queue's
-// sequence number behind the block with system scope -- what payne_ns_rwalk_queue_end waits for).
-__global__ void __launch_bounds__(256) payne_stage_in_kernel(double* __restrict__ dst, const double* __restrict__ src_host, size_t n) {
-  for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (size_t)gridDim.x * 256) dst[i] = src_host[i];
-}
-__global__ void __launch_bounds__(1024) payne_stage_out_kernel(double* __restrict__ dst_host, const double* __restrict__ src, size_t n,
-                                                               unsigned long long* flag, unsigned long long seq,
-                                                               const double* __restrict__ src2 = nullptr, int n2 = 0,
-                                                               unsigned* arrivals = nullptr) {
-  // (several workgroups when `arrivals` is given: the last one to arrive publishes -- atomicInc wraps the count back to zero)
-  for (size_t i = (size_t)blockIdx.x * 1024 + threadIdx.x; i < n; i += (size_t)gridDim.x * 1024) dst_host[i] = src[i];
-  if (blockIdx.x == 0 && src2 && (int)threadIdx.x < n2) dst_host[n + threadIdx.x] = src2[threadIdx.x];   // (the device's scale and threshold behind the block)
-  // (every wave's stores are acknowledged before it passes the barrier; ONE thread's release then covers the workgroup's -- release
-  // fences are cumulative --: a fence in each of the sixteen waves, each a write-back of the L2, was 6 us in the turn kernel)
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    bool last = true;
-    if (arrivals && gridDim.x > 1) { __threadfence_system(); last = atomicInc(arrivals, gridDim.x - 1) == gridDim.x - 1; }
-    if (last) { __threadfence_system(); __hip_atomic_store(flag, seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM); }
-  }
-}
-
-// ---- the queue's turn on the device ------------------------------------------------------------------------------------
-// What payne_ns_rwalk_queue_turn does on the host between two queues, as ONE workgroup: the chains that moved are the proposals;
-// consuming them in order (each replaces the worst live point if it beats it) leaves the nlive LARGEST of live points and proposals
-// -- thresholds only rise, so a proposal in that set beat every threshold it met, and one outside it died or never got in --: a sort
-// by (lnprob descending, live points before proposals on ties: the test is strict).  Then the scale adaptation dynesty-style from
-// the queue's counters, the new threshold (the largest lnprob left outside the set: the last point to die), and every chain's start point, uniform among the new live
-// points (the host's splitmix of the seed).  The host replays the same queue for the evidence in its own time; its live SET is the
-// same, its slot order is not (nothing on the device depends on it).
-// sum of an int over the wave, in lane 63 (an inclusive scan inside each row of 16 lanes, then the rows' totals handed on)
-template <int CTRL> __device__ __forceinline__ int turn_dpp_add(int x) { return x + __builtin_amdgcn_update_dpp(0, x, CTRL, 0xf, 0xf, true); }
-__device__ __forceinline__ int turn_wave_sum_to_last(int x) {
-  x = turn_dpp_add<0x111>(x); x = turn_dpp_add<0x112>(x); x = turn_dpp_add<0x114>(x); x = turn_dpp_add<0x118>(x);   // row_shr 1, 2, 4, 8
-  x = turn_dpp_add<0x142>(x); x = turn_dpp_add<0x143>(x);                                                            // row_bcast 15, 31
-  return x;
-}
-// (the network's exchanges at distances below 64: lane_xor_i32, sampler_core.hpp)
-// one stage of the bitonic network at distance J < 64 inside runs of KK, "before" = larger lnprob, then smaller id
-template <int KK, int J>
-__device__ __forceinline__ void turn_cmpx(double& kv, int& iv, int i) {
-  union { double d; int w[2]; } me, pa;
-  me.d = kv;
-  const bool upper = (i & J) != 0;
-  pa.w[0] = lane_xor_i32<J>(me.w[0], upper); pa.w[1] = lane_xor_i32<J>(me.w[1], upper);
-  const int ip = lane_xor_i32<J>(iv, upper);
-  const bool mine_first = (kv > pa.d) || (kv == pa.d && iv < ip);
-  const bool want_first = (!upper) == ((i & KK) == 0);                       // the lower place of an ascending run, the upper of a descending one
-  if (mine_first != want_first) { kv = pa.d; iv = ip; }
-  if constexpr (J > 1) turn_cmpx<KK, J / 2>(kv, iv, i);
-}
-struct TurnArgs {
-  const double *lu, *lv, *ll; double *ou, *ov, *ol;    // live set in / out (the same arrays when merge == 0)
-  int nlive, nd, K, merge, n2;                         // n2: power of two >= nlive + K (<= 2048)
-  double *cu, *cv, *cl; int *na, *nc, *nr;             // chains: the finished queue's results in, the next queue's start points out
-  double* dyn;                                         // {scale, loglstar}
-  double scale0, lstar0;                               // merge == 0: what to start from
-  unsigned long long seed;
-  // the finished queue's results on their way to the host from HERE (its own transfer kernel was 9 us between two queues): the
-  // stores are issued first and drain under the sort; the completion word follows the kernel's last statement
-  double* exp_dst; int exp_n; unsigned long long* exp_flag; unsigned long long exp_seq;
-  const double* ax_src; double* ax_dst; int ax_n;      // a new bound (axes, centres, inverse axes) from its mapped host block: a launch of its own was 2.8 us in front of this one
-  int live_sorted;                                     // the live set comes from a merging turn: best first (rows and lnprob)
-  int rows_lds;                                        // the launch carries nlive * nd * 16 bytes of dynamic LDS: the new live set's rows stay there for the start points
-};
-constexpr size_t kTurnRowsLdsMax = 128 * 1024;
-__global__ void __launch_bounds__(1024) payne_ns_turn_kernel(TurnArgs a) {
-  __shared__ double key[2048];
-  __shared__ int id[2048];
-  __shared__ int wsum[3][16];
-  __shared__ int got_in_flag;
-  extern __shared__ __attribute__((aligned(16))) double turn_rows[];   // [2][nlive * nd] when a.rows_lds
-  const int tid = threadIdx.x, nl = a.nlive, nd = a.nd, K = a.K;
-  // With the new rows in LDS nothing below the sort reads what this kernel stored to global memory: the barriers there need not wait
-  // for the stores to be acknowledged (1.5 us each time) -- the one in front of the completion word does.
-  const bool lds_rows = a.merge && a.rows_lds;
-  auto lds_barrier = []() {                                  // (__syncthreads also waits for the stores towards the host to be acknowledged)
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup", "local"); __builtin_amdgcn_s_barrier(); __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup", "local");
-  };
-  auto turn_barrier = [&]() {
-    if (lds_rows) { __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup", "local"); __builtin_amdgcn_s_barrier(); __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup", "local"); }
-    else __syncthreads();
-  };
-  double scale = a.scale0, lstar = a.lstar0;
-  // Everything the kernel reads before the sort is REQUESTED first, in one go: the keys (a counter and the lnprob it admits), the
-  // counters, the scale and threshold, the export's values (sixteen to a thread).  One value at a time -- a load, its store towards
-  // the host, the next load: the two may alias -- the export alone was 13 memory latencies end to end (3.3 us), the keys (the counter,
-  // THEN the lnprob) and the counters three more.  The export's stores go out right in front of the sort, whose exchanges and
-  // comparisons leave the memory path to them.
-  // (Every one of these loads is unconditional, its index clamped: a load under a branch leaves the compiler without a count of the
-  // loads behind it, and it waits for ALL of them -- the bound's values included, 2 us away across the bus -- in front of the sort.)
-  double l_in[2]; int na_in[2];
-  int s0 = 0, s1 = 0, s2 = 0;
-#pragma unroll
-  for (int q = 0; q < 2; ++q) {                               // (n2 <= 2048; read whether or not this turn merges: one basic block, loads in source order)
-    const int e = tid + q * 1024;
-    const bool is_live = e < nl;
-    const int k = (!is_live && e < nl + K) ? e - nl : 0;
-    const double* lp = is_live ? a.ll + e : a.cl + k;
-    l_in[q] = *lp;
-    na_in[q] = a.na[k];
-  }
-  const int kc = tid < K ? tid : K - 1;
-  const int cnt0 = a.na[kc], cnt1 = a.nc[kc], cnt2 = a.nr[kc];
-  const double dyn0 = a.dyn[0], dyn1 = a.dyn[1];
-  constexpr int kExpBatch = 16;
-  double ex[kExpBatch];
-  if (a.exp_dst) {
-#pragma unroll
-    for (int q = 0; q < kExpBatch; ++q) { const int e = tid + q * 1024; ex[q] = e < a.exp_n ? a.cu[e] : 0.0; }
-  }
-#pragma unroll
-  for (int q = 0; q < 2; ++q) if (tid + q * 1024 < nl) na_in[q] = 1;
-  if (tid < K) { s0 = cnt0; s1 = cnt1; s2 = cnt2; }
-  if (a.merge) for (int k = tid + 1024; k < K; k += 1024) { s0 += a.na[k]; s1 += a.nc[k]; s2 += a.nr[k]; }
-  auto export_out = [&]() {                                  // chains | counters (contiguous from a.cu), then the scale and threshold they ran under
-    if (!a.exp_dst) return;
-#pragma unroll
-    for (int q = 0; q < kExpBatch; ++q) { const int e = tid + q * 1024; if (e < a.exp_n) a.exp_dst[e] = ex[q]; }
-    for (int e = tid + kExpBatch * 1024; e < a.exp_n; e += 1024) a.exp_dst[e] = a.cu[e];
-    if (tid < 2) a.exp_dst[a.exp_n + tid] = tid ? dyn1 : dyn0;
-  };
-  if (a.merge) {
-    // the queue's counters: a sum per wave (a thousand atomics on three LDS words were 25 us of this kernel), met by thread 0 below
-    s0 = turn_wave_sum_to_last(s0); s1 = turn_wave_sum_to_last(s1); s2 = turn_wave_sum_to_last(s2);
-    if ((tid & 63) == 63) { wsum[0][tid >> 6] = s0; wsum[1][tid >> 6] = s1; wsum[2][tid >> 6] = s2; }
-    if (tid == 0) got_in_flag = 0;
-    auto adapted_scale = [&]() {                               // dynesty-style, from the queue's counters
-      long long c0 = 0, c1 = 0, c2 = 0;
-      for (int w = 0; w < 16; ++w) { c0 += wsum[0][w]; c1 += wsum[1][w]; c2 += wsum[2][w]; }
-      const long long denom = c1 + c2 > 1 ? c1 + c2 : 1;
-      const double frac = (double)c0 / (double)denom;         // a redrawn (out-of-cube) proposal counts as a rejection
-      double sc = dyn0 * exp((frac - 0.5) / nd / 0.5);
-      sc = sc > 1e-4 ? sc : 1e-4;
-      return sc < 4.0 ? sc : 4.0;
-    };
-    double kv0[2]; int iv0[2];
-#pragma unroll
-    for (int q = 0; q < 2; ++q) {
-      const int e = tid + q * 1024;
-      kv0[q] = -INFINITY; iv0[q] = (1 << 30) + e;
-      if (e < nl + K && na_in[q] > 0) { const double l = l_in[q]; kv0[q] = (l != l) ? -INFINITY : l; iv0[q] = e; }
-    }
-    // bitonic sort, "before" = larger lnprob, then smaller id
-    if (a.n2 <= 1024) {
-      // One element per thread, in registers.  The exchanges at distances below 64 stay inside the wave (45 of the 55 stages of 1024
-      // elements), the others go through LDS, two buffers in turn: one barrier a stage (every stage as an LDS pass between two
-      // barriers made this kernel 38 us).
-      // A live set that comes from a merging turn arrives best first, which is the order the network's first stages (runs up to half
-      // the array) would bring it to: when it IS one half of the array its threads sit those stages out.
-      const int i = tid;
-      const bool half_sorted = a.live_sorted && 2 * nl == a.n2 && (nl & 63) == 0;
-      double kv = kv0[0];
-      int iv = iv0[0];
-      lds_barrier();                                          // (the flag's zero in front of its ones; the waves' counters)
-      export_out();
-      if (tid == 0) scale = adapted_scale();                  // (no part of the sort's result in it: here thread 0's wave has the time, with a sorted half)
-      int buf = 0;
-      auto lds_stages = [&](int kk, bool idle) {                // distances 64 and up
-        for (int j = kk >> 1; j >= 64; j >>= 1) {
-          double* kb = key + buf * 1024; int* ib = id + buf * 1024;
-          buf ^= 1;
-          if (i < a.n2) { kb[i] = kv; ib[i] = iv; }             // (the sorted half's threads too: their partners read them at the last level)
-          lds_barrier();
-          if (!idle) {
-            const double kp = i < a.n2 ? kb[i ^ j] : kv; const int ip = i < a.n2 ? ib[i ^ j] : iv;
-            const bool mine_first = (kv > kp) || (kv == kp && iv < ip);
-            const bool want_first = (((i & j) == 0) == ((i & kk) == 0));
-            if (mine_first != want_first) { kv = kp; iv = ip; }
-          }
-        }
-      };
-      if (a.n2 == 1024) {                                       // the usual size, unrolled: the distances are compile-time constants
-#define PAYNE_TURN_LEVEL(KK) do { const bool idle = half_sorted && KK <= nl && i < nl; lds_stages(KK, idle); \
-                                  if (!idle) turn_cmpx<KK, (KK / 2 < 32 ? KK / 2 : 32)>(kv, iv, i); } while (0)
-        PAYNE_TURN_LEVEL(2); PAYNE_TURN_LEVEL(4); PAYNE_TURN_LEVEL(8); PAYNE_TURN_LEVEL(16); PAYNE_TURN_LEVEL(32);
-        PAYNE_TURN_LEVEL(64); PAYNE_TURN_LEVEL(128); PAYNE_TURN_LEVEL(256); PAYNE_TURN_LEVEL(512); PAYNE_TURN_LEVEL(1024);
-#undef PAYNE_TURN_LEVEL
-      } else {
-        for (int kk = 2; kk <= a.n2; kk <<= 1) {
-          const bool idle = half_sorted && kk <= nl && i < nl;   // (the same for a whole wave: nl is a multiple of 64 here)
-          lds_stages(kk, idle);
-          if (idle) continue;
-          for (int j = kk >> 1 < 32 ? kk >> 1 : 32; j > 0; j >>= 1) {
-            const double kp = __shfl_xor(kv, j); const int ip = __shfl_xor(iv, j);
-            const bool mine_first = (kv > kp) || (kv == kp && iv < ip);
-            const bool want_first = (((i & j) == 0) == ((i & kk) == 0));      // the lower place of an ascending run, the upper of a descending one
-            if (mine_first != want_first) { kv = kp; iv = ip; }
-          }
-        }
-      }
-      if (buf == 1) lds_barrier();                            // (the last exchange read the first buffer, which the result goes to)
-      if (i < a.n2) { key[i] = kv; id[i] = iv; }
-      if (i < nl && iv >= nl) got_in_flag = 1;
-    } else {
-#pragma unroll
-      for (int q = 0; q < 2; ++q) { const int e = tid + q * 1024; if (e < a.n2) { key[e] = kv0[q]; id[e] = iv0[q]; } }
-      export_out();
-      lds_barrier();
-      if (tid == 0) scale = adapted_scale();
-      for (int kk = 2; kk <= a.n2; kk <<= 1)
-        for (int j = kk >> 1; j > 0; j >>= 1) {
-          lds_barrier();
-          for (int i = tid; i < a.n2; i += 1024) {
-            const int p = i ^ j;
-            if (p > i) {
-              const double ki = key[i], kp = key[p]; const int ii = id[i], ip = id[p];
-              const bool i_first = (ki > kp) || (ki == kp && ii < ip);
-              const bool up = (i & kk) == 0;                   // this run sorts "first things first"
-              if (i_first != up) { key[i] = kp; key[p] = ki; id[i] = ip; id[p] = ii; }
-            }
-          }
-        }
-      lds_barrier();
-      for (int r = tid; r < nl; r += 1024) if (id[r] >= nl) got_in_flag = 1;
-    }
-    lds_barrier();
-    // the threshold the next queue walks under: the largest lnprob left outside the new set.  That is the lnprob D of the last point
-    // to die (dynesty's loglstar; payne_ns::peek_index) OR a proposal that was turned away after the last replacement, which lies
-    // between D and the new live minimum M -- any threshold in [D, M) is valid to walk under (a proposal is tested again, against the
-    // worst live point of its iteration, when the host consumes it), and the host accepts exactly that window (nested.py
-    // _fill_queue_dev).  If no proposal got in, nothing died and the old threshold stays.
-    if (tid == 0) lstar = got_in_flag ? key[nl] : dyn1;       // (thread 0 alone writes it, and the scale)
-    // the new live set, row r = the r-th best
-    // (four elements' loads in flight per thread: one element at a time this loop was a dozen memory latencies end to end, 2.6 us)
-    const float inv_nd = 1.0f / (float)nd;                   // (e < 2^15, nd <= 64: (e + 0.5) / nd is never within rounding of an integer)
-    for (int e0 = tid; e0 < nl * nd; e0 += 4096) {
-      double xu[4], xv[4];
-#pragma unroll
-      for (int q = 0; q < 4; ++q) {
-        const int e = e0 + q * 1024;
-        xu[q] = 0.0; xv[q] = 0.0;
-        if (e < nl * nd) {
-          const int r = (int)(((float)e + 0.5f) * inv_nd), d = e - r * nd, who = id[r];
-          const bool live = who < nl;
-          const size_t src = (size_t)(live ? who : who - nl) * nd + d;
-          xu[q] = live ? a.lu[src] : a.cu[src];
-          xv[q] = live ? a.lv[src] : a.cv[src];
-        }
-      }
-#pragma unroll
-      for (int q = 0; q < 4; ++q) {
-        const int e = e0 + q * 1024;
-        if (e < nl * nd) {
-          a.ou[e] = xu[q]; a.ov[e] = xv[q];
-          if (lds_rows) { turn_rows[e] = xu[q]; turn_rows[nl * nd + e] = xv[q]; }
-        }
-      }
-    }
-    for (int r = tid; r < nl; r += 1024) a.ol[r] = key[r];
-  }
-  // a new bound: read across the bus (2 us), requested HERE -- loads return in order, whoever waits for a later one waits for these --
-  // and stored at the end, behind the chains' rows
-  double axv[2] = {0.0, 0.0};
-  if (a.ax_n > 0) {
-#pragma unroll
-    for (int q = 0; q < 2; ++q) { const int e = tid + q * 1024; if (e < a.ax_n) axv[q] = a.ax_src[e]; }
-  }
-  if (!a.merge) export_out();
-  turn_barrier();                                            // (the chains' rows are overwritten below -- the export above has read the old values --; the new set is read back by this workgroup only)
-  if (tid == 0) { a.dyn[0] = scale; a.dyn[1] = lstar; }
-  // start points: uniform among the live points (queue_begin_core's draw)
-  auto mix = [](unsigned long long x) {
-    x += 0x9E3779B97F4A7C15ull; x = (x ^ (x >> 30)) * 0xBF58476D1CE4E5B9ull; x = (x ^ (x >> 27)) * 0x94D049BB133111EBull;
-    return x ^ (x >> 31);
-  };
-  for (int k = tid; k < K; k += 1024) {                       // (K <= 1024; the slot of every chain once, through the sort's LDS -- id[] is free: the barrier above)
-    const unsigned long long r0 = mix(a.seed ^ (0xA5A5A5A5ull + (unsigned long long)k * 0x100000001B3ull));
-    const int i = (nl & (nl - 1)) == 0 ? (int)(r0 & (unsigned long long)(nl - 1)) : (int)(r0 % (unsigned long long)nl);   // (the 64-bit remainder is a routine of 200 instructions)
-    id[k] = i;
-    a.cl[k] = a.merge ? key[i] : a.ol[i];
-    a.na[k] = 0; a.nc[k] = 0; a.nr[k] = 0;
-  }
-  turn_barrier();
-  const float inv_nd_ = 1.0f / (float)nd;
-  for (int e0 = tid; e0 < K * nd; e0 += 4096) {
-    double xu[4], xv[4];
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-      const int e = e0 + q * 1024;
-      xu[q] = 0.0; xv[q] = 0.0;
-      if (e < K * nd) {
-        const int k = (int)(((float)e + 0.5f) * inv_nd_), d = e - k * nd, i = id[k];
-        xu[q] = lds_rows ? turn_rows[i * nd + d] : a.ou[(size_t)i * nd + d];
-        xv[q] = lds_rows ? turn_rows[nl * nd + i * nd + d] : a.ov[(size_t)i * nd + d];
-      }
-    }
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-      const int e = e0 + q * 1024;
-      if (e < K * nd) { a.cu[e] = xu[q]; a.cv[e] = xv[q]; }
-    }
-  }
-#pragma unroll
-  for (int q = 0; q < 2; ++q) { const int e = tid + q * 1024; if (e < a.ax_n) a.ax_dst[e] = axv[q]; }
-  for (int e = tid + 2048; e < a.ax_n; e += 1024) a.ax_dst[e] = a.ax_src[e];
-  if (a.exp_dst) {
-    // every wave's stores are acknowledged before it passes the barrier (__syncthreads waits for them); ONE system-scope release then
-    // covers them all (release fences are cumulative) -- a fence in each of the sixteen waves, each a write-back of the L2, was 6 us
-    __syncthreads();
-    if (tid == 0) __hip_atomic_store(a.exp_flag, a.exp_seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
-  }
-}
-static int queue_begin_core(payne_sampler* s, const double* live_u, const double* live_v, const double* live_logl,
-                            int nlive, int K, const double* axes_unit, int n_ell, const double* ctr, const double* ainv,
-                            double scale, double loglstar, int walks, unsigned long long seed, void* stream,
-                            const int* src, const double* qu, const double* qv, const double* lg);
-extern "C" int payne_ns_rwalk_queue_begin(payne_sampler* s, const double* live_u, const double* live_v, const double* live_logl,
-                                          int nlive, int K, const double* axes_unit, int n_ell, const double* ctr, const double* ainv,
-                                          double scale, double loglstar, int walks, unsigned long long seed, void* stream) {
-  return queue_begin_core(s, live_u, live_v, live_logl, nlive, K, axes_unit, n_ell, ctr, ainv, scale, loglstar, walks, seed, stream,
-                          nullptr, nullptr, nullptr, nullptr);
-}
 static int queue_begin_core(payne_sampler* s, const double* live_u, const double* live_v, const double* live_logl,
                             int nlive, int K, const double* axes_unit, int n_ell, const double* ctr, const double* ainv,
                             double scale, double loglstar, int walks, unsigned long long seed, void* stream,
@@ -2118,71 +1813,37 @@ static int queue_begin_core(payne_sampler* s, const double* live_u, const double
   s->queue_open = false;
   if (!live_logl || !axes_unit || nlive <= 0 || walks <= 0)
     return fail(c, PAYNE_E_INVALID, "bad payne_ns_rwalk_queue arguments");
-  if (n_ell < 1 || n_ell > PAYNE_MAX_ELL || (n_ell > 1 && (!ctr || !ainv))) return fail(c, PAYNE_E_INVALID, "bad ellipsoid list");
-  const int nd = s->sd.ndim;
+  if (const char* bad = pq::check_ell_list(n_ell, ctr && ainv)) return fail(c, PAYNE_E_INVALID, bad);
+  const pq::Layout L(K, s->sd.ndim, n_ell);
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  // ---- start points: uniform among the live points (splitmix of the seed).  With several ellipsoids the walk's first step finds
-  //      the one each chain steps in on the device (walk_assign_ell: on the host that loop was 8 us per ellipsoid, before the GPU
-  //      could start)
-  auto mix = [](unsigned long long x) {
-    x += 0x9E3779B97F4A7C15ull; x = (x ^ (x >> 30)) * 0xBF58476D1CE4E5B9ull; x = (x ^ (x >> 27)) * 0x94D049BB133111EBull;
-    return x ^ (x >> 31);
-  };
-  double* hu = s->q_host;
-  double* hv = hu + (size_t)K * nd;
-  double* hl = hv + (size_t)K * nd;
-  for (int k = 0; k < K; ++k) {
-    const unsigned long long r0 = mix(seed ^ (0xA5A5A5A5ull + (unsigned long long)k * 0x100000001B3ull));
-    const int i = (int)(r0 % (unsigned long long)nlive);
-    const bool q = src && src[i] >= 0;
-    // (rows of a dozen doubles, 2 K of them between two queues: copied in place -- a memcpy call each was 20 us of the turn)
-    const double* su = q ? qu + (size_t)src[i] * nd : live_u + (size_t)i * nd;
-    const double* sv = q ? qv + (size_t)src[i] * nd : live_v + (size_t)i * nd;
-    double* du_ = hu + (size_t)k * nd;
-    double* dv_ = hv + (size_t)k * nd;
-    for (int d = 0; d < nd; ++d) { du_[d] = su[d]; dv_[d] = sv[d]; }
-    hl[k] = src ? lg[i] : live_logl[i];
-  }
+  pq::fill_starts(L, s->q_host, seed, nlive, live_u, live_v, live_logl, src, qu, qv, lg);
   // one transfer each way: chains, axes and (several ellipsoids) centres and inverse axes up; chains, then the three counters down
-  const size_t nq_d = (size_t)K * (2 * nd + 1), n_cnt = ((size_t)3 * K + 1) / 2, n_ax = (size_t)n_ell * nd * nd;
-  const size_t n_as = n_ell > 1 ? (size_t)n_ell * nd + n_ax : 0;
-  double* hax = hl + K + n_cnt;
-  std::memcpy(hax, axes_unit, n_ax * 8);
-  if (n_ell > 1) {
-    std::memcpy(hax + n_ax, ctr, (size_t)n_ell * nd * 8);
-    std::memcpy(hax + n_ax + (size_t)n_ell * nd, ainv, n_ax * 8);
-  }
+  pq::pack_bound(L, L.view(s->q_host).axes, axes_unit, ctr, ainv);
   if (s->q_host_dev) {
-    const size_t n_up = nq_d + n_cnt + n_ax + n_as;
+    const size_t n_up = L.n_up();
     hipLaunchKernelGGL(payne_stage_in_kernel, dim3((unsigned)((n_up + 1023) / 1024)), dim3(256), 0, st, s->q_dev, s->q_host_dev, n_up);
   } else {
-    HIPCHK(c, hipMemcpyAsync(s->q_dev, s->q_host, (nq_d + n_cnt + n_ax + n_as) * 8, hipMemcpyHostToDevice, st));
+    HIPCHK(c, hipMemcpyAsync(s->q_dev, s->q_host, L.n_up() * 8, hipMemcpyHostToDevice, st));
   }
-  double* du = s->q_dev;
-  double* dv = du + (size_t)K * nd;
-  double* dl = dv + (size_t)K * nd;
-  int* dna = reinterpret_cast<int*>(dl + K);
-  int* dnc = dna + K;
-  int* dnr = dnc + K;
-  const double* dax = dl + K + n_cnt;
-  int* dell = n_ell > 1 ? reinterpret_cast<int*>(const_cast<double*>(dax) + n_ax + n_as) : nullptr;   // (device only: written by the first step)
-  rwalk_begin_impl(s, du, dv, dl, K, dax, dell, scale, loglstar, walks, seed, dna, dnc, dnr, stream);
-  if (n_ell > 1) { s->walk.as_ctr = dax + n_ax; s->walk.as_ainv = dax + n_ax + (size_t)n_ell * nd; s->walk.ell_out = dell; s->walk.n_ell = n_ell; }
-  for (int w = 0; !rc && w <= walks; ++w) rc = payne_rwalk_step(s, w);
-  if (rc) return rc;
+  if ((rc = queue_walk(s, L, scale, loglstar, walks, seed, nullptr, stream))) return rc;
   if (s->q_host_dev) {
     ++s->q_seq;
-    hipLaunchKernelGGL(payne_stage_out_kernel, dim3(s->q_arrivals ? 8 : 1), dim3(1024), 0, st, s->q_host_dev, s->q_dev, nq_d + n_cnt, s->q_flag_dev, s->q_seq,
+    hipLaunchKernelGGL(payne_stage_out_kernel, dim3(s->q_arrivals ? 8 : 1), dim3(1024), 0, st, s->q_host_dev, s->q_dev, L.n_down(), s->q_flag_dev, s->q_seq,
                        (const double*)nullptr, 0, s->q_arrivals);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return fail(c, PAYNE_E_HIP, std::string("queue staging launch: ") + hipGetErrorString(e));
   } else {
-    HIPCHK(c, hipMemcpyAsync(s->q_host, s->q_dev, (nq_d + n_cnt) * 8, hipMemcpyDeviceToHost, st));
+    HIPCHK(c, hipMemcpyAsync(s->q_host, s->q_dev, L.n_down() * 8, hipMemcpyDeviceToHost, st));
   }
   s->queue_open = true; s->queue_K = K; s->queue_stream = stream;
   return PAYNE_OK;
 }
-static void queue_extract(const double* hu, int K, int nd, double* qu, double* qv, double* ql, int* qnc, int* nq, long long* stats);
+extern "C" int payne_ns_rwalk_queue_begin(payne_sampler* s, const double* live_u, const double* live_v, const double* live_logl,
+                                          int nlive, int K, const double* axes_unit, int n_ell, const double* ctr, const double* ainv,
+                                          double scale, double loglstar, int walks, unsigned long long seed, void* stream) {
+  return queue_begin_core(s, live_u, live_v, live_logl, nlive, K, axes_unit, n_ell, ctr, ainv, scale, loglstar, walks, seed, stream,
+                          nullptr, nullptr, nullptr, nullptr);
+}
 static bool wait_word(volatile unsigned long long* w, unsigned long long want, double seconds) {
   // Spin while the wait is as long as queues have been taking (1.5 x the wait before: a C2 queue is ~1 ms, and a timer's wake-up
   // after a 50 us sleep cost the host-turn loop 50-100 us a collect when queues ran just over a fixed 1 ms window), at least one
@@ -2226,36 +1887,9 @@ extern "C" int payne_ns_rwalk_queue_end(payne_sampler* s, double* qu, double* qv
   } else {
     HIPCHK(c, hipStreamSynchronize(st));
   }
-  queue_extract(hu, K, nd, qu, qv, ql, qnc, nq, stats);
+  pq::queue_extract(hu, K, nd, qu, qv, ql, qnc, nq, stats);
   return PAYNE_OK;
 }
-// ---- the chains that moved are the queue; a chain that never moved is a copy of a live point
-static void queue_extract(const double* hu, int K, int nd, double* qu, double* qv, double* ql, int* qnc, int* nq, long long* stats) {
-  const double* hv = hu + (size_t)K * nd;
-  const double* hl = hv + (size_t)K * nd;
-  long long acc = 0, calls = 0, redraw = 0, idle_calls = 0;
-  int m = 0;
-  const int *na = reinterpret_cast<const int*>(hl + K), *nc = na + K, *nr = nc + K;
-  for (int k = 0; k < K; ++k) {
-    acc += na[k]; calls += nc[k]; redraw += nr[k];
-    if (na[k] > 0) {
-      const double* su = hu + (size_t)k * nd;
-      const double* sv = hv + (size_t)k * nd;
-      double* du_ = qu + (size_t)m * nd;
-      double* dv_ = qv + (size_t)m * nd;
-      for (int d = 0; d < nd; ++d) { du_[d] = su[d]; dv_[d] = sv[d]; }
-      const double l = hl[k];
-      ql[m] = (l != l) ? -INFINITY : l;
-      qnc[m] = nc[k] > 1 ? nc[k] : 1;
-      ++m;
-    } else {
-      idle_calls += nc[k];
-    }
-  }
-  *nq = m;
-  stats[0] = acc; stats[1] = calls; stats[2] = redraw; stats[3] = idle_calls;
-}
-
 // ---- the queue's turn on the device: host entry points (header: payne_ns_queue_dev_*) ------------------------------------------
 extern "C" int payne_ns_queue_dev_init(payne_sampler* s, const double* live_u, const double* live_v, const double* live_logl, int nlive,
                                        double scale, double loglstar) {
@@ -2266,9 +1900,8 @@ extern "C" int payne_ns_queue_dev_init(payne_sampler* s, const double* live_u, c
   if (s->dq_launched != s->dq_collected) return fail(c, PAYNE_E_INVALID, "payne_ns_queue_dev_init with queues in flight");
   const int nd = s->sd.ndim, K = s->k_max;
   if (nlive + K > 2048) return fail(c, PAYNE_E_UNSUPPORTED, "nlive + queue size > 2048");
-  int prev = 0;
-  (void)hipGetDevice(&prev);
-  if (prev != c->device) HIPCHK(c, hipSetDevice(c->device));
+  int rc = on_device(c);
+  if (rc) return rc;
   if (nlive != s->lv_n) {
     for (int b = 0; b < 2; ++b) {
       void* p = nullptr;
@@ -2279,19 +1912,21 @@ extern "C" int payne_ns_queue_dev_init(payne_sampler* s, const double* live_u, c
     s->lv_n = nlive;
   }
   if (!s->dyn) { void* p = nullptr; HIPCHK(c, hipMalloc(&p, 4 * 8)); s->owned.push_back(p); s->dyn = static_cast<double*>(p); }
-  const size_t nblk = q_doubles(K, nd) + 16;
+  const pq::HostBlock blk = pq::dq_host_block(K, nd);
   for (int b = 0; b < 2; ++b) {
     if (!s->dq_host[b]) {
-      HIPCHK(c, hipHostMalloc((void**)&s->dq_host[b], nblk * 8, hipHostMallocMapped));
+      HIPCHK(c, hipHostMalloc((void**)&s->dq_host[b], blk.doubles * 8, hipHostMallocMapped));
       void* dp = nullptr;
       HIPCHK(c, hipHostGetDevicePointer(&dp, s->dq_host[b], 0));
       s->dq_host_dev[b] = static_cast<double*>(dp);
-      s->dax_n = (int)((size_t)PAYNE_MAX_ELL * (2 * nd * nd + nd));
+      s->dq_flag[b] = reinterpret_cast<volatile unsigned long long*>(s->dq_host[b] + blk.flag);
+      s->dq_flag_dev[b] = reinterpret_cast<unsigned long long*>(s->dq_host_dev[b] + blk.flag);
+      s->dax_n = (int)pq::bound_capacity(nd);
       HIPCHK(c, hipHostMalloc((void**)&s->dax_host[b], (size_t)s->dax_n * 8, hipHostMallocMapped));
       HIPCHK(c, hipHostGetDevicePointer(&dp, s->dax_host[b], 0));
       s->dax_host_dev[b] = static_cast<double*>(dp);
     }
-    reinterpret_cast<volatile unsigned long long*>(s->dq_host[b] + q_doubles(K, nd) + 8)[0] = 0ull;
+    *s->dq_flag[b] = 0ull;
     s->dq_seq[b] = 0;
   }
   HIPCHK(c, hipMemcpy(s->lv_u[0], live_u, (size_t)nlive * nd * 8, hipMemcpyHostToDevice));
@@ -2315,38 +1950,24 @@ extern "C" int payne_ns_queue_dev_launch(payne_sampler* s, int K, const double* 
   if (s->dq_launched != s->dq_collected && K != s->dq_K) return fail(c, PAYNE_E_INVALID, "queue size changed with a queue in flight");
   if (s->queue_open) return fail(c, PAYNE_E_INVALID, "a host-turn queue is in flight");
   if (axes_unit) {
-    if (n_ell < 1 || n_ell > PAYNE_MAX_ELL || (n_ell > 1 && (!ctr || !ainv))) return fail(c, PAYNE_E_INVALID, "bad ellipsoid list");
+    if (const char* bad = pq::check_ell_list(n_ell, ctr && ainv)) return fail(c, PAYNE_E_INVALID, bad);
   } else {
     n_ell = s->dq_n_ell;
     if (n_ell < 1) return fail(c, PAYNE_E_INVALID, "no bound on the device yet");
   }
-  int prev = 0;
-  (void)hipGetDevice(&prev);
-  if (prev != c->device) HIPCHK(c, hipSetDevice(c->device));
+  int rc = on_device(c);
+  if (rc) return rc;
   const int nd = s->sd.ndim, nl = s->lv_n, b = s->dq_launched & 1;
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  const size_t nq_d = (size_t)K * (2 * nd + 1), n_cnt = ((size_t)3 * K + 1) / 2, n_ax = (size_t)n_ell * nd * nd;
-  const size_t n_as = n_ell > 1 ? (size_t)n_ell * nd + n_ax : 0;
-  double* du = s->q_dev;
-  double* dv = du + (size_t)K * nd;
-  double* dl = dv + (size_t)K * nd;
-  int* dna = reinterpret_cast<int*>(dl + K);
-  int* dnc = dna + K;
-  int* dnr = dnc + K;
-  double* dax = dl + K + n_cnt;
-  int* dell = n_ell > 1 ? reinterpret_cast<int*>(dax + n_ax + n_as) : nullptr;
+  const pq::Layout L(K, nd, n_ell);
+  const pq::View q = L.view(s->q_dev);
   if (axes_unit) {                                          // a new bound: up through its own mapped block (two, used in turn)
-    double* hax = s->dax_host[b];
-    std::memcpy(hax, axes_unit, n_ax * 8);
-    if (n_ell > 1) {
-      std::memcpy(hax + n_ax, ctr, (size_t)n_ell * nd * 8);
-      std::memcpy(hax + n_ax + (size_t)n_ell * nd, ainv, n_ax * 8);
-    }
+    pq::pack_bound(L, s->dax_host[b], axes_unit, ctr, ainv);
     s->dq_n_ell = n_ell;
   }
   TurnArgs ta{};
   ta.ax_src = s->dyn; ta.ax_dst = nullptr; ta.ax_n = 0;
-  if (axes_unit) { ta.ax_src = s->dax_host_dev[b]; ta.ax_dst = dax; ta.ax_n = (int)(n_ax + n_as); }   // (up with the turn kernel)
+  if (axes_unit) { ta.ax_src = s->dax_host_dev[b]; ta.ax_dst = q.axes; ta.ax_n = (int)L.n_bound(); }   // (up with the turn kernel)
   const int cur = s->lv_cur, nxt = merge ? cur ^ 1 : cur;
   ta.lu = s->lv_u[cur]; ta.lv = s->lv_v[cur]; ta.ll = s->lv_l[cur];
   ta.ou = s->lv_u[nxt]; ta.ov = s->lv_v[nxt]; ta.ol = s->lv_l[nxt];
@@ -2354,12 +1975,12 @@ extern "C" int payne_ns_queue_dev_launch(payne_sampler* s, int K, const double* 
   int n2 = 2;
   while (n2 < nl + K) n2 <<= 1;
   ta.n2 = n2;
-  ta.cu = du; ta.cv = dv; ta.cl = dl; ta.na = dna; ta.nc = dnc; ta.nr = dnr;
+  ta.cu = q.u; ta.cv = q.v; ta.cl = q.lnprob; ta.na = q.nacc; ta.nc = q.ncall; ta.nr = q.nredraw;
   ta.dyn = s->dyn; ta.scale0 = 0.0; ta.lstar0 = 0.0; ta.seed = seed;
   if (s->dq_launched > s->dq_exported) {                    // the queue before this one: its results leave with this turn
     const int pb = s->dq_exported & 1;
-    ta.exp_dst = s->dq_host_dev[pb]; ta.exp_n = (int)(nq_d + n_cnt);
-    ta.exp_flag = reinterpret_cast<unsigned long long*>(s->dq_host_dev[pb] + q_doubles(s->k_max, nd) + 8);
+    ta.exp_dst = s->dq_host_dev[pb]; ta.exp_n = (int)L.n_down();
+    ta.exp_flag = s->dq_flag_dev[pb];
     ta.exp_seq = ++s->dq_seq[pb];
     ++s->dq_exported;
   }
@@ -2375,12 +1996,7 @@ extern "C" int payne_ns_queue_dev_launch(payne_sampler* s, int K, const double* 
   if (merge) s->lv_sorted = true;
   hipLaunchKernelGGL(payne_ns_turn_kernel, dim3(1), dim3(1024), rows_bytes, st, ta);
   s->lv_cur = nxt;
-  rwalk_begin_impl(s, du, dv, dl, K, dax, dell, 0.0, 0.0, walks, seed, dna, dnc, dnr, stream);
-  s->walk.dyn = s->dyn;
-  if (n_ell > 1) { s->walk.as_ctr = dax + n_ax; s->walk.as_ainv = dax + n_ax + (size_t)n_ell * nd; s->walk.ell_out = dell; s->walk.n_ell = n_ell; }
-  int rc = PAYNE_OK;
-  for (int w = 0; !rc && w <= walks; ++w) rc = payne_rwalk_step(s, w);
-  if (rc) return rc;
+  if ((rc = queue_walk(s, L, 0.0, 0.0, walks, seed, s->dyn, stream))) return rc;
   // (its results: with the NEXT queue's turn, or by payne_ns_queue_dev_collect when none has been launched by then)
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) return fail(c, PAYNE_E_HIP, std::string("device-turn launch: ") + hipGetErrorString(e));
@@ -2394,24 +2010,20 @@ extern "C" int payne_ns_queue_dev_collect(payne_sampler* s, double* qu, double* 
   if (s->dq_collected >= s->dq_launched) return fail(c, PAYNE_E_INVALID, "payne_ns_queue_dev_collect without a queue in flight");
   if (!qu || !qv || !ql || !qnc || !nq || !stats) return fail(c, PAYNE_E_INVALID, "bad payne_ns_queue_dev_collect arguments");
   const int b = s->dq_collected & 1, K = s->dq_K, nd = s->sd.ndim;
+  const pq::Layout L(K, nd, 1);                             // (what comes down lies in front of the bound)
   if (s->dq_exported <= s->dq_collected) {                  // the newest queue, no turn behind it: a transfer of its own
-    const size_t nq_d = (size_t)K * (2 * nd + 1), n_cnt = ((size_t)3 * K + 1) / 2;
     ++s->dq_seq[b];
     hipLaunchKernelGGL(payne_stage_out_kernel, dim3(s->q_arrivals ? 8 : 1), dim3(1024), 0, reinterpret_cast<hipStream_t>(s->queue_stream),
-                       s->dq_host_dev[b], s->q_dev, nq_d + n_cnt,
-                       reinterpret_cast<unsigned long long*>(s->dq_host_dev[b] + q_doubles(s->k_max, nd) + 8), s->dq_seq[b], s->dyn, 2, s->q_arrivals);
+                       s->dq_host_dev[b], s->q_dev, L.n_down(), s->dq_flag_dev[b], s->dq_seq[b], s->dyn, 2, s->q_arrivals);
     ++s->dq_exported;
   }
-  volatile unsigned long long* flag = reinterpret_cast<volatile unsigned long long*>(s->dq_host[b] + q_doubles(s->k_max, nd) + 8);
+  volatile unsigned long long* flag = s->dq_flag[b];
   if (!wait_word(flag, s->dq_seq[b], 10.0)) {
     HIPCHK(c, hipStreamSynchronize(reinterpret_cast<hipStream_t>(s->queue_stream)));
     if (*flag != s->dq_seq[b]) return fail(c, PAYNE_E_HIP, "the queue's completion word never arrived");
   }
-  queue_extract(s->dq_host[b], K, nd, qu, qv, ql, qnc, nq, stats);
-  if (dyn_used) {
-    const size_t nq_d = (size_t)K * (2 * nd + 1), n_cnt = ((size_t)3 * K + 1) / 2;
-    dyn_used[0] = s->dq_host[b][nq_d + n_cnt]; dyn_used[1] = s->dq_host[b][nq_d + n_cnt + 1];
-  }
+  pq::queue_extract(s->dq_host[b], K, nd, qu, qv, ql, qnc, nq, stats);
+  if (dyn_used) { dyn_used[0] = s->dq_host[b][L.dyn_pair()]; dyn_used[1] = s->dq_host[b][L.dyn_pair() + 1]; }
   ++s->dq_collected;
   return PAYNE_OK;
 }
@@ -2428,14 +2040,7 @@ extern "C" int payne_ns_rwalk_queue_turn(payne_sampler* s, double* qu, double* q
   void* stream = s->queue_stream;
   int rc = payne_ns_rwalk_queue_end(s, qu, qv, ql, qnc, nq, stats);
   if (rc) return rc;
-  const int nd = s->sd.ndim;
-  {
-    const long long denom = stats[1] + stats[2] > 1 ? stats[1] + stats[2] : 1;
-    const double frac = (double)stats[0] / (double)denom;          // a redrawn (out-of-cube) proposal counts as a rejection
-    double sc = *scale * exp((frac - 0.5) / nd / 0.5);
-    sc = sc > 1e-4 ? sc : 1e-4;
-    *scale = sc < 4.0 ? sc : 4.0;
-  }
+  *scale = pq::adapt_scale(*scale, stats, s->sd.ndim);
   payne_ns::peek_index(nlive, live_logl, ql, *nq, s->pk_src, s->pk_l, s->pk_heap, loglstar, n_dead);
   return queue_begin_core(s, live_u, live_v, live_logl, nlive, K, axes_unit, n_ell, ctr, ainv, *scale, *loglstar, walks, seed, stream,
                           s->pk_src.data(), qu, qv, s->pk_l.data());

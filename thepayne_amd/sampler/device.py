@@ -20,6 +20,15 @@ _KIND = {'uniform': _lib.PRIOR_UNIFORM, 'gaussian': _lib.PRIOR_GAUSSIAN, 'tgauss
          'exp': _lib.PRIOR_EXP, 'texp': _lib.PRIOR_TEXP, 'loguniform': _lib.PRIOR_LOGUNIFORM}
 
 
+def queue_buffer(K, nd):
+    """Fresh host arrays a queue of up to K proposals is written to: (qU[K, nd], qV[K, nd], ql[K], qnc[K] int32)."""
+    return (np.empty((K, nd)), np.empty((K, nd)), np.empty(K), np.empty(K, dtype=np.int32))
+
+
+def _seed64(seed):
+    return int(seed) & 0xFFFFFFFFFFFFFFFF
+
+
 class DeviceProposer(object):
     def __init__(self, likeobj, priorobj, k_max=None, engine=None):
         self.like = likeobj
@@ -70,8 +79,17 @@ class DeviceProposer(object):
         self._lp = self.torch.empty(self.k_max, dtype=f64, device=dev)
         self._nacc = self.torch.empty(self.k_max, dtype=i32, device=dev)
         self._ncall = self.torch.empty(self.k_max, dtype=i32, device=dev)
-        self._pack_h = None                  # pinned staging for rwalk, made on first use
+        # chain staging of rwalk_begin / slice_begin .. _finish: ONE set of pinned and device buffers, made on first use (the library
+        # refuses a random walk and a slice walk open at once on one sampler); what the walk begun last left for its _finish
+        self._pack_h = self._pack_d = self._ipack_h = self._ipack_d = None
+        self._st_stream = self._st_ax = self._st_ell = None
+        self._st_K = 0
         self._qstats = np.zeros(4, dtype=np.int64)
+        self._dyn_used = np.zeros(2)         # queue_dev_collect: the {scale, loglstar} the queue ran under
+        self._qb_key = self._qb = None       # _queue_bound: the bound handed last, as the native calls take it
+        self._qb_dev = None                  # the key of the bound that is on the device (queue_dev_launch)
+        self._dq_out = 0                     # device-turn queues in flight
+        self._dq_epoch = 0                   # queue_dev_init calls so far
 
     # -- priors on derived quantities (prior.py:286-336, :449-451) ----------------------
     def _advanced(self, d, P, L):
@@ -153,6 +171,15 @@ class DeviceProposer(object):
     def _stream(self):
         return self.eng._stream()
 
+    def _check_K(self, K):
+        if K > self.k_max:
+            raise ValueError("K > k_max")
+
+    def _queue_result(self, nq):
+        """(nq, accepted, calls, redrawn, idle_calls) of the queue the native call just wrote."""
+        stats = self._qstats
+        return nq.value, int(stats[0]), int(stats[1]), int(stats[2]), int(stats[3])
+
     def _up(self, a, dst):
         t = self.torch.as_tensor(np.ascontiguousarray(a, dtype=np.float64))
         dst[:len(a)].copy_(t.reshape(dst[:len(a)].shape))
@@ -199,19 +226,17 @@ class DeviceProposer(object):
         ql[K], qnc[K] int32) host arrays the queue is written to.  Returns (nq, accepted, calls, redrawn, idle_calls).
         ``between``: a callable run on the host while the GPU walks (payne_ns_rwalk_queue_begin .. _end)."""
         if between is None:
-            if K > self.k_max:
-                raise ValueError("K > k_max")
+            self._check_K(K)
             axp, n_ell, cp, ap, keep = self._queue_bound(axes_unit, ctr, ainv)
             qU, qV, ql, qnc = qbuf
             nq = C.c_int(0)
-            stats = self._qstats
             rc = self.lib.payne_ns_rwalk_queue(self._handle, live_u.ctypes.data, live_v.ctypes.data, live_logl.ctypes.data,
                                                len(live_logl), int(K), axp, n_ell, cp, ap, float(scale), float(loglstar),
-                                               int(walks), int(seed) & 0xFFFFFFFFFFFFFFFF, qU.ctypes.data, qV.ctypes.data,
-                                               ql.ctypes.data, qnc.ctypes.data, C.byref(nq), stats.ctypes.data, self._stream())
+                                               int(walks), _seed64(seed), qU.ctypes.data, qV.ctypes.data,
+                                               ql.ctypes.data, qnc.ctypes.data, C.byref(nq), self._qstats.ctypes.data, self._stream())
             if rc != 0:
                 self.eng._err(rc, "payne_ns_rwalk_queue")
-            return nq.value, int(stats[0]), int(stats[1]), int(stats[2]), int(stats[3])
+            return self._queue_result(nq)
         self.rwalk_queue_begin(live_u, live_v, live_logl, K, axes_unit, ctr, ainv, scale, loglstar, walks, seed)
         try:
             between()
@@ -223,7 +248,7 @@ class DeviceProposer(object):
         """The bound's arrays as the native call takes them; remembered while the caller hands the same objects (a bound lives for
         several queues, and three ascontiguousarray + six attribute lookups are 10 us between two queues)."""
         key = (id(axes_unit), id(ctr), id(ainv))
-        if getattr(self, "_qb_key", None) == key:
+        if self._qb_key == key:
             return self._qb
         ax = np.ascontiguousarray(axes_unit, dtype=np.float64)
         n_ell = 1 if ax.ndim == 2 else ax.shape[0]
@@ -239,12 +264,11 @@ class DeviceProposer(object):
     def rwalk_queue_begin(self, live_u, live_v, live_logl, K, axes_unit, ctr, ainv, scale, loglstar, walks, seed):
         """payne_ns_rwalk_queue_begin: everything of one queue enqueued on the stream (nothing of the arguments is read after the
         call returns); the host is free until rwalk_queue_end."""
-        if K > self.k_max:
-            raise ValueError("K > k_max")
+        self._check_K(K)
         axp, n_ell, cp, ap, keep = self._queue_bound(axes_unit, ctr, ainv)
         rc = self.lib.payne_ns_rwalk_queue_begin(self._handle, live_u.ctypes.data, live_v.ctypes.data, live_logl.ctypes.data,
                                                  len(live_logl), int(K), axp, n_ell, cp, ap, float(scale),
-                                                 float(loglstar), int(walks), int(seed) & 0xFFFFFFFFFFFFFFFF, self._stream())
+                                                 float(loglstar), int(walks), _seed64(seed), self._stream())
         if rc != 0:
             self.eng._err(rc, "payne_ns_rwalk_queue_begin")
 
@@ -253,39 +277,35 @@ class DeviceProposer(object):
         idle_calls)."""
         qU, qV, ql, qnc = qbuf
         nq = C.c_int(0)
-        stats = self._qstats
         rc = self.lib.payne_ns_rwalk_queue_end(self._handle, qU.ctypes.data, qV.ctypes.data, ql.ctypes.data, qnc.ctypes.data,
-                                               C.byref(nq), stats.ctypes.data)
+                                               C.byref(nq), self._qstats.ctypes.data)
         if rc != 0:
             self.eng._err(rc, "payne_ns_rwalk_queue_end")
-        return nq.value, int(stats[0]), int(stats[1]), int(stats[2]), int(stats[3])
+        return self._queue_result(nq)
 
     def rwalk_queue_turn(self, qbuf, live_u, live_v, live_logl, K, axes_unit, ctr, ainv, scale, loglstar, walks, seed):
         """payne_ns_rwalk_queue_turn: collect the queue in flight into ``qbuf``, adapt the scale, predict the state its consumption
         will leave and launch the next queue from there -- one native call between two queues.  Returns (nq, accepted, calls,
         redrawn, idle_calls, scale, loglstar_after, n_dead)."""
-        if K > self.k_max:
-            raise ValueError("K > k_max")
+        self._check_K(K)
         axp, n_ell, cp, ap, keep = self._queue_bound(axes_unit, ctr, ainv)
         qU, qV, ql, qnc = qbuf
         nq, m = C.c_int(0), C.c_int(0)
         sc, ls = C.c_double(scale), C.c_double(loglstar)
-        stats = self._qstats
         rc = self.lib.payne_ns_rwalk_queue_turn(self._handle, qU.ctypes.data, qV.ctypes.data, ql.ctypes.data, qnc.ctypes.data,
-                                                C.byref(nq), stats.ctypes.data, live_u.ctypes.data, live_v.ctypes.data,
+                                                C.byref(nq), self._qstats.ctypes.data, live_u.ctypes.data, live_v.ctypes.data,
                                                 live_logl.ctypes.data, len(live_logl), int(K), axp, n_ell, cp, ap, C.byref(sc),
-                                                C.byref(ls), int(walks), int(seed) & 0xFFFFFFFFFFFFFFFF, C.byref(m))
+                                                C.byref(ls), int(walks), _seed64(seed), C.byref(m))
         if rc != 0:
             self.eng._err(rc, "payne_ns_rwalk_queue_turn")
-        return nq.value, int(stats[0]), int(stats[1]), int(stats[2]), int(stats[3]), sc.value, ls.value, m.value
+        return self._queue_result(nq) + (sc.value, ls.value, m.value)
 
     # ---- the queue's turn on the device (payne_ns_queue_dev_*): the live set lives there, queues follow each other without the host
     def queue_dev_init(self, live_u, live_v, live_logl, scale, loglstar):
         """Upload the live set and the scale / threshold the first queue starts from.  Queues still in flight (a sampling loop
         that was abandoned without being finalised: its generator still referenced somewhere) are collected and dropped first."""
-        while getattr(self, "_dq_out", 0) > 0:
-            K, nd = self.k_max, self.ndim
-            self.queue_dev_collect((np.empty((K, nd)), np.empty((K, nd)), np.empty(K), np.empty(K, dtype=np.int32)))
+        while self._dq_out > 0:
+            self.queue_dev_collect(queue_buffer(self.k_max, self.ndim))
         u = np.ascontiguousarray(live_u, dtype=np.float64)
         v = np.ascontiguousarray(live_v, dtype=np.float64)
         l = np.ascontiguousarray(np.where(np.isnan(live_logl), -np.inf, live_logl), dtype=np.float64)
@@ -295,78 +315,93 @@ class DeviceProposer(object):
         self._qb_dev = None
         # (whose queues are in flight from here on: a sampler that finds another epoch when it comes to drain "its" queues -- an
         #  abandoned loop finalised after another sampler started on this proposer -- has none left: they were dropped above)
-        self._dq_epoch = getattr(self, "_dq_epoch", 0) + 1
+        self._dq_epoch += 1
         return self._dq_epoch
 
     def queue_dev_launch(self, K, axes_unit, ctr, ainv, walks, seed, merge=True):
         """Enqueue one queue behind whatever is in flight: [the bound, when it is not the one already on the device] + the turn
         (merge: the queue before this one into the live set) + the walk + its results' transfer."""
-        if K > self.k_max:
-            raise ValueError("K > k_max")
+        self._check_K(K)
         key = (id(axes_unit), id(ctr), id(ainv))
-        if getattr(self, "_qb_dev", None) == key:
+        if self._qb_dev == key:
             axp, n_ell, cp, ap = None, 0, None, None                     # (the bound on the device is this one)
         else:
             axp, n_ell, cp, ap, keep = self._queue_bound(axes_unit, ctr, ainv)
-        rc = self.lib.payne_ns_queue_dev_launch(self._handle, int(K), axp, n_ell, cp, ap, int(walks), int(seed) & 0xFFFFFFFFFFFFFFFF,
+        rc = self.lib.payne_ns_queue_dev_launch(self._handle, int(K), axp, n_ell, cp, ap, int(walks), _seed64(seed),
                                                 1 if merge else 0, self._stream())
         if rc != 0:
             self.eng._err(rc, "payne_ns_queue_dev_launch")
         self._qb_dev = key
-        self._dq_out = getattr(self, "_dq_out", 0) + 1
+        self._dq_out += 1
 
     def queue_dev_collect(self, qbuf):
         """The oldest queue in flight, as rwalk_queue_end returns it, + the scale and threshold it ran under."""
         qU, qV, ql, qnc = qbuf
         nq = C.c_int(0)
-        stats = self._qstats
-        if getattr(self, "_dyn_used", None) is None:
-            self._dyn_used = np.zeros(2)
         rc = self.lib.payne_ns_queue_dev_collect(self._handle, qU.ctypes.data, qV.ctypes.data, ql.ctypes.data, qnc.ctypes.data,
-                                                 C.byref(nq), stats.ctypes.data, self._dyn_used.ctypes.data)
+                                                 C.byref(nq), self._qstats.ctypes.data, self._dyn_used.ctypes.data)
         if rc != 0:
             self.eng._err(rc, "payne_ns_queue_dev_collect")
-        self._dq_out = getattr(self, "_dq_out", 1) - 1
-        return nq.value, int(stats[0]), int(stats[1]), int(stats[2]), int(stats[3]), float(self._dyn_used[0]), float(self._dyn_used[1])
+        self._dq_out -= 1
+        return self._queue_result(nq) + (float(self._dyn_used[0]), float(self._dyn_used[1]))
 
-    # the same in three parts (MultiPopProposer interleaves the steps of several populations)
-    def rwalk_begin(self, U, V, lnprob, axes, scale, loglstar, walks, seed, stream=None, ell=None):
+    # ---- chain staging: what a random walk and a slice walk in parts share
+    def _stage_chains(self, U, V, lnprob, axes, ell, stream):
+        """Stage K chains (U | V | lnprob: one packed pinned transfer on `stream`, default the current one) and the bound.  Returns
+        (K, pointers to u, v, lnprob on the device, axes pointer, n_ell, ell pointer or None, pointer to 3 k_max device ints for the
+        walk's counters, the stream's handle)."""
         K, nd = len(U), self.ndim
-        if K > self.k_max:
-            raise ValueError("K > k_max")
+        self._check_K(K)
         t = self.torch
         if self._pack_h is None:
             n = self.k_max * (2 * nd + 1)
             self._pack_h = t.empty(n, dtype=t.float64).pin_memory()
             self._pack_d = t.empty(n, dtype=t.float64, device=self.eng.device)
-            self._ipack_h = t.empty(2 * self.k_max, dtype=t.int32).pin_memory()
-            self._ipack_d = t.empty(2 * self.k_max, dtype=t.int32, device=self.eng.device)
-        self._run_stream = stream if stream is not None else t.cuda.current_stream(self.eng.device)
+            self._ipack_h = t.empty(3 * self.k_max, dtype=t.int32).pin_memory()
+            self._ipack_d = t.empty(3 * self.k_max, dtype=t.int32, device=self.eng.device)
+        self._st_stream = stream if stream is not None else t.cuda.current_stream(self.eng.device)
         n = K * (2 * nd + 1)
         h = self._pack_h.numpy()
         h[:K * nd] = np.asarray(U, dtype=np.float64).reshape(-1)
         h[K * nd:2 * K * nd] = np.asarray(V, dtype=np.float64).reshape(-1)
         h[2 * K * nd:n] = lnprob
         d = self._pack_d
-        with t.cuda.stream(self._run_stream):
+        with t.cuda.stream(self._st_stream):
             d[:n].copy_(self._pack_h[:n], non_blocking=True)
-        pu, pv, pl = d.data_ptr(), d.data_ptr() + 8 * K * nd, d.data_ptr() + 16 * K * nd
         ax = np.ascontiguousarray(axes, dtype=np.float64)
         n_ell, ell_p = 1, None
         if ax.ndim == 3:
             n_ell = ax.shape[0]
             if n_ell > 1:
-                self._ell_h = np.ascontiguousarray(ell, dtype=np.int32)
-                if self._ell_h.shape != (K,):
+                self._st_ell = np.ascontiguousarray(ell, dtype=np.int32)
+                if self._st_ell.shape != (K,):
                     raise ValueError("ell must name one ellipsoid per chain")
-                ell_p = self._ell_h.ctypes.data
-        rc = self.lib.payne_rwalk_begin_ell(self._handle, pu, pv, pl, K, ax.ctypes.data, n_ell, ell_p,
-                                            float(scale), float(loglstar), int(walks), int(seed) & 0xFFFFFFFFFFFFFFFF,
-                                            self._ipack_d.data_ptr(), self._ipack_d.data_ptr() + 4 * K,
-                                            C.c_void_p(self._run_stream.cuda_stream))
+                ell_p = self._st_ell.ctypes.data
+        self._st_ax, self._st_K = ax, K
+        p = d.data_ptr()
+        return (K, p, p + 8 * K * nd, p + 16 * K * nd, ax.ctypes.data, n_ell, ell_p, self._ipack_d.data_ptr(),
+                C.c_void_p(self._st_stream.cuda_stream))
+
+    def _unstage_chains(self, n_int):
+        """The staged chains and the first n_int of their per-chain int counters back: (U, V, lnprob, counter 0, ...)."""
+        K, nd, t = self._st_K, self.ndim, self.torch
+        n = K * (2 * nd + 1)
+        with t.cuda.stream(self._st_stream):
+            self._pack_h[:n].copy_(self._pack_d[:n], non_blocking=True)
+            self._ipack_h[:n_int * K].copy_(self._ipack_d[:n_int * K], non_blocking=True)
+        self._st_stream.synchronize()
+        h = self._pack_h.numpy()
+        ih = self._ipack_h.numpy()
+        return (h[:K * nd].reshape(K, nd).copy(), h[K * nd:2 * K * nd].reshape(K, nd).copy(), h[2 * K * nd:n].copy()) + \
+            tuple(ih[j * K:(j + 1) * K].astype(np.int64) for j in range(n_int))
+
+    # the same in three parts (MultiPopProposer interleaves the steps of several populations)
+    def rwalk_begin(self, U, V, lnprob, axes, scale, loglstar, walks, seed, stream=None, ell=None):
+        K, pu, pv, pl, axp, n_ell, ell_p, ip, st = self._stage_chains(U, V, lnprob, axes, ell, stream)
+        rc = self.lib.payne_rwalk_begin_ell(self._handle, pu, pv, pl, K, axp, n_ell, ell_p, float(scale), float(loglstar), int(walks),
+                                            _seed64(seed), ip, ip + 4 * K, st)
         if rc != 0:
             self.eng._err(rc, "payne_rwalk_begin_ell")
-        self._run_K = K
 
     def rwalk_step(self, w):
         rc = self.lib.payne_rwalk_step(self._handle, int(w))
@@ -374,53 +409,15 @@ class DeviceProposer(object):
             self.eng._err(rc, "payne_rwalk_step")
 
     def rwalk_finish(self):
-        K, nd, t = self._run_K, self.ndim, self.torch
-        n = K * (2 * nd + 1)
-        with t.cuda.stream(self._run_stream):
-            self._pack_h[:n].copy_(self._pack_d[:n], non_blocking=True)
-            self._ipack_h[:2 * K].copy_(self._ipack_d[:2 * K], non_blocking=True)
-        self._run_stream.synchronize()
-        h = self._pack_h.numpy()
-        ih = self._ipack_h.numpy()
-        return (h[:K * nd].reshape(K, nd).copy(), h[K * nd:2 * K * nd].reshape(K, nd).copy(), h[2 * K * nd:n].copy(),
-                ih[:K].astype(np.int64), ih[K:2 * K].astype(np.int64))
+        """The chains and their counters back: (U, V, lnprob, nacc, ncall)."""
+        return self._unstage_chains(2)
 
     # ---- slice sampling on the device (payne_slice_*): the chain is a state machine there, a round is one likelihood batch
     def _slice_args(self, U, V, lnprob, axes, scale, loglstar, slices, random_dirs, seed, ell, stream):
         """Upload the chains (one packed pinned transfer) and build the argument list payne_slice_begin / _batch share."""
-        K, nd = len(U), self.ndim
-        if K > self.k_max:
-            raise ValueError("K > k_max")
-        t = self.torch
-        if getattr(self, "_sl_pack_h", None) is None:
-            n = self.k_max * (2 * nd + 1)
-            self._sl_pack_h = t.empty(n, dtype=t.float64).pin_memory()
-            self._sl_pack_d = t.empty(n, dtype=t.float64, device=self.eng.device)
-            self._sl_ipack_h = t.empty(3 * self.k_max, dtype=t.int32).pin_memory()
-            self._sl_ipack_d = t.empty(3 * self.k_max, dtype=t.int32, device=self.eng.device)
-        self._sl_stream = stream if stream is not None else t.cuda.current_stream(self.eng.device)
-        n = K * (2 * nd + 1)
-        h = self._sl_pack_h.numpy()
-        h[:K * nd] = np.asarray(U, dtype=np.float64).reshape(-1)
-        h[K * nd:2 * K * nd] = np.asarray(V, dtype=np.float64).reshape(-1)
-        h[2 * K * nd:n] = lnprob
-        d = self._sl_pack_d
-        with t.cuda.stream(self._sl_stream):
-            d[:n].copy_(self._sl_pack_h[:n], non_blocking=True)
-        ax = np.ascontiguousarray(axes, dtype=np.float64)
-        n_ell, ell_p = 1, None
-        if ax.ndim == 3:
-            n_ell = ax.shape[0]
-            if n_ell > 1:
-                self._sl_ell_h = np.ascontiguousarray(ell, dtype=np.int32)
-                if self._sl_ell_h.shape != (K,):
-                    raise ValueError("ell must name one ellipsoid per chain")
-                ell_p = self._sl_ell_h.ctypes.data
-        self._sl_ax, self._sl_K = ax, K
-        ip = self._sl_ipack_d.data_ptr()
-        return (self._handle, d.data_ptr(), d.data_ptr() + 8 * K * nd, d.data_ptr() + 16 * K * nd, K, ax.ctypes.data, n_ell, ell_p,
-                float(scale), float(loglstar), int(slices), 1 if random_dirs else 0, int(seed) & 0xFFFFFFFFFFFFFFFF,
-                ip, ip + 4 * K, ip + 8 * K, C.c_void_p(self._sl_stream.cuda_stream))
+        K, pu, pv, pl, axp, n_ell, ell_p, ip, st = self._stage_chains(U, V, lnprob, axes, ell, stream)
+        return (self._handle, pu, pv, pl, K, axp, n_ell, ell_p, float(scale), float(loglstar), int(slices), 1 if random_dirs else 0,
+                _seed64(seed), ip, ip + 4 * K, ip + 8 * K, st)
 
     def slice_begin(self, U, V, lnprob, axes, scale, loglstar, slices, random_dirs, seed, ell=None, stream=None):
         """payne_slice_begin: K lock-step slice-sampling chains under lnprob > loglstar ('slice': `slices` sweeps over the columns
@@ -439,16 +436,7 @@ class DeviceProposer(object):
 
     def slice_finish(self):
         """The chains and their counters back: (U, V, lnprob, ncall, nexpand, ncontract)."""
-        K, nd, t = self._sl_K, self.ndim, self.torch
-        n = K * (2 * nd + 1)
-        with t.cuda.stream(self._sl_stream):
-            self._sl_pack_h[:n].copy_(self._sl_pack_d[:n], non_blocking=True)
-            self._sl_ipack_h[:3 * K].copy_(self._sl_ipack_d[:3 * K], non_blocking=True)
-        self._sl_stream.synchronize()
-        h = self._sl_pack_h.numpy()
-        ih = self._sl_ipack_h.numpy()
-        return (h[:K * nd].reshape(K, nd).copy(), h[K * nd:2 * K * nd].reshape(K, nd).copy(), h[2 * K * nd:n].copy(),
-                ih[:K].astype(np.int64), ih[K:2 * K].astype(np.int64), ih[2 * K:3 * K].astype(np.int64))
+        return self._unstage_chains(3)
 
     def slice_walk(self, U, V, lnprob, axes, scale, loglstar, slices, random_dirs, seed, ell=None, chunk=16, max_rounds=None):
         """One whole slice walk in one native call (payne_slice_batch): one upload, rounds enqueued `chunk` at a time until no
@@ -472,7 +460,7 @@ class DeviceProposer(object):
                 self.torch.cuda.synchronize(self.eng.device)
             self.lib.payne_sampler_destroy(self._handle)
             self._handle = C.c_void_p()
-        if getattr(self, "_held", False):
+        if self._held:
             self._held = False
             self.eng.drop()
 
@@ -517,7 +505,7 @@ class MultiPopProposer(object):
             lo, hi = i * per, min(K, (i + 1) * per)
             if hi > lo:
                 p.rwalk_begin(U[lo:hi], V[lo:hi], lnprob[lo:hi], axes, scale, loglstar, walks,
-                              (int(seed) + 0x9E3779B9 * i) & 0xFFFFFFFFFFFFFFFF, stream=self._streams[i],
+                              _seed64(int(seed) + 0x9E3779B9 * i), stream=self._streams[i],
                               ell=None if ell is None else ell[lo:hi])
                 live.append(p)
         for w in range(int(walks) + 1):                 # one step of every population, round robin

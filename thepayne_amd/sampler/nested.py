@@ -32,6 +32,8 @@ import math
 
 import numpy as np
 
+from .device import queue_buffer
+
 __all__ = ["NestedSampler", "Results"]
 
 
@@ -150,14 +152,7 @@ class NestedSampler(object):
                 raise ValueError("live_points must be (u[nlive, ndim], v[nlive, ndim], logl[nlive])")
         else:
             self.live_u = self.rng.uniform(size=(self.nlive, self.ndim))
-        if live_points is not None:
-            pass
-        elif self.proposer is not None:
-            self.live_v, ll = self.proposer.lnprob_u(self.live_u)
-            self.live_logl = np.where(np.isnan(ll), -np.inf, ll)
-        else:
-            self.live_v = self._ptform(self.live_u)
-            self.live_logl = self._eval(self.live_v)
+            self.live_v, self.live_logl = self._eval_u(self.live_u)
         self.live_u = np.ascontiguousarray(self.live_u, dtype=np.float64)
         self.live_v = np.ascontiguousarray(self.live_v, dtype=np.float64)
         self.live_logl = np.ascontiguousarray(self.live_logl, dtype=np.float64)
@@ -231,6 +226,9 @@ class NestedSampler(object):
         self._ahead = None                         # the queue in flight: {"it", "lstar"} the consumption must arrive at, its "seed"
         self._seed_again = None                    # the seed of a queue that was dropped: the queue made in its place takes it
         self._qbufs = [None, None]
+        n, nd = self.nlive, self.ndim              # _launch_ahead: the live set the consumption will leave (payne_ns_peek writes it here)
+        self._peek = (np.empty((n, nd)), np.empty((n, nd)), np.empty(n)) if self.pipeline else None
+        self._dev_epoch = None                     # pipeline='device': the proposer's queue_dev_init this sampler's queues belong to
         self._cycle = 0                            # queues filled so far
         self._last_m = 0                           # dead points the last consumed queue gave
         self._m_acc = 0
@@ -309,8 +307,7 @@ class NestedSampler(object):
 
     # ---- proposal generation: fills the queue with batched evaluations -------------------
     def _clear_queue(self):
-        nd = self.ndim
-        self._q_assign(np.empty((0, nd)), np.empty((0, nd)), np.empty(0), np.empty(0, dtype=np.int32))
+        self._q_assign(*queue_buffer(0, self.ndim))
 
     def _set_queue(self, U, V, ll, nc):
         self._q_assign(np.ascontiguousarray(U, dtype=np.float64), np.ascontiguousarray(V, dtype=np.float64),
@@ -322,87 +319,104 @@ class NestedSampler(object):
         self._q_addr = tuple(a.__array_interface__['data'][0] for a in (U, V, ll, nc))
 
     def _fill_queue(self):
-        K, nd, rng = self.queue_size, self.ndim, self.rng
-        lstar = self.loglstar
         if self._axes is None and not (self.bound == 'none' and self.method == 'unif'):
             self._update_bound()
         if self.method == 'unif':
-            if self.bound == 'none':
-                U = rng.uniform(size=(K, nd))
-            elif len(self._ells) == 1:
-                U = self._ctr + _unit_ball(rng, K, nd) @ self._axes.T
-            else:                          # uniform in the union: volume-weighted choice, 1/q thinning of overlaps
-                E = self._ells
-                lv = np.array([e.logvol for e in E])
-                pick = rng.choice(len(E), size=K, p=np.exp(lv - lv.max()) / np.exp(lv - lv.max()).sum())
-                ball = _unit_ball(rng, K, nd)
-                U = np.stack([e.ctr for e in E])[pick] + np.einsum('kij,kj->ki', np.stack([e.axes for e in E])[pick], ball)
-                q = np.sum([e.dist2(U) <= 1.0 for e in E], axis=0)
-                U = U[rng.uniform(size=K) * np.maximum(q, 1) < 1.0]
-            inside = np.all((U > 0.0) & (U < 1.0), axis=1)
-            U = U[inside]
-            nin = len(U)
-            if nin:
-                if self.proposer is not None:
-                    V, ll = self.proposer.lnprob_u(U)
-                    ll = np.where(np.isnan(ll), -np.inf, ll)
-                else:
-                    V = self._ptform(U)
-                    ll = self._eval(V)
-                self._set_queue(U, V, ll, np.ones(nin, dtype=np.int32))
-            else:
-                self._clear_queue()
-                self._update_bound()
-            self.ncall += nin
-            return
+            return self._fill_queue_unif()
         self._cycle += 1
         self._last_m, self._m_acc = self._m_acc, 0
         if self.method == 'rwalk' and self._dev_turn:
             return self._fill_queue_dev()
         if self.method == 'rwalk' and hasattr(self.proposer, "rwalk_queue"):
-            # the whole queue in one native call: start points, ellipsoid assignment, transfers, walk, selection
-            # (two host buffers in turn: the queue launched ahead is collected while the one before may still hold proposals)
-            self._qbufs.reverse()
-            if self._qbufs[0] is None or len(self._qbufs[0][2]) < K:
-                self._qbufs[0] = (np.empty((K, nd)), np.empty((K, nd)), np.empty(K), np.empty(K, dtype=np.int32))
-            self._qbuf = self._qbufs[0]
-            res = None
-            if self._ahead is not None:                                      # launched before the last queue was consumed
-                ok = self.it == self._ahead["it"] and self.loglstar == self._ahead["lstar"]
-                seed, self._ahead = self._ahead["seed"], None
-                if ok and self._use_turn:
-                    # collected, and the next one launched from the state ITS consumption will leave, in one native call
-                    seed = self._queue_seed()
-                    ctr, au, ai = self._ell_stack
-                    nq, acc, calls, redrawn, idle, self.scale, lnext, m = self.proposer.rwalk_queue_turn(
-                        self._qbuf, self.live_u, self.live_v, self.live_logl, K, self._ax_arg, ctr, ai, self.scale, lstar,
-                        self.walks, seed)
-                    self.ncall += calls
-                    self._pending_nc += idle
-                    qU, qV, ql, qnc = self._qbuf
-                    self._q_assign(qU[:nq], qV[:nq], ql[:nq], qnc[:nq])
-                    self._ahead = {"it": self.it + m, "lstar": lnext if m else self.loglstar, "seed": seed}
-                    return
-                res = self.proposer.rwalk_queue_end(self._qbuf)              # (collected either way: the stream must drain)
-                if not ok:
-                    res, self._seed_again = None, seed
-            if res is None:
+            return self._fill_queue_host_turn()
+        return self._fill_queue_chains()
+
+    def _next_qbuf(self):
+        """The host buffer the next queue is collected into (two in turn: the queue launched ahead is collected while the one before
+        may still hold proposals)."""
+        K = self.queue_size
+        self._qbufs.reverse()
+        if self._qbufs[0] is None or len(self._qbufs[0][2]) < K:
+            self._qbufs[0] = queue_buffer(K, self.ndim)
+        self._qbuf = self._qbufs[0]
+
+    def _adapt_scale(self, frac, scale=None):
+        """dynesty-like scale adaptation towards 50 % acceptance, from `scale` (default: the current one), kept in [1e-4, 4]."""
+        base = self.scale if scale is None else scale
+        self.scale = min(max(base * math.exp((frac - 0.5) / self.ndim / 0.5), 1e-4), 4.0)
+
+    def _fill_queue_unif(self):
+        """Uniform in the bound (the cube, one ellipsoid, or the union of several), one batch."""
+        K, nd, rng = self.queue_size, self.ndim, self.rng
+        if self.bound == 'none':
+            U = rng.uniform(size=(K, nd))
+        elif len(self._ells) == 1:
+            U = self._ctr + _unit_ball(rng, K, nd) @ self._axes.T
+        else:                          # uniform in the union: volume-weighted choice, 1/q thinning of overlaps
+            E = self._ells
+            lv = np.array([e.logvol for e in E])
+            pick = rng.choice(len(E), size=K, p=np.exp(lv - lv.max()) / np.exp(lv - lv.max()).sum())
+            ball = _unit_ball(rng, K, nd)
+            U = np.stack([e.ctr for e in E])[pick] + np.einsum('kij,kj->ki', np.stack([e.axes for e in E])[pick], ball)
+            q = np.sum([e.dist2(U) <= 1.0 for e in E], axis=0)
+            U = U[rng.uniform(size=K) * np.maximum(q, 1) < 1.0]
+        inside = np.all((U > 0.0) & (U < 1.0), axis=1)
+        U = U[inside]
+        nin = len(U)
+        if nin:
+            V, ll = self._eval_u(U)
+            self._set_queue(U, V, ll, np.ones(nin, dtype=np.int32))
+        else:
+            self._clear_queue()
+            self._update_bound()
+        self.ncall += nin
+
+    def _take_queue(self, nq):
+        """The first nq proposals of the buffer just written are the queue."""
+        qU, qV, ql, qnc = self._qbuf
+        self._q_assign(qU[:nq], qV[:nq], ql[:nq], qnc[:nq])
+
+    def _fill_queue_host_turn(self):
+        """The whole queue in one native call (start points, ellipsoid assignment, transfers, walk, selection), the turn between
+        two queues on the host; with pipeline, the next queue is launched ahead of this one's consumption."""
+        K, lstar = self.queue_size, self.loglstar
+        self._next_qbuf()
+        res = None
+        if self._ahead is not None:                                      # launched before the last queue was consumed
+            ok = self.it == self._ahead["it"] and self.loglstar == self._ahead["lstar"]
+            seed, self._ahead = self._ahead["seed"], None
+            if ok and self._use_turn:
+                # collected, and the next one launched from the state ITS consumption will leave, in one native call
+                seed = self._queue_seed()
                 ctr, au, ai = self._ell_stack
-                res = self.proposer.rwalk_queue(
-                    self.live_u, self.live_v, self.live_logl, K, self._ax_arg, ctr, ai, self.scale, lstar,
-                    self.walks, self._queue_seed(), self._qbuf,
-                    **({"between": self._prefetch_bound} if self.overlap_bound and not self.pipeline else {}))
-            nq, acc, calls, redrawn, idle = res
-            self.ncall += calls
-            frac = acc / max(1, calls + redrawn)          # a redrawn (out-of-cube) proposal counts as a rejection (dynesty)
-            self.scale = min(max(self.scale * math.exp((frac - 0.5) / nd / 0.5), 1e-4), 4.0)
-            self._pending_nc += idle
-            qU, qV, ql, qnc = self._qbuf
-            self._q_assign(qU[:nq], qV[:nq], ql[:nq], qnc[:nq])
-            if self.pipeline:
-                self._launch_ahead()
-            return
-        # rwalk / slice: K lock-step chains
+                nq, acc, calls, redrawn, idle, self.scale, lnext, m = self.proposer.rwalk_queue_turn(
+                    self._qbuf, self.live_u, self.live_v, self.live_logl, K, self._ax_arg, ctr, ai, self.scale, lstar,
+                    self.walks, seed)
+                self.ncall += calls
+                self._pending_nc += idle
+                self._take_queue(nq)
+                self._ahead = {"it": self.it + m, "lstar": lnext if m else self.loglstar, "seed": seed}
+                return
+            res = self.proposer.rwalk_queue_end(self._qbuf)              # (collected either way: the stream must drain)
+            if not ok:
+                res, self._seed_again = None, seed
+        if res is None:
+            ctr, au, ai = self._ell_stack
+            res = self.proposer.rwalk_queue(
+                self.live_u, self.live_v, self.live_logl, K, self._ax_arg, ctr, ai, self.scale, lstar,
+                self.walks, self._queue_seed(), self._qbuf,
+                **({"between": self._prefetch_bound} if self.overlap_bound and not self.pipeline else {}))
+        nq, acc, calls, redrawn, idle = res
+        self.ncall += calls
+        self._adapt_scale(acc / max(1, calls + redrawn))     # a redrawn (out-of-cube) proposal counts as a rejection (dynesty)
+        self._pending_nc += idle
+        self._take_queue(nq)
+        if self.pipeline:
+            self._launch_ahead()
+
+    def _fill_queue_chains(self):
+        """rwalk / slice: K lock-step chains from random live points (the proposer's rwalk, or numpy)."""
+        K, nd, rng, lstar = self.queue_size, self.ndim, self.rng, self.loglstar
         start = rng.integers(0, self.nlive, size=K)
         U, V, ll = self.live_u[start].copy(), self.live_v[start].copy(), self.live_logl[start].copy()
         if self.method in ('slice', 'rslice'):
@@ -438,21 +452,15 @@ class NestedSampler(object):
                 U[idx], V[idx], ll[idx] = prop[idx], pv[ok], pl[ok]
                 nacc[idx] += 1
         self.ncall += int(ncalls.sum())
-        frac = nacc.sum() / max(1, ncalls.sum())
-        # dynesty-like scale adaptation towards 50 % acceptance
-        self.scale *= math.exp((frac - 0.5) / nd / 0.5)
-        self.scale = min(max(self.scale, 1e-4), 4.0)
+        self._adapt_scale(nacc.sum() / max(1, ncalls.sum()))
         moved = nacc > 0                                      # a chain that never moved is a copy of a live point
         self._pending_nc += int(ncalls[~moved].sum())
         self._set_queue(U[moved], V[moved], ll[moved], np.maximum(1, ncalls[moved]))
 
     def _fill_queue_dev(self, again=True):
         """pipeline='device': keep one queue enqueued behind the one being collected; the device makes the turn between them."""
-        K, nd, prop = self.queue_size, self.ndim, self.proposer
-        self._qbufs.reverse()
-        if self._qbufs[0] is None or len(self._qbufs[0][2]) < K:
-            self._qbufs[0] = (np.empty((K, nd)), np.empty((K, nd)), np.empty(K), np.empty(K, dtype=np.int32))
-        self._qbuf = self._qbufs[0]
+        K, prop = self.queue_size, self.proposer
+        self._next_qbuf()
         ctr, au, ai = self._ell_stack
         if not self._dev_sync:                     # the first queue of a loop (or after a mismatch): from the host's live set
             self._dev_epoch = prop.queue_dev_init(self.live_u, self.live_v, self.live_logl, self.scale, self.loglstar)
@@ -480,20 +488,17 @@ class NestedSampler(object):
                                    % (ls_used, self.loglstar, float(self.live_logl.min())))
             self._qbufs.reverse()
             return self._fill_queue_dev(again=False)
-        frac = acc / max(1, calls + redrawn)
-        self.scale = min(max(sc_used * math.exp((frac - 0.5) / nd / 0.5), 1e-4), 4.0)     # (what the device's turn computed too)
+        self._adapt_scale(acc / max(1, calls + redrawn), sc_used)     # (what the device's turn computed too)
         self._pending_nc += idle
-        qU, qV, ql, qnc = self._qbuf
-        self._q_assign(qU[:nq], qV[:nq], ql[:nq], qnc[:nq])
+        self._take_queue(nq)
 
     def _dev_drain(self):
         """Collect and discard the queues still in flight; the device's live set no longer counts."""
-        K, nd = self.queue_size, self.ndim
-        scratch = (np.empty((K, nd)), np.empty((K, nd)), np.empty(K), np.empty(K, dtype=np.int32))
+        scratch = queue_buffer(self.queue_size, self.ndim)
         closed = not getattr(getattr(self.proposer, "_handle", None), "value", True)   # (closed before an abandoned generator was finalised)
         # (... or re-initialised since by another sampler on the same proposer -- the dynamic sampler shares one across its runs --:
         #  that init collected and dropped what was in flight; what is in flight now is not ours)
-        if getattr(self, "_dev_epoch", None) is not None and getattr(self.proposer, "_dq_epoch", self._dev_epoch) != self._dev_epoch:
+        if self._dev_epoch is not None and getattr(self.proposer, "_dq_epoch", self._dev_epoch) != self._dev_epoch:
             closed = True
         while self._dev_inflight > 0:
             if not closed:                         # any other failure is an error: the C side would still count the queue as in flight
@@ -504,8 +509,6 @@ class NestedSampler(object):
     def _launch_ahead(self):
         """The next queue, launched from the state the consumption of the current one will leave (payne_ns_peek)."""
         K, nd, n = self.queue_size, self.ndim, self.nlive
-        if getattr(self, "_peek", None) is None:
-            self._peek = (np.empty((n, nd)), np.empty((n, nd)), np.empty(n))
         pu, pv, pl = self._peek
         lstar, m = C.c_double(self.loglstar), C.c_int(0)
         lu, lv, lll, _ = self._live_addr()
@@ -531,12 +534,9 @@ class NestedSampler(object):
             self._dev_drain()
         if self._ahead is not None:
             self._seed_again, self._ahead = self._ahead["seed"], None
-            self._qbufs.reverse()
-            if self._qbufs[0] is None:
-                K, nd = self.queue_size, self.ndim
-                self._qbufs[0] = (np.empty((K, nd)), np.empty((K, nd)), np.empty(K), np.empty(K, dtype=np.int32))
+            self._next_qbuf()
             try:
-                self.proposer.rwalk_queue_end(self._qbufs[0])
+                self.proposer.rwalk_queue_end(self._qbuf)
             except Exception:                  # (a proposer closed before an abandoned generator was finalised: nothing to collect)
                 pass
             self._qbufs.reverse()
