@@ -17,7 +17,7 @@ __abspath__ = _impl.__path__[0] + "/"          # the reference's install-time co
 
 _MODULES = ["fitting", "fitting.fitstar", "fitting.likelihood", "fitting.prior", "fitting.genmod", "fitting.fitutils",
             "fitting.advancedpriors", "predict", "predict.ystpred", "predict.predictspec", "predict.predictsed",
-            "predict.photANN", "predict.highred", "utils", "utils.smoothing", "testing", "testing.testspec"]
+            "predict.photANN", "predict.photANN_new", "predict.highred", "utils", "utils.smoothing", "testing", "testing.testspec"]
 for _m in _MODULES:
     try:
         _mod = importlib.import_module("thepayne_amd." + _m)

@@ -283,6 +283,50 @@ int payne_chisq_below(int device, const float* rows, int ld, int n, int G, const
 int payne_mad_stats(int device, const float* pred, int ld_pred, const float* truth, int ld_truth, int N, int P,
                     const unsigned char* groups, int G, double* pix_med, double* row_med, void* stream);
 
+/* ---- photometric LayerNorm + SiLU networks: Payne/predict/photANN_new.py (MLP_v0 / MLP_v1 of Payne/train/NNmodels_new.py) ----
+ * One network maps D_in labels to D_out bands through n_layers Linear layers; every layer but the last is followed by
+ * nn.LayerNorm over its true width (mean, biased variance about that mean, eps = 1e-5, gain and bias per column) and SiLU,
+ * z / (1 + exp(-z)).  All arithmetic of the network is fp32 (products on the fp32 matrix instruction, an fp32 fmaf chain per
+ * output); one launch evaluates every layer for a tile of 64 rows (csrc/k_lnmlp.hip, csrc/lnmlp_core.hpp).
+ * payne_lnmlp_create: every pointer of the descriptor is a HOST pointer; the arrays are copied (the weights re-ordered and
+ * padded) to `device`.  layers[i].w is row-major fp32 [n_out][n_in] (torch's Linear.weight), b fp32 [n_out], ln_gain / ln_bias
+ * fp32 [n_out] on every layer but the last, where both are NULL.  in_mid / in_std fp64 [D_in] (both or neither): the input is
+ * (x - mid) / std in fp64, rounded once to fp32; without them x itself rounded to fp32.  out_mid / out_std fp64 [D_out] (both
+ * or neither): the output is y * std + mid in fp64, rounded once to fp32.
+ *   PAYNE_E_INVALID      null desc / out, a width < 1, n_in of a layer != n_out of the one before, null w / b, a hidden layer
+ *                        without ln_gain / ln_bias, an output layer with them, one of a mid / std pair without the other
+ *   PAYNE_E_UNSUPPORTED  n_layers outside 2..8, D_in > 32, a hidden width or D_out > 512
+ * payne_lnmlp_eval: x_dev DEVICE fp64 [N][ld_x] (D_in columns read), y_dev DEVICE fp32 [N][ld_y] (D_out columns written;
+ * nothing beyond them, nothing beyond N rows).  The launch is enqueued on `stream`; the call does not wait for it.  No
+ * atomics, no order that depends on timing: the same input gives the same bits.  N == 0 succeeds and launches nothing.
+ *   PAYNE_E_INVALID      null handle, N < 0, null x_dev / y_dev with N > 0, ld_x < D_in, ld_y < D_out */
+#define PAYNE_LNMLP_MAX_LAYERS 8
+#define PAYNE_LNMLP_MAX_IN 32
+#define PAYNE_LNMLP_MAX_WIDTH 512
+
+typedef struct payne_lnmlp_layer {
+  int n_in, n_out;
+  const float* w;
+  const float* b;
+  const float* ln_gain; /* NULL on the output layer */
+  const float* ln_bias; /* NULL on the output layer */
+} payne_lnmlp_layer;
+
+typedef struct payne_lnmlp_desc {
+  int n_layers;
+  payne_lnmlp_layer layers[PAYNE_LNMLP_MAX_LAYERS];
+  const double* in_mid;
+  const double* in_std;
+  const double* out_mid;
+  const double* out_std;
+} payne_lnmlp_desc;
+
+typedef struct payne_lnmlp payne_lnmlp;
+
+int payne_lnmlp_create(int device, const payne_lnmlp_desc* desc, payne_lnmlp** out);
+int payne_lnmlp_eval(payne_lnmlp* h, const double* x_dev, int ld_x, int N, float* y_dev, int ld_y, void* stream);
+void payne_lnmlp_destroy(payne_lnmlp* h);
+
 /* Magnitudes for B parameter vectors: FastPayneSEDPredict.sed
  * (Payne/predict/predictsed.py:75-103).  pars: device fp64 [B][9] =
  * logt, logg, feh, afe, av, rv, logl, dist, logA  (NaN = kwarg absent; the

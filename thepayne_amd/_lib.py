@@ -34,7 +34,8 @@ SYMBOLS = ["payne_version", "payne_ctx_create", "payne_ctx_set_obs", "payne_ctx_
            "payne_rwalk_batch", "payne_rwalk_begin", "payne_rwalk_begin_ell", "payne_rwalk_step", "payne_sampler_counters", "payne_ns_rwalk_queue", "payne_ns_rwalk_queue_begin", "payne_ns_rwalk_queue_end", "payne_ns_rwalk_queue_turn", "payne_ns_consume", "payne_ns_peek", "payne_ns_bound", "payne_format_rows",
            "payne_ns_queue_dev_init", "payne_ns_queue_dev_launch", "payne_ns_queue_dev_collect",
            "payne_slice_begin", "payne_slice_rounds", "payne_slice_batch",
-           "payne_rv_scan", "payne_chisq_below", "payne_mad_stats"]
+           "payne_rv_scan", "payne_chisq_below", "payne_mad_stats",
+           "payne_lnmlp_create", "payne_lnmlp_eval", "payne_lnmlp_destroy"]
 
 PAYNE_MAX_DIM, PAYNE_MAX_FIXED = 24, 16
 PRIOR_UNIFORM, PRIOR_GAUSSIAN, PRIOR_TGAUSSIAN, PRIOR_EXP, PRIOR_TEXP, PRIOR_LOGUNIFORM, PRIOR_TABLE = range(7)
@@ -60,6 +61,16 @@ class PhotDesc(C.Structure):
                 ("w1", C.c_void_p), ("b1", C.c_void_p), ("w2", C.c_void_p), ("b2", C.c_void_p),
                 ("w3", C.c_void_p), ("b3", C.c_void_p),
                 ("xmin", _dp), ("xmax", _dp), ("hiav", _dp), ("obs_mag", _dp), ("obs_err", _dp)]
+
+
+class LnmlpLayer(C.Structure):
+    _fields_ = [("n_in", C.c_int), ("n_out", C.c_int), ("w", C.c_void_p), ("b", C.c_void_p),
+                ("ln_gain", C.c_void_p), ("ln_bias", C.c_void_p)]
+
+
+class LnmlpDesc(C.Structure):
+    _fields_ = [("n_layers", C.c_int), ("layers", LnmlpLayer * PAYNE_MAX_LAYERS),
+                ("in_mid", C.c_void_p), ("in_std", C.c_void_p), ("out_mid", C.c_void_p), ("out_std", C.c_void_p)]
 
 
 class Opts(C.Structure):
@@ -156,6 +167,12 @@ def load(path=None):
     lib.payne_mad_stats.argtypes = [C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int,
                                     C.c_void_p, C.c_void_p, C.c_void_p]
     lib.payne_mad_stats.restype = C.c_int
+    lib.payne_lnmlp_create.argtypes = [C.c_int, C.POINTER(LnmlpDesc), C.POINTER(ctxp)]
+    lib.payne_lnmlp_create.restype = C.c_int
+    lib.payne_lnmlp_eval.argtypes = [ctxp, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p]
+    lib.payne_lnmlp_eval.restype = C.c_int
+    lib.payne_lnmlp_destroy.argtypes = [ctxp]
+    lib.payne_lnmlp_destroy.restype = None
     lib.payne_ctx_destroy.argtypes = [ctxp]
     lib.payne_ctx_destroy.restype = None
     lib.payne_last_error.argtypes = [ctxp]

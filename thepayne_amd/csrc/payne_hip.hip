@@ -40,6 +40,7 @@ using namespace payne;
 
 #include "sed_kernel.hpp"
 #include "select.hpp"
+#include "lnmlp_core.hpp"
 
 // photometry-only fits: lnL = -0.5 chi2_sed
 __global__ void payne_photonly_kernel(const double* mags, const double* obs, const double* err, int F, int B, double* lnl) {
@@ -2060,6 +2061,109 @@ extern "C" int payne_bc_batch(payne_ctx* c, const double* x, int B, double* bc, 
   if (rc) return rc;
   if (!c->has_phot) return fail(c, PAYNE_E_INVALID, "context has no photometric model");
   return run_sed(c, x, 6, 2, B, bc, reinterpret_cast<hipStream_t>(stream));
+}
+
+// ---- photometric LayerNorm + SiLU networks (photANN_new): the handle; the kernel is k_lnmlp.hip ---------------------------
+int payne_lnmlp_launch(const payne::lnmlp::NetArgs& net, const double* x, int ld_x, int N, float* y, int ld_y, void* stream);
+
+struct payne_lnmlp {
+  int device = 0;
+  payne::lnmlp::NetArgs net{};
+  std::vector<void*> owned;
+};
+
+extern "C" void payne_lnmlp_destroy(payne_lnmlp* h) {
+  if (!h) return;
+  int prev = 0;
+  (void)hipGetDevice(&prev);
+  if (hipSetDevice(h->device) == hipSuccess)
+    for (void* p : h->owned) (void)hipFree(p);
+  (void)hipSetDevice(prev);
+  delete h;
+}
+
+extern "C" int payne_lnmlp_create(int device, const payne_lnmlp_desc* d, payne_lnmlp** out) {
+  namespace ln = payne::lnmlp;
+  static_assert(PAYNE_LNMLP_MAX_LAYERS == ln::kMaxLayers && PAYNE_LNMLP_MAX_IN == ln::kMaxIn && PAYNE_LNMLP_MAX_WIDTH == ln::kMaxWidth,
+                "payne_hip.h and lnmlp_core.hpp disagree on the limits");
+  if (!d || !out) return fail(nullptr, PAYNE_E_INVALID, "payne_lnmlp_create: null descriptor or handle pointer");
+  *out = nullptr;
+  if (d->n_layers < 2 || d->n_layers > ln::kMaxLayers) return fail(nullptr, PAYNE_E_UNSUPPORTED, "payne_lnmlp_create: 2 to 8 linear layers");
+  for (int l = 0; l < d->n_layers; ++l) {
+    const payne_lnmlp_layer& L = d->layers[l];
+    const bool last = l + 1 == d->n_layers;
+    if (L.n_in < 1 || L.n_out < 1 || !L.w || !L.b || (l > 0 && L.n_in != d->layers[l - 1].n_out))
+      return fail(nullptr, PAYNE_E_INVALID, "payne_lnmlp_create: layer " + std::to_string(l) + ": bad widths or null weights");
+    if (last ? (L.ln_gain || L.ln_bias) : (!L.ln_gain || !L.ln_bias))
+      return fail(nullptr, PAYNE_E_INVALID, "payne_lnmlp_create: LayerNorm gain and bias on every layer but the last");
+  }
+  if (!d->in_mid != !d->in_std || !d->out_mid != !d->out_std)
+    return fail(nullptr, PAYNE_E_INVALID, "payne_lnmlp_create: a normalisation needs both mid and std");
+  if (d->layers[0].n_in > ln::kMaxIn) return fail(nullptr, PAYNE_E_UNSUPPORTED, "payne_lnmlp_create: more than 32 inputs");
+  for (int l = 0; l < d->n_layers; ++l)
+    if (d->layers[l].n_out > ln::kMaxWidth) return fail(nullptr, PAYNE_E_UNSUPPORTED, "payne_lnmlp_create: a width above 512");
+
+  int prev = 0;
+  (void)hipGetDevice(&prev);
+  if (hipSetDevice(device) != hipSuccess) return fail(nullptr, PAYNE_E_HIP, "payne_lnmlp_create: hipSetDevice");
+  payne_lnmlp* h = new payne_lnmlp;
+  h->device = device;
+  bool ok = true;
+  auto upload = [&](const void* src, size_t bytes) -> void* {
+    void* p = nullptr;
+    if (!ok || hipMalloc(&p, bytes) != hipSuccess) { ok = false; return nullptr; }
+    h->owned.push_back(p);
+    if (hipMemcpy(p, src, bytes, hipMemcpyHostToDevice) != hipSuccess) ok = false;
+    return p;
+  };
+  auto padded = [&](const float* src, int n, int n_pad) {
+    std::vector<float> v((size_t)n_pad, 0.0f);
+    memcpy(v.data(), src, (size_t)n * sizeof(float));
+    return static_cast<const float*>(upload(v.data(), v.size() * sizeof(float)));
+  };
+  h->net.n_layers = d->n_layers;
+  for (int l = 0; l < d->n_layers; ++l) {
+    const payne_lnmlp_layer& L = d->layers[l];
+    ln::LayerArgs& A = h->net.L[l];
+    const int n_pad = ln::col_tiles(L.n_out) * ln::kTile;
+    std::vector<float> pk(ln::packed_floats(L.n_in, L.n_out));
+    ln::pack_weights(L.w, L.n_in, L.n_out, pk.data());
+    A.w = static_cast<const float*>(upload(pk.data(), pk.size() * sizeof(float)));
+    A.b = padded(L.b, L.n_out, n_pad);
+    A.gain = L.ln_gain ? padded(L.ln_gain, L.n_out, n_pad) : nullptr;
+    A.beta = L.ln_bias ? padded(L.ln_bias, L.n_out, n_pad) : nullptr;
+    A.n_in = L.n_in;
+    A.n_out = L.n_out;
+  }
+  const int d_in = d->layers[0].n_in, d_out = d->layers[d->n_layers - 1].n_out;
+  if (d->in_mid) {
+    h->net.in_mid = static_cast<const double*>(upload(d->in_mid, (size_t)d_in * sizeof(double)));
+    h->net.in_std = static_cast<const double*>(upload(d->in_std, (size_t)d_in * sizeof(double)));
+  }
+  if (d->out_mid) {
+    h->net.out_mid = static_cast<const double*>(upload(d->out_mid, (size_t)d_out * sizeof(double)));
+    h->net.out_std = static_cast<const double*>(upload(d->out_std, (size_t)d_out * sizeof(double)));
+  }
+  (void)hipSetDevice(prev);
+  if (!ok) {
+    payne_lnmlp_destroy(h);
+    return fail(nullptr, PAYNE_E_HIP, "payne_lnmlp_create: copying the network to the device failed");
+  }
+  *out = h;
+  return PAYNE_OK;
+}
+
+extern "C" int payne_lnmlp_eval(payne_lnmlp* h, const double* x_dev, int ld_x, int N, float* y_dev, int ld_y, void* stream) {
+  if (!h || N < 0) return PAYNE_E_INVALID;
+  if (ld_x < h->net.L[0].n_in || ld_y < h->net.L[h->net.n_layers - 1].n_out) return PAYNE_E_INVALID;
+  if (N == 0) return PAYNE_OK;
+  if (!x_dev || !y_dev) return PAYNE_E_INVALID;
+  int prev = 0;
+  (void)hipGetDevice(&prev);
+  if (hipSetDevice(h->device) != hipSuccess) return PAYNE_E_HIP;
+  const int rc = payne_lnmlp_launch(h->net, x_dev, ld_x, N, y_dev, ld_y, stream);
+  (void)hipSetDevice(prev);
+  return rc;
 }
 
 // ---- per-kernel timing ---------------------------------------------------------

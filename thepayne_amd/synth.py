@@ -150,6 +150,51 @@ def make_phot_nets(filters=PHOT_FILTERS, H=64, seed=1):
     }
 
 
+PHOT_MLP_LABELS = ['teff', 'logg', 'feh', 'afe', 'av', 'rv']
+
+
+def phot_mlp(path=None, nntype='MLP_v0', D_in=6, H=(256, 256, 256), D_out=8, seed=0):
+    """Random photometric LayerNorm + SiLU network with the reference's key names (Payne/train/NNmodels_new.py as
+    trainphot.py stores it, read by Payne/predict/photANN_new.py): ``model/mlp.lin<i>.{weight,bias}``,
+    ``model/mlp.ln<i>.{weight,bias}``, the output layer ``lin6`` (MLP_v0: five blocks of widths H1, H2, H3, H3, H3) or
+    ``linout`` (MLP_v1: three blocks), ``label_i``, ``label_o`` and one (mid, std) pair per label under ``norm_i/`` and
+    ``norm_o/``.  Linear layers are drawn as torch draws them, U(+-1/sqrt(n_in)); the LayerNorm gains are 1 + N(0, 0.3) and
+    its biases N(0, 0.3), so that neither can be dropped unnoticed.  Returns the arrays; with `path`, also writes the
+    ``.npz`` file."""
+    rng = np.random.default_rng(seed)
+    H1, H2, H3 = H
+    if nntype == 'MLP_v0':
+        widths, out_name = [H1, H2, H3, H3, H3], 'lin6'
+    elif nntype == 'MLP_v1':
+        widths, out_name = [H1, H2, H3], 'linout'
+    else:
+        raise ValueError(nntype)
+    net = {}
+
+    def lin(name, n_out, n_in):
+        k = 1.0 / np.sqrt(n_in)
+        net['model/mlp.%s.weight' % name] = rng.uniform(-k, k, (n_out, n_in)).astype(np.float32)
+        net['model/mlp.%s.bias' % name] = rng.uniform(-k, k, n_out).astype(np.float32)
+    n_in = D_in
+    for i, w in enumerate(widths, start=1):
+        lin('lin%d' % i, w, n_in)
+        net['model/mlp.ln%d.weight' % i] = (1.0 + rng.normal(0, 0.3, w)).astype(np.float32)
+        net['model/mlp.ln%d.bias' % i] = rng.normal(0, 0.3, w).astype(np.float32)
+        n_in = w
+    lin(out_name, D_out, n_in)
+    label_i = [PHOT_MLP_LABELS[i] if i < len(PHOT_MLP_LABELS) else 'par%d' % i for i in range(D_in)]
+    label_o = [PHOT_FILTERS[i] if i < len(PHOT_FILTERS) else 'band%d' % i for i in range(D_out)]
+    net['label_i'] = np.array([s.encode('utf-8') for s in label_i])
+    net['label_o'] = np.array([s.encode('utf-8') for s in label_o])
+    for kk in label_i:
+        net['norm_i/' + kk] = np.array([rng.normal(0, 2.0), rng.uniform(0.5, 3.0)])
+    for kk in label_o:
+        net['norm_o/' + kk] = np.array([rng.normal(5.0, 3.0), rng.uniform(0.5, 4.0)])
+    if path is not None:
+        np.savez(path, **net)
+    return net
+
+
 TRUTH = dict(Teff=5770.0, logg=4.44, feh=0.0, afe=0.0, vrad=10.0, vrot=3.0, inst_R=28800.0)
 
 
