@@ -327,6 +327,61 @@ int payne_lnmlp_create(int device, const payne_lnmlp_desc* desc, payne_lnmlp** o
 int payne_lnmlp_eval(payne_lnmlp* h, const double* x_dev, int ld_x, int N, float* y_dev, int ld_y, void* stream);
 void payne_lnmlp_destroy(payne_lnmlp* h);
 
+/* ---- training those networks: Payne/train/trainphot.py (TrainMod.train_mod) on MLP_v0 / MLP_v1 of Payne/train/NNmodels_new.py ----
+ * One step is trainphot.py:411-447: the forward in training mode (the dropout of NNmodels_new.py:21 / :48 from a counter-based
+ * mask), MSELoss(reduction='mean') (:343), backward, torch.optim.RAdam(lr) with its defaults (:353).  All arithmetic of the
+ * network, the backward and the update is fp32 (products on the fp32 matrix instruction); the loss is the fp32 residuals
+ * squared and summed in fp64.  Three launches a step (csrc/k_lnmlp_train.hip, csrc/lnmlp_train_core.hpp), no atomics: the same
+ * parameters, batch, seed and step counter give the same bits for loss, gradients and updated parameters.  With every
+ * dropout_p = 0 the handle's forward returns payne_lnmlp_eval's bits on the same parameters.  A handle is used from one stream
+ * at a time.
+ * payne_lnmlp_train_create: `init` as for payne_lnmlp_create (HOST pointers, row-major weights) = the initial parameters, or a
+ * restart file's (trainphot.py:278-292); opts: RAdam's lr, beta1, beta2, eps (torch's defaults: 1e-3, 0.9, 0.999, 1e-8),
+ * dropout_p[i] the probability behind hidden block i (0 = none; MLP_v0: p[2] = 0.3, MLP_v1: p[1] = 0.01), the mask's seed, and
+ * max_rows, the largest batch of a step; the workspace (activations and gradients of max_rows rows) is allocated here.
+ *   PAYNE_E_INVALID      what payne_lnmlp_create rejects; in_mid / in_std / out_mid / out_std not NULL (training data arrive
+ *                        normalised, as ReadPhot(norm=True) hands them over); null opts; a dropout_p outside [0, 1); max_rows < 1;
+ *                        lr <= 0, a beta outside [0, 1), eps < 0
+ *   PAYNE_E_UNSUPPORTED  n_layers outside 2..8, D_in > 32, a hidden width or D_out > 512
+ * payne_lnmlp_train_step: one forward / backward / update on x_dev DEVICE fp32 [N][ld_x] (D_in columns read) and t_dev DEVICE
+ * fp32 [N][ld_t] (D_out columns read), 1 <= N <= max_rows (trainphot.py:428-443).  loss_dev: DEVICE double, the loss before the
+ * update (:431), or NULL.  Enqueued on `stream`; the call does not wait.  N == 0 succeeds and does nothing.
+ *   PAYNE_E_INVALID      null handle, N < 0, N > max_rows, null x_dev / t_dev with N > 0, ld_x < D_in, ld_t < D_out
+ * payne_lnmlp_train_loss: the loss in evaluation mode (trainphot.py:456-476): no dropout, no parameter, optimiser state or step
+ * counter changes.  N may exceed max_rows (evaluated in chunks).  Enqueued; does not wait.  N == 0 succeeds, writes nothing.
+ *   PAYNE_E_INVALID      as payne_lnmlp_train_step without the limit on N; null loss_dev with N > 0
+ * payne_lnmlp_train_get: what = PAYNE_LNMLP_PARAMS (the current parameters, model.state_dict() of trainphot.py:511-519) or
+ * PAYNE_LNMLP_GRADS (the gradients of the last step), copied row-major into the HOST arrays host_out's pointers name (same
+ * widths as `init`; the norm pointers are ignored).  Waits for the work enqueued through the handle.
+ *   PAYNE_E_INVALID      null handle / host_out, another `what`, n_layers or a width differing from the handle's, a null array
+ * payne_lnmlp_train_steps: the number of steps taken (RAdam's t; the mask of the next step uses this value); -1 for NULL.
+ * payne_lnmlp_train_destroy: NULL is allowed.
+ * payne_lnmlp_dropout_mask: HOST only, no GPU work: out_host[r * n_cols + c] = 1 where column c of hidden block `layer` is kept
+ * in row r of the batch of step `step` (0 = a handle's first), from the function the kernels use.  p == 0 keeps everything.
+ *   PAYNE_E_INVALID      null out_host, negative n_rows / n_cols / layer, p outside [0, 1) */
+#define PAYNE_LNMLP_PARAMS 0
+#define PAYNE_LNMLP_GRADS 1
+
+typedef struct payne_lnmlp_train_opts {
+  double lr, beta1, beta2, eps;
+  double dropout_p[PAYNE_LNMLP_MAX_LAYERS];
+  unsigned long long seed;
+  int max_rows;
+} payne_lnmlp_train_opts;
+
+typedef struct payne_lnmlp_train payne_lnmlp_train;
+
+int payne_lnmlp_train_create(int device, const payne_lnmlp_desc* init, const payne_lnmlp_train_opts* opts, payne_lnmlp_train** out);
+int payne_lnmlp_train_step(payne_lnmlp_train* h, const float* x_dev, int ld_x, const float* t_dev, int ld_t, int N, double* loss_dev,
+                           void* stream);
+int payne_lnmlp_train_loss(payne_lnmlp_train* h, const float* x_dev, int ld_x, const float* t_dev, int ld_t, int N, double* loss_dev,
+                           void* stream);
+int payne_lnmlp_train_get(payne_lnmlp_train* h, int what, payne_lnmlp_desc* host_out);
+long long payne_lnmlp_train_steps(payne_lnmlp_train* h);
+void payne_lnmlp_train_destroy(payne_lnmlp_train* h);
+int payne_lnmlp_dropout_mask(unsigned long long seed, unsigned long long step, int layer, int n_rows, int n_cols, double p,
+                             unsigned char* out_host);
+
 /* Magnitudes for B parameter vectors: FastPayneSEDPredict.sed
  * (Payne/predict/predictsed.py:75-103).  pars: device fp64 [B][9] =
  * logt, logg, feh, afe, av, rv, logl, dist, logA  (NaN = kwarg absent; the

@@ -35,7 +35,9 @@ SYMBOLS = ["payne_version", "payne_ctx_create", "payne_ctx_set_obs", "payne_ctx_
            "payne_ns_queue_dev_init", "payne_ns_queue_dev_launch", "payne_ns_queue_dev_collect",
            "payne_slice_begin", "payne_slice_rounds", "payne_slice_batch",
            "payne_rv_scan", "payne_chisq_below", "payne_mad_stats",
-           "payne_lnmlp_create", "payne_lnmlp_eval", "payne_lnmlp_destroy"]
+           "payne_lnmlp_create", "payne_lnmlp_eval", "payne_lnmlp_destroy",
+           "payne_lnmlp_train_create", "payne_lnmlp_train_step", "payne_lnmlp_train_loss", "payne_lnmlp_train_get", "payne_lnmlp_train_steps",
+           "payne_lnmlp_train_destroy", "payne_lnmlp_dropout_mask"]
 
 PAYNE_MAX_DIM, PAYNE_MAX_FIXED = 24, 16
 PRIOR_UNIFORM, PRIOR_GAUSSIAN, PRIOR_TGAUSSIAN, PRIOR_EXP, PRIOR_TEXP, PRIOR_LOGUNIFORM, PRIOR_TABLE = range(7)
@@ -71,6 +73,14 @@ class LnmlpLayer(C.Structure):
 class LnmlpDesc(C.Structure):
     _fields_ = [("n_layers", C.c_int), ("layers", LnmlpLayer * PAYNE_MAX_LAYERS),
                 ("in_mid", C.c_void_p), ("in_std", C.c_void_p), ("out_mid", C.c_void_p), ("out_std", C.c_void_p)]
+
+
+LNMLP_PARAMS, LNMLP_GRADS = 0, 1
+
+
+class LnmlpTrainOpts(C.Structure):
+    _fields_ = [("lr", C.c_double), ("beta1", C.c_double), ("beta2", C.c_double), ("eps", C.c_double),
+                ("dropout_p", C.c_double * PAYNE_MAX_LAYERS), ("seed", C.c_ulonglong), ("max_rows", C.c_int)]
 
 
 class Opts(C.Structure):
@@ -173,6 +183,20 @@ def load(path=None):
     lib.payne_lnmlp_eval.restype = C.c_int
     lib.payne_lnmlp_destroy.argtypes = [ctxp]
     lib.payne_lnmlp_destroy.restype = None
+    lib.payne_lnmlp_train_create.argtypes = [C.c_int, C.POINTER(LnmlpDesc), C.POINTER(LnmlpTrainOpts), C.POINTER(ctxp)]
+    lib.payne_lnmlp_train_create.restype = C.c_int
+    lib.payne_lnmlp_train_step.argtypes = [ctxp, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
+    lib.payne_lnmlp_train_step.restype = C.c_int
+    lib.payne_lnmlp_train_loss.argtypes = lib.payne_lnmlp_train_step.argtypes
+    lib.payne_lnmlp_train_loss.restype = C.c_int
+    lib.payne_lnmlp_train_get.argtypes = [ctxp, C.c_int, C.POINTER(LnmlpDesc)]
+    lib.payne_lnmlp_train_get.restype = C.c_int
+    lib.payne_lnmlp_train_steps.argtypes = [ctxp]
+    lib.payne_lnmlp_train_steps.restype = C.c_longlong
+    lib.payne_lnmlp_train_destroy.argtypes = [ctxp]
+    lib.payne_lnmlp_train_destroy.restype = None
+    lib.payne_lnmlp_dropout_mask.argtypes = [C.c_ulonglong, C.c_ulonglong, C.c_int, C.c_int, C.c_int, C.c_double, C.c_void_p]
+    lib.payne_lnmlp_dropout_mask.restype = C.c_int
     lib.payne_ctx_destroy.argtypes = [ctxp]
     lib.payne_ctx_destroy.restype = None
     lib.payne_last_error.argtypes = [ctxp]

@@ -41,6 +41,7 @@ using namespace payne;
 #include "sed_kernel.hpp"
 #include "select.hpp"
 #include "lnmlp_core.hpp"
+#include "lnmlp_train_core.hpp"
 
 // photometry-only fits: lnL = -0.5 chi2_sed
 __global__ void payne_photonly_kernel(const double* mags, const double* obs, const double* err, int F, int B, double* lnl) {
@@ -2164,6 +2165,223 @@ extern "C" int payne_lnmlp_eval(payne_lnmlp* h, const double* x_dev, int ld_x, i
   const int rc = payne_lnmlp_launch(h->net, x_dev, ld_x, N, y_dev, ld_y, stream);
   (void)hipSetDevice(prev);
   return rc;
+}
+
+// ---- training the photometric networks (trainphot.TrainMod): the handle; the kernels are k_lnmlp_train.hip ----------------
+int payne_lnmlp_train_launch(const payne::lnmlp::TrainNet& net, const float* x, int ld_x, const float* t, int ld_t, int N, int train,
+                             unsigned long long seed, unsigned long long step, float scale, void* stream);
+int payne_lnmlp_train_update(const payne::lnmlp::TrainNet& net, int N, const payne::lnmlp::RadamStep& rs, void* stream);
+int payne_lnmlp_train_loss_sum(const payne::lnmlp::TrainNet& net, int N, double* acc, int first, double denom, double* out, void* stream);
+
+struct payne_lnmlp_train {
+  int device = 0;
+  payne::lnmlp::TrainNet net{};
+  payne_lnmlp_train_opts opts{};
+  int rows = 0;                                                     // the workspace's rows: max_rows rounded up to the tile
+  long long t = 0;                                                  // steps taken
+  double* loss_acc = nullptr;
+  void* last_stream = nullptr;
+  std::vector<void*> owned;
+};
+
+extern "C" void payne_lnmlp_train_destroy(payne_lnmlp_train* h) {
+  if (!h) return;
+  int prev = 0;
+  (void)hipGetDevice(&prev);
+  if (hipSetDevice(h->device) == hipSuccess) {
+    (void)hipDeviceSynchronize();
+    for (void* p : h->owned) (void)hipFree(p);
+  }
+  (void)hipSetDevice(prev);
+  delete h;
+}
+
+extern "C" int payne_lnmlp_train_create(int device, const payne_lnmlp_desc* d, const payne_lnmlp_train_opts* o, payne_lnmlp_train** out) {
+  namespace ln = payne::lnmlp;
+  if (!d || !o || !out) return fail(nullptr, PAYNE_E_INVALID, "payne_lnmlp_train_create: null descriptor, options or handle pointer");
+  *out = nullptr;
+  if (d->n_layers < 2 || d->n_layers > ln::kMaxLayers) return fail(nullptr, PAYNE_E_UNSUPPORTED, "payne_lnmlp_train_create: 2 to 8 linear layers");
+  for (int l = 0; l < d->n_layers; ++l) {
+    const payne_lnmlp_layer& L = d->layers[l];
+    const bool last = l + 1 == d->n_layers;
+    if (L.n_in < 1 || L.n_out < 1 || !L.w || !L.b || (l > 0 && L.n_in != d->layers[l - 1].n_out))
+      return fail(nullptr, PAYNE_E_INVALID, "payne_lnmlp_train_create: layer " + std::to_string(l) + ": bad widths or null weights");
+    if (last ? (L.ln_gain || L.ln_bias) : (!L.ln_gain || !L.ln_bias))
+      return fail(nullptr, PAYNE_E_INVALID, "payne_lnmlp_train_create: LayerNorm gain and bias on every layer but the last");
+  }
+  if (d->in_mid || d->in_std || d->out_mid || d->out_std)
+    return fail(nullptr, PAYNE_E_INVALID, "payne_lnmlp_train_create: training data arrive normalised; the descriptor must hold no norms");
+  for (int l = 0; l < ln::kMaxLayers; ++l)
+    if (!(o->dropout_p[l] >= 0.0 && o->dropout_p[l] < 1.0))
+      return fail(nullptr, PAYNE_E_INVALID, "payne_lnmlp_train_create: dropout_p outside [0, 1)");
+  if (o->max_rows < 1 || !(o->lr > 0.0) || !(o->beta1 >= 0.0 && o->beta1 < 1.0) || !(o->beta2 >= 0.0 && o->beta2 < 1.0) || !(o->eps >= 0.0))
+    return fail(nullptr, PAYNE_E_INVALID, "payne_lnmlp_train_create: max_rows < 1 or an optimiser constant out of range");
+  if (d->layers[0].n_in > ln::kMaxIn) return fail(nullptr, PAYNE_E_UNSUPPORTED, "payne_lnmlp_train_create: more than 32 inputs");
+  for (int l = 0; l < d->n_layers; ++l)
+    if (d->layers[l].n_out > ln::kMaxWidth) return fail(nullptr, PAYNE_E_UNSUPPORTED, "payne_lnmlp_train_create: a width above 512");
+
+  int prev = 0;
+  (void)hipGetDevice(&prev);
+  if (hipSetDevice(device) != hipSuccess) return fail(nullptr, PAYNE_E_HIP, "payne_lnmlp_train_create: hipSetDevice");
+  payne_lnmlp_train* h = new payne_lnmlp_train;
+  h->device = device;
+  h->opts = *o;
+  h->rows = (o->max_rows + ln::kTileRows - 1) / ln::kTileRows * ln::kTileRows;
+  const size_t rows = (size_t)h->rows, tiles = rows / ln::kTileRows;
+  bool ok = true;
+  auto zeros = [&](size_t bytes) -> void* {
+    void* p = nullptr;
+    if (!ok || hipMalloc(&p, bytes) != hipSuccess) { ok = false; return nullptr; }
+    h->owned.push_back(p);
+    if (hipMemset(p, 0, bytes) != hipSuccess) ok = false;
+    return p;
+  };
+  auto floats = [&](size_t n) { return static_cast<float*>(zeros(n * sizeof(float))); };
+  auto put = [&](float* dst, const float* src, size_t n) {
+    if (ok && hipMemcpy(dst, src, n * sizeof(float), hipMemcpyHostToDevice) != hipSuccess) ok = false;
+  };
+  h->net.n_layers = d->n_layers;
+  for (int l = 0; l < d->n_layers; ++l) {
+    const payne_lnmlp_layer& L = d->layers[l];
+    ln::TrainLayer& A = h->net.L[l];
+    const size_t nw = (size_t)L.n_in * L.n_out, npad = (size_t)ln::pad32(L.n_out), kpad = (size_t)ln::pad32(L.n_in);
+    A.n_in = L.n_in;
+    A.n_out = L.n_out;
+    A.p = l + 1 < d->n_layers ? (float)o->dropout_p[l] : 0.0f;
+    A.wm = floats(nw);
+    A.gw = floats(nw);
+    A.mw = floats(nw);
+    A.vw = floats(nw);
+    A.wp = floats(ln::packed_floats(L.n_in, L.n_out));
+    A.wt = floats(ln::packed_floats(L.n_out, L.n_in));
+    A.vec = floats(3 * npad);
+    A.gvec = floats(3 * npad);
+    A.mvec = floats(3 * npad);
+    A.vvec = floats(3 * npad);
+    if (l == 0) A.a_in = floats(rows * kpad);                       // (a hidden block's output is the next layer's a_in, below)
+    A.xh = floats(rows * npad);
+    A.rs = floats(rows);
+    A.dz = floats(rows * npad);
+    A.slab = floats(tiles * 3 * npad);
+    if (l + 1 < d->n_layers) h->net.L[l + 1].a_in = floats(rows * npad);
+    std::vector<float> pk(ln::packed_floats(L.n_in, L.n_out)), tr(nw), pt(ln::packed_floats(L.n_out, L.n_in));
+    ln::pack_weights(L.w, L.n_in, L.n_out, pk.data());
+    for (int n = 0; n < L.n_out; ++n)
+      for (int k = 0; k < L.n_in; ++k) tr[(size_t)k * L.n_out + n] = L.w[(size_t)n * L.n_in + k];
+    ln::pack_weights(tr.data(), L.n_out, L.n_in, pt.data());
+    if (ok) {
+      put(A.wm, L.w, nw);
+      put(A.wp, pk.data(), pk.size());
+      put(A.wt, pt.data(), pt.size());
+      put(A.vec, L.b, (size_t)L.n_out);
+      if (L.ln_gain) put(A.vec + npad, L.ln_gain, (size_t)L.n_out);
+      if (L.ln_bias) put(A.vec + 2 * npad, L.ln_bias, (size_t)L.n_out);
+    }
+  }
+  h->net.loss_slab = static_cast<double*>(zeros(tiles * sizeof(double)));
+  h->loss_acc = static_cast<double*>(zeros(sizeof(double)));
+  (void)hipSetDevice(prev);
+  if (!ok) {
+    payne_lnmlp_train_destroy(h);
+    return fail(nullptr, PAYNE_E_HIP, "payne_lnmlp_train_create: allocating or copying to the device failed");
+  }
+  *out = h;
+  return PAYNE_OK;
+}
+
+static int lnmlp_train_check(payne_lnmlp_train* h, const float* x_dev, int ld_x, const float* t_dev, int ld_t, int N) {
+  if (!h || N < 0) return PAYNE_E_INVALID;
+  if (ld_x < h->net.L[0].n_in || ld_t < h->net.L[h->net.n_layers - 1].n_out) return PAYNE_E_INVALID;
+  if (N > 0 && (!x_dev || !t_dev)) return PAYNE_E_INVALID;
+  return PAYNE_OK;
+}
+
+extern "C" int payne_lnmlp_train_step(payne_lnmlp_train* h, const float* x_dev, int ld_x, const float* t_dev, int ld_t, int N,
+                                      double* loss_dev, void* stream) {
+  namespace ln = payne::lnmlp;
+  int rc = lnmlp_train_check(h, x_dev, ld_x, t_dev, ld_t, N);
+  if (rc) return rc;
+  if (N > h->opts.max_rows) return PAYNE_E_INVALID;
+  if (N == 0) return PAYNE_OK;
+  int prev = 0;
+  (void)hipGetDevice(&prev);
+  if (hipSetDevice(h->device) != hipSuccess) return PAYNE_E_HIP;
+  const int d_out = h->net.L[h->net.n_layers - 1].n_out;
+  h->last_stream = stream;
+  rc = payne_lnmlp_train_launch(h->net, x_dev, ld_x, t_dev, ld_t, N, 1, h->opts.seed, (unsigned long long)h->t,
+                                ln::loss_grad_scale(N, d_out), stream);
+  if (!rc && loss_dev) rc = payne_lnmlp_train_loss_sum(h->net, N, h->loss_acc, 1, (double)N * (double)d_out, loss_dev, stream);
+  if (!rc) {
+    rc = payne_lnmlp_train_update(h->net, N, ln::radam_scalars(h->opts.lr, h->opts.beta1, h->opts.beta2, h->opts.eps, h->t + 1), stream);
+    h->t += 1;
+  }
+  (void)hipSetDevice(prev);
+  return rc;
+}
+
+extern "C" int payne_lnmlp_train_loss(payne_lnmlp_train* h, const float* x_dev, int ld_x, const float* t_dev, int ld_t, int N,
+                                      double* loss_dev, void* stream) {
+  int rc = lnmlp_train_check(h, x_dev, ld_x, t_dev, ld_t, N);
+  if (rc) return rc;
+  if (N == 0) return PAYNE_OK;
+  if (!loss_dev) return PAYNE_E_INVALID;
+  int prev = 0;
+  (void)hipGetDevice(&prev);
+  if (hipSetDevice(h->device) != hipSuccess) return PAYNE_E_HIP;
+  const int d_out = h->net.L[h->net.n_layers - 1].n_out;
+  h->last_stream = stream;
+  for (int r0 = 0; r0 < N && !rc; r0 += h->rows) {                  // the workspace's rows a launch
+    const int n = N - r0 < h->rows ? N - r0 : h->rows;
+    rc = payne_lnmlp_train_launch(h->net, x_dev + (size_t)r0 * (size_t)ld_x, ld_x, t_dev + (size_t)r0 * (size_t)ld_t, ld_t, n, 0, 0, 0,
+                                  0.0f, stream);
+    if (!rc) rc = payne_lnmlp_train_loss_sum(h->net, n, h->loss_acc, r0 == 0, r0 + n == N ? (double)N * (double)d_out : 0.0, loss_dev, stream);
+  }
+  (void)hipSetDevice(prev);
+  return rc;
+}
+
+extern "C" int payne_lnmlp_train_get(payne_lnmlp_train* h, int what, payne_lnmlp_desc* host_out) {
+  namespace ln = payne::lnmlp;
+  if (!h || !host_out || (what != PAYNE_LNMLP_PARAMS && what != PAYNE_LNMLP_GRADS) || host_out->n_layers != h->net.n_layers)
+    return PAYNE_E_INVALID;
+  for (int l = 0; l < h->net.n_layers; ++l) {
+    const payne_lnmlp_layer& L = host_out->layers[l];
+    const bool last = l + 1 == h->net.n_layers;
+    if (L.n_in != h->net.L[l].n_in || L.n_out != h->net.L[l].n_out || !L.w || !L.b || (!last && (!L.ln_gain || !L.ln_bias)))
+      return PAYNE_E_INVALID;
+  }
+  int prev = 0;
+  (void)hipGetDevice(&prev);
+  if (hipSetDevice(h->device) != hipSuccess) return PAYNE_E_HIP;
+  bool ok = hipStreamSynchronize(reinterpret_cast<hipStream_t>(h->last_stream)) == hipSuccess;
+  auto take = [&](const float* dst, const float* src, size_t n) {
+    if (ok && hipMemcpy(const_cast<float*>(dst), src, n * sizeof(float), hipMemcpyDeviceToHost) != hipSuccess) ok = false;
+  };
+  for (int l = 0; l < h->net.n_layers; ++l) {
+    const payne_lnmlp_layer& L = host_out->layers[l];
+    const ln::TrainLayer& A = h->net.L[l];
+    const size_t npad = (size_t)ln::pad32(A.n_out);
+    const float* vec = what == PAYNE_LNMLP_PARAMS ? A.vec : A.gvec;
+    take(L.w, what == PAYNE_LNMLP_PARAMS ? A.wm : A.gw, (size_t)A.n_in * A.n_out);
+    take(L.b, vec, (size_t)A.n_out);
+    if (l + 1 < h->net.n_layers) {
+      take(L.ln_gain, vec + npad, (size_t)A.n_out);
+      take(L.ln_bias, vec + 2 * npad, (size_t)A.n_out);
+    }
+  }
+  (void)hipSetDevice(prev);
+  return ok ? PAYNE_OK : PAYNE_E_HIP;
+}
+
+extern "C" long long payne_lnmlp_train_steps(payne_lnmlp_train* h) { return h ? h->t : -1; }
+
+extern "C" int payne_lnmlp_dropout_mask(unsigned long long seed, unsigned long long step, int layer, int n_rows, int n_cols, double p,
+                                        unsigned char* out_host) {
+  if (!out_host || n_rows < 0 || n_cols < 0 || layer < 0 || !(p >= 0.0 && p < 1.0)) return PAYNE_E_INVALID;
+  for (int r = 0; r < n_rows; ++r)
+    for (int c = 0; c < n_cols; ++c)
+      out_host[(size_t)r * (size_t)n_cols + (size_t)c] = payne::lnmlp::keep(seed, step, layer, r, c, (float)p) ? 1 : 0;
+  return PAYNE_OK;
 }
 
 // ---- per-kernel timing ---------------------------------------------------------

@@ -195,6 +195,52 @@ def phot_mlp(path=None, nntype='MLP_v0', D_in=6, H=(256, 256, 256), D_out=8, see
     return net
 
 
+def phot_mlp_forward(net, x, nntype='MLP_v0'):
+    """The network of `phot_mlp` on physical labels x [N, D_in] in numpy fp64, norms applied: the magnitudes [N, D_out].  For
+    synthetic data only (`phot_grid`); the product path evaluates these networks on the device."""
+    dec = lambda a: [s.decode('utf-8') if isinstance(s, bytes) else str(s) for s in a]
+    label_i, label_o = dec(net['label_i']), dec(net['label_o'])
+    ni = np.array([net['norm_i/' + k] for k in label_i])
+    no = np.array([net['norm_o/' + k] for k in label_o])
+    a = (np.asarray(x, dtype=np.float64) - ni[:, 0]) / ni[:, 1]
+    n_hidden, out_name = {'MLP_v0': (5, 'lin6'), 'MLP_v1': (3, 'linout')}[nntype]
+    k = lambda s: net['model/mlp.' + s].astype(np.float64)
+    for i in range(1, n_hidden + 1):
+        z = a @ k('lin%d.weight' % i).T + k('lin%d.bias' % i)
+        mean = z.mean(axis=1, keepdims=True)
+        z = (z - mean) / np.sqrt(((z - mean) ** 2).mean(axis=1, keepdims=True) + 1e-5) * k('ln%d.weight' % i) + k('ln%d.bias' % i)
+        a = z / (1.0 + np.exp(-z))
+    return (a @ k(out_name + '.weight').T + k(out_name + '.bias')) * no[:, 1] + no[:, 0]
+
+
+def phot_grid(path, n_models, nntype='MLP_v1', H=(24, 24, 24), D_out=7, seed=0):
+    """A synthetic photometric model grid in the layout Payne/utils/readKorg.py (ReadPhot) reads, as ``.npz``: a record array
+    ``parameters`` with the fields teff, logg, feh, afe, av, rv (uniform over PHOT_LABEL_MIN .. PHOT_LABEL_MAX) and one record
+    array per photometric system whose fields are its filters (``Bessell``: B, V, R, I; ``2MASS``: J, H, Ks), so that the output
+    labels are ``<system>_<filter>``.  The magnitudes are those of a `phot_mlp` teacher of type `nntype` and nothing else.
+    Returns (the arrays written, the output labels, the teacher's arrays)."""
+    if D_out > len(PHOT_FILTERS):
+        raise ValueError("at most %d bands" % len(PHOT_FILTERS))
+    rng = np.random.default_rng(seed + 1000)
+    teacher = phot_mlp(nntype=nntype, D_in=6, H=H, D_out=D_out, seed=seed)
+    for i, kk in enumerate(PHOT_MLP_LABELS):                          # norms that centre the teacher on the grid's box
+        teacher['norm_i/' + kk] = np.array([0.5 * (PHOT_LABEL_MIN[i] + PHOT_LABEL_MAX[i]), (PHOT_LABEL_MAX[i] - PHOT_LABEL_MIN[i]) / 12 ** 0.5])
+    x = rng.uniform(PHOT_LABEL_MIN, PHOT_LABEL_MAX, (n_models, 6))
+    mags = phot_mlp_forward(teacher, x, nntype=nntype)
+    pars = np.zeros(n_models, dtype=[(kk, 'f8') for kk in PHOT_MLP_LABELS])
+    for i, kk in enumerate(PHOT_MLP_LABELS):
+        pars[kk] = x[:, i]
+    out, label_o = {'parameters': pars}, PHOT_FILTERS[:D_out]
+    for ss in dict.fromkeys(ll.split('_')[0] for ll in label_o):
+        filt = [ll.split('_', 1)[1] for ll in label_o if ll.split('_')[0] == ss]
+        rec = np.zeros(n_models, dtype=[(f, 'f8') for f in filt])
+        for f in filt:
+            rec[f] = mags[:, label_o.index(ss + '_' + f)]
+        out[ss] = rec
+    np.savez(path, **out)
+    return out, label_o, teacher
+
+
 TRUTH = dict(Teff=5770.0, logg=4.44, feh=0.0, afe=0.0, vrad=10.0, vrot=3.0, inst_R=28800.0)
 
 

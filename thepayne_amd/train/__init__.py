@@ -1,0 +1,1 @@
+"""Training on the device: mirrors Payne/train (``trainphot``: the photometric LayerNorm + SiLU networks)."""
