@@ -4,9 +4,10 @@ The reference's callers do ``from Payne.fitting import fitstar`` (demo/runPayne.
 ``from Payne.predict.ystpred import PayneSpecPredict`` and so on.  This package holds no code of its
 own: every ``Payne.<x>`` module of the likelihood hot path is the
 ``thepayne_amd.<x>`` module of the same name, registered under both names, so existing scripts
-run on the MI355X path without edits; so are the quick-look fits, ``testing.testspec``, ``predict.photANN_new`` and the
-trainer of its networks, ``train.trainphot``.  Modules of the reference outside that (training of the spectral networks, grid
-readers, the JAX mirror) do not exist here and raise ImportError as any missing module would.
+run on the MI355X path without edits; so are the quick-look fits, ``testing.testspec``, ``predict.photANN_new``, the
+trainer of its networks, ``train.trainphot``, and the trainer of the spectral networks, ``train.trainspec``.  Modules of the
+reference outside that (``trainflux`` / ``traincont``, grid readers, the JAX mirror) do not exist here and raise ImportError as
+any missing module would.
 """
 import importlib
 import sys
@@ -19,7 +20,7 @@ __abspath__ = _impl.__path__[0] + "/"          # the reference's install-time co
 _MODULES = ["fitting", "fitting.fitstar", "fitting.likelihood", "fitting.prior", "fitting.genmod", "fitting.fitutils",
             "fitting.advancedpriors", "predict", "predict.ystpred", "predict.predictspec", "predict.predictsed",
             "predict.photANN", "predict.photANN_new", "predict.highred", "utils", "utils.smoothing", "testing", "testing.testspec",
-            "train", "train.trainphot"]
+            "train", "train.trainphot", "train.trainspec"]
 for _m in _MODULES:
     try:
         _mod = importlib.import_module("thepayne_amd." + _m)

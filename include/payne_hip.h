@@ -382,6 +382,74 @@ void payne_lnmlp_train_destroy(payne_lnmlp_train* h);
 int payne_lnmlp_dropout_mask(unsigned long long seed, unsigned long long step, int layer, int n_rows, int n_cols, double p,
                              unsigned char* out_host);
 
+/* ---- training the spectral networks: Payne/train/trainspec.py (TrainMod.train_mod) on SMLP / LinNet of Payne/train/NNmodels.py ----
+ * The network maps D_in encoded labels to D_out pixels through n_layers Linear layers; every layer but the last is followed by
+ * LeakyReLU(0.01) (PAYNE_SPECMLP_LEAKY: SMLP, three hidden layers) or a sigmoid (PAYNE_SPECMLP_SIGMOID: LinNet, five).  One step
+ * is trainspec.py:422-444: forward, MSELoss(reduction='sum') (:319), backward, torch.optim.RAdam(lr) with its defaults (:328).
+ * All arithmetic of the network, the backward and the update is fp32 (products on the fp32 matrix instruction); the loss is the
+ * fp32 residuals squared and summed in fp64.  Five launches a step (csrc/k_specmlp_train.hip, csrc/specmlp_train_core.hpp), no
+ * atomics: the same parameters, batch and step counter give the same bits for loss, gradients and updated parameters.  The rows
+ * arrive encoded, (x - xmin) / (xmax - xmin) - 0.5 rounded to fp32 (NNmodels.py:109-113).  A handle is used from one stream at a
+ * time.
+ * payne_specmlp_train_create: every pointer of the descriptor is a HOST pointer: layers[i].w row-major fp32 [n_out][n_in]
+ * (torch's Linear.weight), b fp32 [n_out]: the initial parameters, or a restart file's.  opts: RAdam's lr, beta1, beta2, eps
+ * (the reference: 1e-4, 0.9, 0.999, 1e-8) and max_rows, the largest batch of a step; the workspace is allocated here.
+ *   PAYNE_E_INVALID      null desc / opts / out, a width < 1, n_in of a layer != n_out of the one before, null w / b, an
+ *                        activation kind other than the two, max_rows < 1, lr <= 0, a beta outside [0, 1), eps < 0
+ *   PAYNE_E_UNSUPPORTED  n_layers outside 2..8, D_in > 32, a hidden width > 512, D_out > 65536
+ * payne_specmlp_train_step: one forward / backward / update on x_dev DEVICE fp32 [N][ld_x] (D_in columns read) and t_dev DEVICE
+ * fp32 [N][ld_t] (D_out columns read), 1 <= N <= max_rows.  loss_dev: DEVICE double, the batch's sum of squares before the
+ * update, or NULL.  Enqueued on `stream`; the call does not wait.  N == 0 succeeds and does nothing.
+ *   PAYNE_E_INVALID      null handle, N < 0, N > max_rows, null x_dev / t_dev with N > 0, ld_x < D_in, ld_t < D_out
+ * payne_specmlp_train_loss: the forward and the sum of squares alone; no parameter, optimiser state or step counter changes.
+ * N may exceed max_rows (evaluated in chunks).  N == 0 succeeds, writes nothing.
+ *   PAYNE_E_INVALID      as payne_specmlp_train_step without the limit on N; null loss_dev with N > 0
+ * payne_specmlp_train_predict: the forward alone, y_dev DEVICE fp32 [N][ld_y] (D_out columns written; nothing beyond them,
+ * nothing beyond N rows).  N may exceed max_rows.
+ *   PAYNE_E_INVALID      null handle, N < 0, null x_dev / y_dev with N > 0, ld_x < D_in, ld_y < D_out
+ * payne_specmlp_train_set_lr: the learning rate of the steps that follow (trainspec.py:334,531 StepLR once an epoch).
+ *   PAYNE_E_INVALID      null handle, lr <= 0 or not finite
+ * payne_specmlp_train_get: what = PAYNE_SPECMLP_PARAMS or PAYNE_SPECMLP_GRADS (the gradients of the last step), copied row-major
+ * into the HOST arrays host_out's pointers name (same widths as `init`).  Waits for the work enqueued through the handle.
+ *   PAYNE_E_INVALID      null handle / host_out, another `what`, n_layers or a width differing from the handle's, a null array
+ * payne_specmlp_train_steps: the number of steps taken (RAdam's t); -1 for NULL.
+ * payne_specmlp_train_destroy: NULL is allowed. */
+#define PAYNE_SPECMLP_LEAKY 0
+#define PAYNE_SPECMLP_SIGMOID 1
+#define PAYNE_SPECMLP_PARAMS 0
+#define PAYNE_SPECMLP_GRADS 1
+#define PAYNE_SPECMLP_MAX_OUT 65536
+
+typedef struct payne_specmlp_layer {
+  int n_in, n_out;
+  const float* w;
+  const float* b;
+} payne_specmlp_layer;
+
+typedef struct payne_specmlp_desc {
+  int n_layers;
+  int act;
+  payne_specmlp_layer layers[PAYNE_LNMLP_MAX_LAYERS];
+} payne_specmlp_desc;
+
+typedef struct payne_specmlp_train_opts {
+  double lr, beta1, beta2, eps;
+  int max_rows;
+} payne_specmlp_train_opts;
+
+typedef struct payne_specmlp_train payne_specmlp_train;
+
+int payne_specmlp_train_create(int device, const payne_specmlp_desc* init, const payne_specmlp_train_opts* opts, payne_specmlp_train** out);
+int payne_specmlp_train_step(payne_specmlp_train* h, const float* x_dev, int ld_x, const float* t_dev, int ld_t, int N, double* loss_dev,
+                             void* stream);
+int payne_specmlp_train_loss(payne_specmlp_train* h, const float* x_dev, int ld_x, const float* t_dev, int ld_t, int N, double* loss_dev,
+                             void* stream);
+int payne_specmlp_train_predict(payne_specmlp_train* h, const float* x_dev, int ld_x, int N, float* y_dev, int ld_y, void* stream);
+int payne_specmlp_train_set_lr(payne_specmlp_train* h, double lr);
+int payne_specmlp_train_get(payne_specmlp_train* h, int what, payne_specmlp_desc* host_out);
+long long payne_specmlp_train_steps(payne_specmlp_train* h);
+void payne_specmlp_train_destroy(payne_specmlp_train* h);
+
 /* Magnitudes for B parameter vectors: FastPayneSEDPredict.sed
  * (Payne/predict/predictsed.py:75-103).  pars: device fp64 [B][9] =
  * logt, logg, feh, afe, av, rv, logl, dist, logA  (NaN = kwarg absent; the

@@ -37,7 +37,9 @@ SYMBOLS = ["payne_version", "payne_ctx_create", "payne_ctx_set_obs", "payne_ctx_
            "payne_rv_scan", "payne_chisq_below", "payne_mad_stats",
            "payne_lnmlp_create", "payne_lnmlp_eval", "payne_lnmlp_destroy",
            "payne_lnmlp_train_create", "payne_lnmlp_train_step", "payne_lnmlp_train_loss", "payne_lnmlp_train_get", "payne_lnmlp_train_steps",
-           "payne_lnmlp_train_destroy", "payne_lnmlp_dropout_mask"]
+           "payne_lnmlp_train_destroy", "payne_lnmlp_dropout_mask",
+           "payne_specmlp_train_create", "payne_specmlp_train_step", "payne_specmlp_train_loss", "payne_specmlp_train_predict",
+           "payne_specmlp_train_set_lr", "payne_specmlp_train_get", "payne_specmlp_train_steps", "payne_specmlp_train_destroy"]
 
 PAYNE_MAX_DIM, PAYNE_MAX_FIXED = 24, 16
 PRIOR_UNIFORM, PRIOR_GAUSSIAN, PRIOR_TGAUSSIAN, PRIOR_EXP, PRIOR_TEXP, PRIOR_LOGUNIFORM, PRIOR_TABLE = range(7)
@@ -81,6 +83,22 @@ LNMLP_PARAMS, LNMLP_GRADS = 0, 1
 class LnmlpTrainOpts(C.Structure):
     _fields_ = [("lr", C.c_double), ("beta1", C.c_double), ("beta2", C.c_double), ("eps", C.c_double),
                 ("dropout_p", C.c_double * PAYNE_MAX_LAYERS), ("seed", C.c_ulonglong), ("max_rows", C.c_int)]
+
+
+SPECMLP_LEAKY, SPECMLP_SIGMOID = 0, 1
+SPECMLP_PARAMS, SPECMLP_GRADS = 0, 1
+
+
+class SpecmlpLayer(C.Structure):
+    _fields_ = [("n_in", C.c_int), ("n_out", C.c_int), ("w", C.c_void_p), ("b", C.c_void_p)]
+
+
+class SpecmlpDesc(C.Structure):
+    _fields_ = [("n_layers", C.c_int), ("act", C.c_int), ("layers", SpecmlpLayer * PAYNE_MAX_LAYERS)]
+
+
+class SpecmlpTrainOpts(C.Structure):
+    _fields_ = [("lr", C.c_double), ("beta1", C.c_double), ("beta2", C.c_double), ("eps", C.c_double), ("max_rows", C.c_int)]
 
 
 class Opts(C.Structure):
@@ -197,6 +215,22 @@ def load(path=None):
     lib.payne_lnmlp_train_destroy.restype = None
     lib.payne_lnmlp_dropout_mask.argtypes = [C.c_ulonglong, C.c_ulonglong, C.c_int, C.c_int, C.c_int, C.c_double, C.c_void_p]
     lib.payne_lnmlp_dropout_mask.restype = C.c_int
+    lib.payne_specmlp_train_create.argtypes = [C.c_int, C.POINTER(SpecmlpDesc), C.POINTER(SpecmlpTrainOpts), C.POINTER(ctxp)]
+    lib.payne_specmlp_train_create.restype = C.c_int
+    lib.payne_specmlp_train_step.argtypes = [ctxp, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
+    lib.payne_specmlp_train_step.restype = C.c_int
+    lib.payne_specmlp_train_loss.argtypes = lib.payne_specmlp_train_step.argtypes
+    lib.payne_specmlp_train_loss.restype = C.c_int
+    lib.payne_specmlp_train_predict.argtypes = [ctxp, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p]
+    lib.payne_specmlp_train_predict.restype = C.c_int
+    lib.payne_specmlp_train_set_lr.argtypes = [ctxp, C.c_double]
+    lib.payne_specmlp_train_set_lr.restype = C.c_int
+    lib.payne_specmlp_train_get.argtypes = [ctxp, C.c_int, C.POINTER(SpecmlpDesc)]
+    lib.payne_specmlp_train_get.restype = C.c_int
+    lib.payne_specmlp_train_steps.argtypes = [ctxp]
+    lib.payne_specmlp_train_steps.restype = C.c_longlong
+    lib.payne_specmlp_train_destroy.argtypes = [ctxp]
+    lib.payne_specmlp_train_destroy.restype = None
     lib.payne_ctx_destroy.argtypes = [ctxp]
     lib.payne_ctx_destroy.restype = None
     lib.payne_last_error.argtypes = [ctxp]

@@ -42,6 +42,7 @@ using namespace payne;
 #include "select.hpp"
 #include "lnmlp_core.hpp"
 #include "lnmlp_train_core.hpp"
+#include "specmlp_train_core.hpp"
 
 // photometry-only fits: lnL = -0.5 chi2_sed
 __global__ void payne_photonly_kernel(const double* mags, const double* obs, const double* err, int F, int B, double* lnl) {
@@ -2383,6 +2384,217 @@ extern "C" int payne_lnmlp_dropout_mask(unsigned long long seed, unsigned long l
       out_host[(size_t)r * (size_t)n_cols + (size_t)c] = payne::lnmlp::keep(seed, step, layer, r, c, (float)p) ? 1 : 0;
   return PAYNE_OK;
 }
+
+// ---- training the spectral networks (trainspec.TrainMod): the handle; the kernels are k_specmlp_train.hip -------------------
+int payne_specmlp_train_forward(const payne::specmlp::SpecNet& net, const float* x, int ld_x, const float* t, int ld_t, float* y, int ld_y,
+                                int N, int train, void* stream);
+int payne_specmlp_train_backward(const payne::specmlp::SpecNet& net, int N, const payne::lnmlp::RadamStep& rs, void* stream);
+int payne_specmlp_train_loss_sum(const payne::specmlp::SpecNet& net, int N, double* acc, int first, double* out, void* stream);
+
+struct payne_specmlp_train {
+  int device = 0;
+  payne::specmlp::SpecNet net{};
+  payne_specmlp_train_opts opts{};
+  int rows = 0;                                                     // the workspace's rows: max_rows rounded up to the tile
+  long long t = 0;                                                  // steps taken
+  double* loss_acc = nullptr;
+  void* last_stream = nullptr;
+  std::vector<void*> owned;
+};
+
+extern "C" void payne_specmlp_train_destroy(payne_specmlp_train* h) {
+  if (!h) return;
+  int prev = 0;
+  (void)hipGetDevice(&prev);
+  if (hipSetDevice(h->device) == hipSuccess) {
+    (void)hipDeviceSynchronize();
+    for (void* p : h->owned) (void)hipFree(p);
+  }
+  (void)hipSetDevice(prev);
+  delete h;
+}
+
+extern "C" int payne_specmlp_train_create(int device, const payne_specmlp_desc* d, const payne_specmlp_train_opts* o, payne_specmlp_train** out) {
+  namespace sp = payne::specmlp;
+  if (!d || !o || !out) return fail(nullptr, PAYNE_E_INVALID, "payne_specmlp_train_create: null descriptor, options or handle pointer");
+  *out = nullptr;
+  if (d->n_layers < 2 || d->n_layers > sp::kMaxLayers) return fail(nullptr, PAYNE_E_UNSUPPORTED, "payne_specmlp_train_create: 2 to 8 linear layers");
+  for (int l = 0; l < d->n_layers; ++l) {
+    const payne_specmlp_layer& L = d->layers[l];
+    if (L.n_in < 1 || L.n_out < 1 || !L.w || !L.b || (l > 0 && L.n_in != d->layers[l - 1].n_out))
+      return fail(nullptr, PAYNE_E_INVALID, "payne_specmlp_train_create: layer " + std::to_string(l) + ": bad widths or null weights");
+  }
+  if (d->act != PAYNE_SPECMLP_LEAKY && d->act != PAYNE_SPECMLP_SIGMOID)
+    return fail(nullptr, PAYNE_E_INVALID, "payne_specmlp_train_create: the activation is PAYNE_SPECMLP_LEAKY or PAYNE_SPECMLP_SIGMOID");
+  if (o->max_rows < 1 || !(o->lr > 0.0) || !(o->beta1 >= 0.0 && o->beta1 < 1.0) || !(o->beta2 >= 0.0 && o->beta2 < 1.0) || !(o->eps >= 0.0))
+    return fail(nullptr, PAYNE_E_INVALID, "payne_specmlp_train_create: max_rows < 1 or an optimiser constant out of range");
+  if (d->layers[0].n_in > sp::kMaxIn) return fail(nullptr, PAYNE_E_UNSUPPORTED, "payne_specmlp_train_create: more than 32 inputs");
+  for (int l = 0; l + 1 < d->n_layers; ++l)
+    if (d->layers[l].n_out > sp::kMaxWidth) return fail(nullptr, PAYNE_E_UNSUPPORTED, "payne_specmlp_train_create: a hidden width above 512");
+  if (d->layers[d->n_layers - 1].n_out > sp::kMaxOut) return fail(nullptr, PAYNE_E_UNSUPPORTED, "payne_specmlp_train_create: more than 65536 outputs");
+
+  int prev = 0;
+  (void)hipGetDevice(&prev);
+  if (hipSetDevice(device) != hipSuccess) return fail(nullptr, PAYNE_E_HIP, "payne_specmlp_train_create: hipSetDevice");
+  payne_specmlp_train* h = new payne_specmlp_train;
+  h->device = device;
+  h->opts = *o;
+  h->rows = (o->max_rows + sp::kTileRows - 1) / sp::kTileRows * sp::kTileRows;
+  const size_t rows = (size_t)h->rows, tiles = rows / sp::kTileRows;
+  bool ok = true;
+  auto zeros = [&](size_t bytes) -> void* {
+    void* p = nullptr;
+    if (!ok || hipMalloc(&p, bytes) != hipSuccess) { ok = false; return nullptr; }
+    h->owned.push_back(p);
+    if (hipMemset(p, 0, bytes) != hipSuccess) ok = false;
+    return p;
+  };
+  auto floats = [&](size_t n) { return static_cast<float*>(zeros(n * sizeof(float))); };
+  auto put = [&](float* dst, const float* src, size_t n) {
+    if (ok && hipMemcpy(dst, src, n * sizeof(float), hipMemcpyHostToDevice) != hipSuccess) ok = false;
+  };
+  h->net.n_layers = d->n_layers;
+  h->net.act = d->act == PAYNE_SPECMLP_SIGMOID ? sp::kActSigmoid : sp::kActLeaky;
+  for (int l = 0; l < d->n_layers; ++l) {
+    const payne_specmlp_layer& L = d->layers[l];
+    sp::SpecLayer& A = h->net.L[l];
+    const size_t nw = (size_t)L.n_in * L.n_out, npad = (size_t)sp::pad32(L.n_out), kpad = (size_t)sp::pad32(L.n_in);
+    A.n_in = L.n_in;
+    A.n_out = L.n_out;
+    A.wm = floats(nw);
+    A.gw = floats(nw);
+    A.mw = floats(nw);
+    A.vw = floats(nw);
+    A.wp = floats(sp::packed_floats(L.n_in, L.n_out));
+    A.wt = floats(sp::packed_floats(L.n_out, L.n_in));
+    A.vec = floats(npad);
+    A.gvec = floats(npad);
+    A.mvec = floats(npad);
+    A.vvec = floats(npad);
+    if (l == 0) A.a_in = floats(rows * kpad);                       // (a hidden block's output is the next layer's a_in, below)
+    A.dz = floats(rows * npad);
+    A.slab = floats(tiles * npad);
+    if (l + 1 < d->n_layers) h->net.L[l + 1].a_in = floats(rows * npad);
+    std::vector<float> pk(sp::packed_floats(L.n_in, L.n_out)), tr(nw), pt(sp::packed_floats(L.n_out, L.n_in));
+    sp::pack_weights(L.w, L.n_in, L.n_out, pk.data());
+    for (int n = 0; n < L.n_out; ++n)
+      for (int k = 0; k < L.n_in; ++k) tr[(size_t)k * L.n_out + n] = L.w[(size_t)n * L.n_in + k];
+    sp::pack_weights(tr.data(), L.n_out, L.n_in, pt.data());
+    if (ok) {
+      put(A.wm, L.w, nw);
+      put(A.wp, pk.data(), pk.size());
+      put(A.wt, pt.data(), pt.size());
+      put(A.vec, L.b, (size_t)L.n_out);
+    }
+  }
+  h->net.loss_slab = static_cast<double*>(zeros(tiles * (size_t)sp::out_chunks(d->layers[d->n_layers - 1].n_out) * sizeof(double)));
+  h->loss_acc = static_cast<double*>(zeros(sizeof(double)));
+  (void)hipSetDevice(prev);
+  if (!ok) {
+    payne_specmlp_train_destroy(h);
+    return fail(nullptr, PAYNE_E_HIP, "payne_specmlp_train_create: allocating or copying to the device failed");
+  }
+  *out = h;
+  return PAYNE_OK;
+}
+
+static int specmlp_train_check(payne_specmlp_train* h, const float* x_dev, int ld_x, const float* t_dev, int ld_t, int N) {
+  if (!h || N < 0) return PAYNE_E_INVALID;
+  if (ld_x < h->net.L[0].n_in || ld_t < h->net.L[h->net.n_layers - 1].n_out) return PAYNE_E_INVALID;
+  if (N > 0 && (!x_dev || !t_dev)) return PAYNE_E_INVALID;
+  return PAYNE_OK;
+}
+
+extern "C" int payne_specmlp_train_step(payne_specmlp_train* h, const float* x_dev, int ld_x, const float* t_dev, int ld_t, int N,
+                                        double* loss_dev, void* stream) {
+  int rc = specmlp_train_check(h, x_dev, ld_x, t_dev, ld_t, N);
+  if (rc) return rc;
+  if (N > h->opts.max_rows) return PAYNE_E_INVALID;
+  if (N == 0) return PAYNE_OK;
+  int prev = 0;
+  (void)hipGetDevice(&prev);
+  if (hipSetDevice(h->device) != hipSuccess) return PAYNE_E_HIP;
+  h->last_stream = stream;
+  rc = payne_specmlp_train_forward(h->net, x_dev, ld_x, t_dev, ld_t, nullptr, 0, N, 1, stream);
+  if (!rc && loss_dev) rc = payne_specmlp_train_loss_sum(h->net, N, h->loss_acc, 1, loss_dev, stream);
+  if (!rc) {
+    rc = payne_specmlp_train_backward(h->net, N, payne::lnmlp::radam_scalars(h->opts.lr, h->opts.beta1, h->opts.beta2, h->opts.eps, h->t + 1),
+                                      stream);
+    h->t += 1;
+  }
+  (void)hipSetDevice(prev);
+  return rc;
+}
+
+extern "C" int payne_specmlp_train_loss(payne_specmlp_train* h, const float* x_dev, int ld_x, const float* t_dev, int ld_t, int N,
+                                        double* loss_dev, void* stream) {
+  int rc = specmlp_train_check(h, x_dev, ld_x, t_dev, ld_t, N);
+  if (rc) return rc;
+  if (N == 0) return PAYNE_OK;
+  if (!loss_dev) return PAYNE_E_INVALID;
+  int prev = 0;
+  (void)hipGetDevice(&prev);
+  if (hipSetDevice(h->device) != hipSuccess) return PAYNE_E_HIP;
+  h->last_stream = stream;
+  for (int r0 = 0; r0 < N && !rc; r0 += h->rows) {                  // the workspace's rows a pass
+    const int n = N - r0 < h->rows ? N - r0 : h->rows;
+    rc = payne_specmlp_train_forward(h->net, x_dev + (size_t)r0 * (size_t)ld_x, ld_x, t_dev + (size_t)r0 * (size_t)ld_t, ld_t, nullptr, 0, n,
+                                     0, stream);
+    if (!rc) rc = payne_specmlp_train_loss_sum(h->net, n, h->loss_acc, r0 == 0, r0 + n == N ? loss_dev : nullptr, stream);
+  }
+  (void)hipSetDevice(prev);
+  return rc;
+}
+
+extern "C" int payne_specmlp_train_predict(payne_specmlp_train* h, const float* x_dev, int ld_x, int N, float* y_dev, int ld_y, void* stream) {
+  if (!h || N < 0) return PAYNE_E_INVALID;
+  if (ld_x < h->net.L[0].n_in || ld_y < h->net.L[h->net.n_layers - 1].n_out) return PAYNE_E_INVALID;
+  if (N == 0) return PAYNE_OK;
+  if (!x_dev || !y_dev) return PAYNE_E_INVALID;
+  int prev = 0, rc = PAYNE_OK;
+  (void)hipGetDevice(&prev);
+  if (hipSetDevice(h->device) != hipSuccess) return PAYNE_E_HIP;
+  h->last_stream = stream;
+  for (int r0 = 0; r0 < N && !rc; r0 += h->rows) {
+    const int n = N - r0 < h->rows ? N - r0 : h->rows;
+    rc = payne_specmlp_train_forward(h->net, x_dev + (size_t)r0 * (size_t)ld_x, ld_x, nullptr, 0, y_dev + (size_t)r0 * (size_t)ld_y, ld_y, n, 0,
+                                     stream);
+  }
+  (void)hipSetDevice(prev);
+  return rc;
+}
+
+extern "C" int payne_specmlp_train_set_lr(payne_specmlp_train* h, double lr) {
+  if (!h || !(lr > 0.0) || !std::isfinite(lr)) return PAYNE_E_INVALID;
+  h->opts.lr = lr;
+  return PAYNE_OK;
+}
+
+extern "C" int payne_specmlp_train_get(payne_specmlp_train* h, int what, payne_specmlp_desc* host_out) {
+  if (!h || !host_out || (what != PAYNE_SPECMLP_PARAMS && what != PAYNE_SPECMLP_GRADS) || host_out->n_layers != h->net.n_layers)
+    return PAYNE_E_INVALID;
+  for (int l = 0; l < h->net.n_layers; ++l) {
+    const payne_specmlp_layer& L = host_out->layers[l];
+    if (L.n_in != h->net.L[l].n_in || L.n_out != h->net.L[l].n_out || !L.w || !L.b) return PAYNE_E_INVALID;
+  }
+  int prev = 0;
+  (void)hipGetDevice(&prev);
+  if (hipSetDevice(h->device) != hipSuccess) return PAYNE_E_HIP;
+  bool ok = hipStreamSynchronize(reinterpret_cast<hipStream_t>(h->last_stream)) == hipSuccess;
+  auto take = [&](const float* dst, const float* src, size_t n) {
+    if (ok && hipMemcpy(const_cast<float*>(dst), src, n * sizeof(float), hipMemcpyDeviceToHost) != hipSuccess) ok = false;
+  };
+  for (int l = 0; l < h->net.n_layers; ++l) {
+    const payne_specmlp_layer& L = host_out->layers[l];
+    const payne::specmlp::SpecLayer& A = h->net.L[l];
+    take(L.w, what == PAYNE_SPECMLP_PARAMS ? A.wm : A.gw, (size_t)A.n_in * A.n_out);
+    take(L.b, what == PAYNE_SPECMLP_PARAMS ? A.vec : A.gvec, (size_t)A.n_out);
+  }
+  (void)hipSetDevice(prev);
+  return ok ? PAYNE_OK : PAYNE_E_HIP;
+}
+
+extern "C" long long payne_specmlp_train_steps(payne_specmlp_train* h) { return h ? h->t : -1; }
 
 // ---- per-kernel timing ---------------------------------------------------------
 extern "C" int payne_profile(payne_ctx* c, int enable) {

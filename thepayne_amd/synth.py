@@ -126,6 +126,36 @@ def add_test_set(net, forward, n=65, seed=0, labels=None, sigma=1e-3):
     return out
 
 
+SPEC_LABEL_NAMES = ['teff', 'logg', 'feh', 'afe']
+
+
+def torch_net_forward(net, labels):
+    """The network of `make_torch_net` on physical labels [N, D] in numpy fp64 (NNmodels.py: encode, then Linear + LeakyReLU(0.01)
+    for SMLP, Linear + sigmoid for LinNet, a closing Linear): the spectra [N, npix].  For synthetic data only (`spec_grid`); the
+    product path evaluates these networks on the device."""
+    a = (np.asarray(labels, dtype=np.float64) - net["xmin"]) / (net["xmax"] - net["xmin"]) - 0.5
+    names = ["features.%d" % i for i in (0, 2, 4, 6)] if net["kind"] == "SMLP" else ["lin%d" % i for i in range(1, 7)]
+    for i, nm in enumerate(names):
+        z = a @ net[nm + ".weight"].astype(np.float64).T + net[nm + ".bias"].astype(np.float64)
+        if i + 1 == len(names):
+            return z
+        a = np.where(z > 0, z, 0.01 * z) if net["kind"] == "SMLP" else 1.0 / (1.0 + np.exp(-z))
+
+
+def spec_grid(path, n_models, kind="SMLP", npix=300, H=(24, 24, 24), seed=0, lam0=5150.0, R_fwhm=32000.0):
+    """A synthetic pre-pulled spectral grid as ``Payne.train.trainspec.TrainMod(c3kpath=...)`` reads it, an ``.npz`` with
+    ``spectra`` fp32 [n_models, npix], ``labels`` fp64 [n_models, 4] (uniform over SPEC_LABEL_MIN .. SPEC_LABEL_MAX),
+    ``label_names`` and ``wavelengths`` (`ann_wavelength`).  The spectra are those of a `make_torch_net` teacher of type `kind`
+    and nothing else.  Returns (the arrays written, the teacher's arrays)."""
+    rng = np.random.default_rng(seed + 2000)
+    teacher = make_torch_net(kind, npix=npix, lam0=lam0, R_fwhm=R_fwhm, H=H, seed=seed, D=4)
+    labels = rng.uniform(SPEC_LABEL_MIN, SPEC_LABEL_MAX, (n_models, 4))
+    out = {"spectra": torch_net_forward(teacher, labels).astype(np.float32), "labels": labels,
+           "label_names": np.array([s.encode("utf-8") for s in SPEC_LABEL_NAMES]), "wavelengths": teacher["wavelength"]}
+    np.savez(path, **out)
+    return out, teacher
+
+
 PHOT_FILTERS = ['Bessell_B', 'Bessell_V', 'Bessell_R', 'Bessell_I', '2MASS_J', '2MASS_H', '2MASS_Ks']
 PHOT_LABEL_MIN = np.array([2500.0, -1.0, -4.0, -0.2, 0.0, 2.0])
 PHOT_LABEL_MAX = np.array([20000.0, 5.5, 0.5, 0.6, 5.0, 5.0])

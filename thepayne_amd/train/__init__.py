@@ -1,1 +1,1 @@
-"""Training on the device: mirrors Payne/train (``trainphot``: the photometric LayerNorm + SiLU networks)."""
+"""Training on the device: mirrors Payne/train (``trainphot``: the photometric LayerNorm + SiLU networks; ``trainspec``: the spectral networks SMLP and LinNet)."""
