@@ -450,6 +450,50 @@ int payne_specmlp_train_get(payne_specmlp_train* h, int what, payne_specmlp_desc
 long long payne_specmlp_train_steps(payne_specmlp_train* h);
 void payne_specmlp_train_destroy(payne_specmlp_train* h);
 
+/* ---- label gradients of the emulated spectrum and Fisher matrices ----
+ * payne_specjac_*: the spectral networks as payne_specmlp_desc describes them (Net of Payne/predict/ystpred.py:18-58, SMLP / LinNet
+ * of Payne/train/NNmodels.py:92-168) evaluated together with their Jacobian with respect to the labels, by a forward-mode pass
+ * through the dense layers: for label k the tangent starts as column k of the first weight matrix, is multiplied by act'(z) behind
+ * every hidden layer and by the next weight matrix (no bias), and leaves the output layer as dy/de_k, e the encoded labels
+ * (x - xmin) / (xmax - xmin) - 0.5 (ystpred.py:47-50, NNmodels.py:109-113; formed in fp64, rounded once to fp32).  dy/dx_k is that
+ * times (float)(1 / (xmax_k - xmin_k)).  act' of LeakyReLU(0.01) is 1 for z > 0 and 0.01 otherwise (torch's rule at z == 0; the
+ * reference's numpy leaky_relu, ystpred.py:41-45, is 0 there: a set of measure zero); the sigmoid's is s (1 - s) from the primal's
+ * fp32 s.  Everything after the network in getspec (ystpred.py:211-277: rotational broadening with its edge rule, the Doppler
+ * shift, instrumental broadening, resampling) is linear in the flux, so the Jacobian of the broadened spectrum is
+ * payne_smooth_batch applied to these rows.  All arithmetic is fp32 with the products on the fp32 matrix instruction; two launches
+ * (csrc/k_specjac.hip, csrc/specjac_core.hpp), no atomics: the same inputs give the same bits.  A handle is used from one stream at
+ * a time.
+ * payne_specjac_create: every pointer is a HOST pointer: the descriptor's layers[i].w row-major fp32 [n_out][n_in], b fp32 [n_out];
+ * xmin, xmax fp64 [D_in].  max_rows: the stars of one pass; the workspace is allocated here.
+ *   PAYNE_E_INVALID      null net / xmin / xmax / out, a width < 1, n_in of a layer != n_out of the one before, null w / b, an
+ *                        activation kind other than the two, max_rows < 1, an xmin or xmax that is not finite, xmin == xmax
+ *   PAYNE_E_UNSUPPORTED  n_layers outside 2..8, D_in > 8, a hidden width > 512, D_out > PAYNE_SPECMLP_MAX_OUT (within these the
+ *                        workgroup's image is at most 132 KB of the 160 KB of LDS)
+ * payne_specjac_eval: labels_dev DEVICE fp64 [N][ld_x], the raw labels (Teff in K; D_in columns read).  y_dev DEVICE fp32 [N][ld_y],
+ * the network's output, or NULL; jac_dev DEVICE fp32 [N][D_in][ld_j], row [i][k] = dy_i / dx_k, or dy_i / de_k with
+ * PAYNE_JAC_ENCODED in flags.  D_out columns and N rows are written, nothing beyond them.  N may exceed max_rows (evaluated in
+ * chunks, the same bits).  N == 0 succeeds and does nothing.  Enqueued on `stream`; the call does not wait.
+ *   PAYNE_E_INVALID      null handle, N < 0, a flag other than PAYNE_JAC_ENCODED, ld_x < D_in, ld_j < D_out, ld_y < D_out with
+ *                        y_dev, null labels_dev / jac_dev with N > 0
+ * payne_specjac_destroy: NULL is allowed.
+ * payne_fisher_batch: F[b][i][j] = sum_p rows[b][i][p] rows[b][j][p] w[p] for B stars and K rows of n pixels each: with rows the
+ * derivatives of the model spectrum and w = 1 / sigma^2 the Fisher matrix of the star's parameters.  rows_dev DEVICE fp32
+ * [B][K][ld]; w_dev DEVICE fp64 [n], one vector for all stars; F_dev DEVICE fp64 [B][K][K].  Products and sums in fp64, the pixels
+ * in index order, no atomics; F[i][j] and F[j][i] are the same bits.  A pixel with w[p] == 0 is skipped whatever the rows hold
+ * there (getspec is NaN outside the model's range); any other NaN propagates.  B == 0 succeeds and does nothing.  Enqueued on
+ * `stream`; the call does not wait.
+ *   PAYNE_E_INVALID      K < 1, n < 1, B < 0, ld < n, null rows_dev / w_dev / F_dev with B > 0
+ *   PAYNE_E_UNSUPPORTED  K > 16 */
+#define PAYNE_JAC_ENCODED 1u
+
+typedef struct payne_specjac payne_specjac;
+
+int payne_specjac_create(int device, const payne_specmlp_desc* net, const double* xmin, const double* xmax, int max_rows, payne_specjac** out);
+int payne_specjac_eval(payne_specjac* h, const double* labels_dev, int ld_x, int N, float* y_dev, int ld_y, float* jac_dev, int ld_j,
+                       unsigned flags, void* stream);
+void payne_specjac_destroy(payne_specjac* h);
+int payne_fisher_batch(int device, const float* rows_dev, int ld, int K, int n, int B, const double* w_dev, double* F_dev, void* stream);
+
 /* Magnitudes for B parameter vectors: FastPayneSEDPredict.sed
  * (Payne/predict/predictsed.py:75-103).  pars: device fp64 [B][9] =
  * logt, logg, feh, afe, av, rv, logl, dist, logA  (NaN = kwarg absent; the

@@ -39,7 +39,8 @@ SYMBOLS = ["payne_version", "payne_ctx_create", "payne_ctx_set_obs", "payne_ctx_
            "payne_lnmlp_train_create", "payne_lnmlp_train_step", "payne_lnmlp_train_loss", "payne_lnmlp_train_get", "payne_lnmlp_train_steps",
            "payne_lnmlp_train_destroy", "payne_lnmlp_dropout_mask",
            "payne_specmlp_train_create", "payne_specmlp_train_step", "payne_specmlp_train_loss", "payne_specmlp_train_predict",
-           "payne_specmlp_train_set_lr", "payne_specmlp_train_get", "payne_specmlp_train_steps", "payne_specmlp_train_destroy"]
+           "payne_specmlp_train_set_lr", "payne_specmlp_train_get", "payne_specmlp_train_steps", "payne_specmlp_train_destroy",
+           "payne_specjac_create", "payne_specjac_eval", "payne_specjac_destroy", "payne_fisher_batch"]
 
 PAYNE_MAX_DIM, PAYNE_MAX_FIXED = 24, 16
 PRIOR_UNIFORM, PRIOR_GAUSSIAN, PRIOR_TGAUSSIAN, PRIOR_EXP, PRIOR_TEXP, PRIOR_LOGUNIFORM, PRIOR_TABLE = range(7)
@@ -99,6 +100,10 @@ class SpecmlpDesc(C.Structure):
 
 class SpecmlpTrainOpts(C.Structure):
     _fields_ = [("lr", C.c_double), ("beta1", C.c_double), ("beta2", C.c_double), ("eps", C.c_double), ("max_rows", C.c_int)]
+
+
+JAC_ENCODED = 1
+SPECJAC_MAX_LABELS, FISHER_MAX_ROWS = 8, 16
 
 
 class Opts(C.Structure):
@@ -231,6 +236,14 @@ def load(path=None):
     lib.payne_specmlp_train_steps.restype = C.c_longlong
     lib.payne_specmlp_train_destroy.argtypes = [ctxp]
     lib.payne_specmlp_train_destroy.restype = None
+    lib.payne_specjac_create.argtypes = [C.c_int, C.POINTER(SpecmlpDesc), C.c_void_p, C.c_void_p, C.c_int, C.POINTER(ctxp)]
+    lib.payne_specjac_create.restype = C.c_int
+    lib.payne_specjac_eval.argtypes = [ctxp, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_uint, C.c_void_p]
+    lib.payne_specjac_eval.restype = C.c_int
+    lib.payne_specjac_destroy.argtypes = [ctxp]
+    lib.payne_specjac_destroy.restype = None
+    lib.payne_fisher_batch.argtypes = [C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.payne_fisher_batch.restype = C.c_int
     lib.payne_ctx_destroy.argtypes = [ctxp]
     lib.payne_ctx_destroy.restype = None
     lib.payne_last_error.argtypes = [ctxp]

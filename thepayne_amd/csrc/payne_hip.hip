@@ -43,6 +43,7 @@ using namespace payne;
 #include "lnmlp_core.hpp"
 #include "lnmlp_train_core.hpp"
 #include "specmlp_train_core.hpp"
+#include "specjac_core.hpp"
 
 // photometry-only fits: lnL = -0.5 chi2_sed
 __global__ void payne_photonly_kernel(const double* mags, const double* obs, const double* err, int F, int B, double* lnl) {
@@ -2595,6 +2596,138 @@ extern "C" int payne_specmlp_train_get(payne_specmlp_train* h, int what, payne_s
 }
 
 extern "C" long long payne_specmlp_train_steps(payne_specmlp_train* h) { return h ? h->t : -1; }
+
+// ---- label gradients of the spectral networks and Fisher matrices: the handle; the kernels are k_specjac.hip -----------------
+int payne_specjac_launch(const payne::specjac::JacNet& net, const double* x, int ld_x, int N, float* y, int ld_y, float* jac, int ld_j,
+                         void* stream);
+int payne_specjac_prepare(const payne::specjac::JacNet& net);
+int payne_fisher_launch(const float* rows, int ld, int K, int n, int B, const double* w, double* F, void* stream);
+
+struct payne_specjac {
+  int device = 0;
+  payne::specjac::JacNet net{};                                     // (scale: the physical one, 1 / (xmax - xmin))
+  int stars = 0;                                                    // the workspace's stars: max_rows rounded up to whole tiles
+  std::vector<void*> owned;
+};
+
+extern "C" void payne_specjac_destroy(payne_specjac* h) {
+  if (!h) return;
+  int prev = 0;
+  (void)hipGetDevice(&prev);
+  if (hipSetDevice(h->device) == hipSuccess) {
+    (void)hipDeviceSynchronize();
+    for (void* p : h->owned) (void)hipFree(p);
+  }
+  (void)hipSetDevice(prev);
+  delete h;
+}
+
+extern "C" int payne_specjac_create(int device, const payne_specmlp_desc* d, const double* xmin, const double* xmax, int max_rows,
+                                    payne_specjac** out) {
+  namespace sj = payne::specjac;
+  if (!d || !xmin || !xmax || !out) return fail(nullptr, PAYNE_E_INVALID, "payne_specjac_create: null descriptor, xmin, xmax or handle pointer");
+  *out = nullptr;
+  if (d->n_layers < 2 || d->n_layers > sj::kMaxLayers) return fail(nullptr, PAYNE_E_UNSUPPORTED, "payne_specjac_create: 2 to 8 linear layers");
+  for (int l = 0; l < d->n_layers; ++l) {
+    const payne_specmlp_layer& L = d->layers[l];
+    if (L.n_in < 1 || L.n_out < 1 || !L.w || !L.b || (l > 0 && L.n_in != d->layers[l - 1].n_out))
+      return fail(nullptr, PAYNE_E_INVALID, "payne_specjac_create: layer " + std::to_string(l) + ": bad widths or null weights");
+  }
+  if (d->act != PAYNE_SPECMLP_LEAKY && d->act != PAYNE_SPECMLP_SIGMOID)
+    return fail(nullptr, PAYNE_E_INVALID, "payne_specjac_create: the activation is PAYNE_SPECMLP_LEAKY or PAYNE_SPECMLP_SIGMOID");
+  if (max_rows < 1) return fail(nullptr, PAYNE_E_INVALID, "payne_specjac_create: max_rows < 1");
+  const int d_in = d->layers[0].n_in;
+  if (d_in > sj::kMaxLabels) return fail(nullptr, PAYNE_E_UNSUPPORTED, "payne_specjac_create: more than 8 labels");
+  for (int l = 0; l + 1 < d->n_layers; ++l)
+    if (d->layers[l].n_out > sj::kMaxWidth) return fail(nullptr, PAYNE_E_UNSUPPORTED, "payne_specjac_create: a hidden width above 512");
+  if (d->layers[d->n_layers - 1].n_out > sj::kMaxOut) return fail(nullptr, PAYNE_E_UNSUPPORTED, "payne_specjac_create: more than 65536 outputs");
+  for (int k = 0; k < d_in; ++k)
+    if (!std::isfinite(xmin[k]) || !std::isfinite(xmax[k]) || xmin[k] == xmax[k])
+      return fail(nullptr, PAYNE_E_INVALID, "payne_specjac_create: label " + std::to_string(k) + ": xmin / xmax not finite or equal");
+
+  int prev = 0;
+  (void)hipGetDevice(&prev);
+  if (hipSetDevice(device) != hipSuccess) return fail(nullptr, PAYNE_E_HIP, "payne_specjac_create: hipSetDevice");
+  payne_specjac* h = new payne_specjac;
+  h->device = device;
+  const int tiles = sj::tiles_of(max_rows, d_in);
+  h->stars = tiles * sj::stars_per_tile(d_in);
+  bool ok = true;
+  auto floats = [&](size_t n) -> float* {
+    void* p = nullptr;
+    if (!ok || hipMalloc(&p, n * sizeof(float)) != hipSuccess) { ok = false; return nullptr; }
+    h->owned.push_back(p);
+    if (hipMemset(p, 0, n * sizeof(float)) != hipSuccess) ok = false;
+    return static_cast<float*>(p);
+  };
+  h->net.n_layers = d->n_layers;
+  h->net.act = d->act == PAYNE_SPECMLP_SIGMOID ? sj::kActSigmoid : sj::kActLeaky;
+  for (int l = 0; l < d->n_layers; ++l) {
+    const payne_specmlp_layer& L = d->layers[l];
+    std::vector<float> pk(sj::packed_floats(L.n_in, L.n_out));
+    sj::pack_weights(L.w, L.n_in, L.n_out, pk.data());
+    float* w = floats(pk.size());
+    float* b = floats((size_t)sj::pad32(L.n_out));
+    if (ok && (hipMemcpy(w, pk.data(), pk.size() * sizeof(float), hipMemcpyHostToDevice) != hipSuccess ||
+               hipMemcpy(b, L.b, (size_t)L.n_out * sizeof(float), hipMemcpyHostToDevice) != hipSuccess))
+      ok = false;
+    h->net.L[l].w = w;
+    h->net.L[l].b = b;
+    h->net.L[l].n_in = L.n_in;
+    h->net.L[l].n_out = L.n_out;
+  }
+  for (int k = 0; k < sj::kMaxLabels; ++k) {
+    h->net.xmin[k] = k < d_in ? xmin[k] : 0.0;
+    h->net.xmax[k] = k < d_in ? xmax[k] : 1.0;
+    h->net.scale[k] = sj::label_scale(h->net.xmin[k], h->net.xmax[k]);
+  }
+  h->net.a_last = floats((size_t)tiles * sj::kTileRows * (size_t)sj::pad32(d->layers[d->n_layers - 1].n_in));
+  if (ok && payne_specjac_prepare(h->net) != PAYNE_OK) ok = false;
+  (void)hipSetDevice(prev);
+  if (!ok) {
+    payne_specjac_destroy(h);
+    return fail(nullptr, PAYNE_E_HIP, "payne_specjac_create: allocating, copying to the device or reserving LDS failed");
+  }
+  *out = h;
+  return PAYNE_OK;
+}
+
+extern "C" int payne_specjac_eval(payne_specjac* h, const double* labels_dev, int ld_x, int N, float* y_dev, int ld_y, float* jac_dev,
+                                  int ld_j, unsigned flags, void* stream) {
+  namespace sj = payne::specjac;
+  if (!h || N < 0 || (flags & ~PAYNE_JAC_ENCODED)) return PAYNE_E_INVALID;
+  const int d_in = h->net.L[0].n_in, d_out = h->net.L[h->net.n_layers - 1].n_out;
+  if (ld_x < d_in || ld_j < d_out || (y_dev && ld_y < d_out)) return PAYNE_E_INVALID;
+  if (N == 0) return PAYNE_OK;
+  if (!labels_dev || !jac_dev) return PAYNE_E_INVALID;
+  int prev = 0, rc = PAYNE_OK;
+  (void)hipGetDevice(&prev);
+  if (hipSetDevice(h->device) != hipSuccess) return PAYNE_E_HIP;
+  sj::JacNet net = h->net;
+  if (flags & PAYNE_JAC_ENCODED)
+    for (int k = 0; k < sj::kMaxLabels; ++k) net.scale[k] = 1.0f;
+  for (int r0 = 0; r0 < N && !rc; r0 += h->stars) {                 // the workspace's stars a pass
+    const int n = N - r0 < h->stars ? N - r0 : h->stars;
+    rc = payne_specjac_launch(net, labels_dev + (size_t)r0 * (size_t)ld_x, ld_x, n, y_dev ? y_dev + (size_t)r0 * (size_t)ld_y : nullptr, ld_y,
+                              jac_dev + (size_t)r0 * (size_t)d_in * (size_t)ld_j, ld_j, stream);
+  }
+  (void)hipSetDevice(prev);
+  return rc;
+}
+
+extern "C" int payne_fisher_batch(int device, const float* rows_dev, int ld, int K, int n, int B, const double* w_dev, double* F_dev,
+                                  void* stream) {
+  if (K < 1 || n < 1 || B < 0 || ld < n) return PAYNE_E_INVALID;
+  if (K > payne::specjac::kMaxFisherRows) return PAYNE_E_UNSUPPORTED;
+  if (B == 0) return PAYNE_OK;
+  if (!rows_dev || !w_dev || !F_dev) return PAYNE_E_INVALID;
+  int prev = 0;
+  (void)hipGetDevice(&prev);
+  if (hipSetDevice(device) != hipSuccess) return PAYNE_E_HIP;
+  const int rc = payne_fisher_launch(rows_dev, ld, K, n, B, w_dev, F_dev, stream);
+  (void)hipSetDevice(prev);
+  return rc;
+}
 
 // ---- per-kernel timing ---------------------------------------------------------
 extern "C" int payne_profile(payne_ctx* c, int enable) {

@@ -77,6 +77,112 @@ class ContANN(object):
         return out[0] if x.ndim == 1 else out
 
 
+class SpecJacobian(object):
+    """Owner of one ``payne_specjac`` handle (include/payne_hip.h): a spectral network as ``nnio`` normalises it, evaluated
+    together with its Jacobian with respect to the labels.  ``max_rows`` stars are evaluated per pass."""
+
+    def __init__(self, net, max_rows=256, device=None):
+        import ctypes as C
+        import torch
+        from .. import _lib
+        if not torch.cuda.is_available():
+            raise RuntimeError("SpecJacobian needs a ROCm GPU (torch.cuda.is_available() is False); there is no CPU fallback")
+        self.torch = torch
+        self.lib = _lib.load()
+        self.device = torch.device("cuda", torch.cuda.current_device() if device is None else int(device))
+        layers = net["layers"]
+        acts = set(act for W, b, act in layers[:-1])
+        if len(acts) != 1 or layers[-1][2] != _lib.ACT_NONE or not acts <= {_lib.ACT_LRELU, _lib.ACT_SIGMOID}:
+            raise ValueError("the hidden layers share one activation, LeakyReLU or sigmoid, and the last layer has none")
+        d = _lib.SpecmlpDesc()
+        d.n_layers = len(layers)
+        d.act = _lib.SPECMLP_LEAKY if acts == {_lib.ACT_LRELU} else _lib.SPECMLP_SIGMOID
+        keep = []
+        for i, (W, b, act) in enumerate(layers):
+            W, b = np.ascontiguousarray(W, dtype=np.float32), np.ascontiguousarray(b, dtype=np.float32)
+            keep.append((W, b))
+            d.layers[i].n_out, d.layers[i].n_in = W.shape
+            d.layers[i].w, d.layers[i].b = W.ctypes.data, b.ctypes.data
+        self.n_labels, self.npix = keep[0][0].shape[1], keep[-1][0].shape[0]
+        xmin = np.ascontiguousarray(net["xmin"], dtype=np.float64)
+        xmax = np.ascontiguousarray(net["xmax"], dtype=np.float64)
+        if len(xmin) != self.n_labels or len(xmax) != self.n_labels:
+            raise ValueError("xmin / xmax do not have one entry per label")
+        self._h = C.c_void_p()
+        rc = self.lib.payne_specjac_create(self.device.index, C.byref(d), xmin.ctypes.data, xmax.ctypes.data, int(max_rows),
+                                           C.byref(self._h))
+        if rc != 0:
+            raise RuntimeError("payne_specjac_create failed (%d): %s" % (rc, self.lib.payne_last_error(None).decode()))
+
+    def eval(self, labels, encoded=False, want_y=True):
+        """labels [N, D] (raw: Teff in K; a host array or a device tensor) -> (y [N, npix] or None, jac [N, D, npix]) as fp32
+        device tensors: jac[i, k] = dy_i / dlabel_k, or with ``encoded`` the derivative with respect to the encoded label.
+        Enqueued on the current torch stream."""
+        import ctypes as C
+        from .. import _lib
+        torch = self.torch
+        if isinstance(labels, torch.Tensor):
+            x = labels.to(device=self.device, dtype=torch.float64).contiguous()
+        else:
+            x = torch.as_tensor(np.ascontiguousarray(labels, dtype=np.float64)).to(self.device)
+        if x.dim() != 2 or x.shape[1] != self.n_labels:
+            raise ValueError("labels must be [N, %d], got %s" % (self.n_labels, tuple(x.shape)))
+        N = x.shape[0]
+        y = torch.empty((N, self.npix), dtype=torch.float32, device=self.device) if want_y else None
+        jac = torch.empty((N, self.n_labels, self.npix), dtype=torch.float32, device=self.device)
+        rc = self.lib.payne_specjac_eval(self._h, x.data_ptr(), self.n_labels, N, y.data_ptr() if want_y else None, self.npix,
+                                         jac.data_ptr(), self.npix, _lib.JAC_ENCODED if encoded else 0,
+                                         C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream))
+        if rc != 0:
+            raise RuntimeError("payne_specjac_eval failed (%d)" % rc)
+        return y, jac
+
+    def close(self):
+        if getattr(self, "_h", None) is not None and self._h.value:
+            self.torch.cuda.synchronize(self.device)
+            self.lib.payne_specjac_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def smooth_rows(eng, rows, theta, stage):
+    """``eng.smooth_batch`` on derivative rows [B, npix] (device fp32): getspec's stages behind the network are linear in the flux,
+    but the engine carries a spectrum as flux - 1 in fp32, which keeps the precision of a flux of order one and would lose that of
+    a row of order 1e-6 (a derivative per K).  Each row is therefore brought into [1, 2) by a power of two -- exact in both
+    directions -- pushed through, and scaled back."""
+    torch = eng.torch
+    amax = rows.abs().amax(dim=-1, keepdim=True)
+    ok = torch.isfinite(amax) & (amax > 0)
+    s = torch.where(ok, torch.exp2(torch.floor(torch.log2(torch.where(ok, amax, torch.ones_like(amax))))), torch.ones_like(amax))
+    return eng.smooth_batch(rows / s, theta, stage=stage) * s
+
+
+def fisher_batch(rows, w):
+    """F[b, i, j] = sum_p rows[b, i, p] rows[b, j, p] w[p] in fp64 (payne_fisher_batch): rows fp32 device tensor [B, K, n], K <= 16;
+    w fp64 device tensor [n] = 1 / sigma^2, a pixel with w == 0 skipped whatever the rows hold there.  Returns a fp64 device
+    tensor [B, K, K]; enqueued on the current torch stream."""
+    import ctypes as C
+    import torch
+    from .. import _lib
+    lib = _lib.load()
+    if rows.dim() != 3 or w.dim() != 1 or rows.shape[2] != w.shape[0]:
+        raise ValueError("rows must be [B, K, n] and w [n], got %s and %s" % (tuple(rows.shape), tuple(w.shape)))
+    rows = rows.to(dtype=torch.float32).contiguous()
+    w = w.to(device=rows.device, dtype=torch.float64).contiguous()
+    B, K, n = rows.shape
+    F = torch.empty((B, K, K), dtype=torch.float64, device=rows.device)
+    rc = lib.payne_fisher_batch(rows.device.index, rows.data_ptr(), n, K, n, B, w.data_ptr(), F.data_ptr(),
+                                C.c_void_p(torch.cuda.current_stream(rows.device).cuda_stream))
+    if rc != 0:
+        raise RuntimeError("payne_fisher_batch failed (%d)" % rc)
+    return F
+
+
 class PayneSpecPredict(object):
     """Predict spectra from a Payne-learned ANN (drop-in for the reference class)."""
 
@@ -359,6 +465,66 @@ class PayneSpecPredict(object):
 
     def _device_index(self):
         return self.anns.engine.device.index
+
+    # -- new: label gradients ------------------------------------------------------
+    def _jacobian(self):
+        """The network's ``SpecJacobian``, built once per object from the arrays ``nnio`` normalised."""
+        if getattr(self, "_jac", None) is None:
+            self._jac = SpecJacobian(self.anns.net, max_rows=self.anns.engine.b_max, device=self._device_index())
+        return self._jac
+
+    def predictgrad(self, labels):
+        """The raw ANN flux and its derivatives with respect to the labels [Teff, log(g), [Fe/H], [alpha/Fe] (, vmic)]: for one
+        star (flux [npix], dflux [D, npix]), for labels [N, D] ([N, npix], [N, D, npix]).  dflux[k] is per unit of label k (per K
+        for Teff).  A device tensor in gives fp32 device tensors out; anything else gives numpy arrays of ``predictspec``'s type."""
+        import torch
+        on_device = isinstance(labels, torch.Tensor)
+        x = labels if on_device else np.asarray(labels, dtype=np.float64)
+        one = x.ndim == 1
+        y, jac = self._jacobian().eval(x.reshape(1, -1) if one else x)
+        if not on_device:
+            y, jac = y.cpu().numpy(), jac.cpu().numpy()
+            if self.NNtype in ("YST1", "YST2"):
+                y, jac = y.astype(np.float64), jac.astype(np.float64)
+        return (y[0], jac[0]) if one else (y, jac)
+
+    def _check_linear(self, kwargs):
+        """What getgrad differentiates is the spectral network's output pushed through getspec's linear stages; the continuum
+        network makes the model a product and an LSF vector is not pushed through here."""
+        if self.Canns is not None:
+            raise NotImplementedError("getgrad with a continuum network (Cnnpath): the model is a product of two networks")
+        if 'inst_R' in kwargs and not isinstance(kwargs['inst_R'], float):
+            raise NotImplementedError("getgrad: inst_R must be a Python float (sigma-based R); anything else is an LSF vector to "
+                                      "getspec (ystpred.py:248-269), which getgrad does not push the rows through")
+
+    def getgrad(self, **kwargs):
+        """(wave, flux, dflux [D, nout]) for one parameter set, kwargs as getspec's: flux is getspec's own result and dflux[k] its
+        derivative with respect to label k of [Teff, log(g), [Fe/H], [alpha/Fe] (, vmic)].  Everything getspec does after the
+        network is linear in the flux (ystpred.py:211-277), so the rows are the network's Jacobian pushed through the same
+        stages with the star's own Vrad, Vrot and inst_R.  NaN where flux is NaN."""
+        self._check_linear(kwargs)
+        wave, flux = self.getspec(**kwargs)
+        eng = self.anns.engine
+        d = self.inputdict
+        labels = [d['teff'], d['logg'], d['feh'], d['afe']] + ([d['vmic']] if self.anns.n_labels == 5 else [])
+        _, jac = self._jacobian().eval(np.array([labels], dtype=np.float64), want_y=False)
+        D = jac.shape[1]
+        outwave = kwargs.get('outwave', None)
+        has_R = 'inst_R' in kwargs
+        th = np.full((D, eng.ncols), np.nan)
+        th[:, :8] = [d['teff'], d['logg'], d['feh'], d['afe'], kwargs.get('rad_vel', 0.0), kwargs.get('rot_vel', 0.0), d['vmic'],
+                     kwargs['inst_R'] if has_R else np.nan]
+        if outwave is None and not (has_R and kwargs['inst_R'] > 0.0):
+            dflux = smooth_rows(eng, jac[0], th, 1).cpu().numpy().astype(np.float64)
+            if kwargs.get('rot_vel', 0.0) != 0.0:                       # ystpred.py:223-224 (stage 1 of smooth_batch is smoothspec alone)
+                dflux[:, 0], dflux[:, -1] = dflux[:, 1], dflux[:, -2]
+            return wave, flux, dflux
+        self._bind(np.ascontiguousarray(wave, dtype=np.float64))       # (getspec bound this grid; the key matches)
+        dflux = smooth_rows(eng, jac[0], th, 2).cpu().numpy().astype(np.float64)
+        if outwave is None:
+            for row in dflux:
+                native_grid_edges(wave, row)
+        return wave, flux, dflux
 
     # -- new: batch API ------------------------------------------------------------
     def getspec_batch(self, theta8, outwave, stage=2):
