@@ -146,7 +146,7 @@ void forward_backward(const ln::TrainNet& net, const float* x, int ld_x, const f
   }
 }
 
-// payne_lnmlp_dw_kernel and payne_lnmlp_update_kernel
+// payne_mlp_dw_kernel and payne_mlp_update_kernel (csrc/mlp_train_tail.hpp)
 void update(const ln::TrainNet& net, int N, const ln::RadamStep& rs) {
   const int tiles = (N + ln::kTileRows - 1) / ln::kTileRows, rows = tiles * ln::kTileRows;
   for (int l = 0; l < net.n_layers; ++l) {

@@ -152,7 +152,7 @@ void backward(const sp::SpecNet& net, int N) {
   }
 }
 
-// payne_specmlp_dw_kernel and the update kernel's slab sums
+// payne_mlp_dw_kernel and the update kernel's slab sums (csrc/mlp_train_tail.hpp)
 void gradients(const sp::SpecNet& net, int N) {
   const int tiles = (N + sp::kTileRows - 1) / sp::kTileRows, rows = tiles * sp::kTileRows;
   for (int l = 0; l < net.n_layers; ++l) {

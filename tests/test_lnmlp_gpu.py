@@ -272,6 +272,7 @@ def test_return_codes_without_a_launch(lib, g18):
     for dims in ([6, 513, 8], [6, 16, 513], [33, 16, 8], [6, 8]):                   # a width of 513, 33 inputs, one layer
         rc, hh = create(lib, net(dims))
         assert rc == _lib.E_UNSUPPORTED and not hh.value, dims
+        assert lib.payne_last_error(None).startswith(b"payne_lnmlp_create: "), dims    # the message of a create that had no context
     d, keep = make_desc(net([6] + [8] * 8))
     d.n_layers = 9                                                                 # nine layers
     assert lib.payne_lnmlp_create(0, C.byref(d), C.byref(C.c_void_p())) == _lib.E_UNSUPPORTED

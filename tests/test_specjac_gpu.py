@@ -177,6 +177,7 @@ def test_invalid_and_unsupported_arguments(lib, g20):
     assert rc_create(edit=lambda d: setattr(d, "n_layers", 9)) == _lib.E_UNSUPPORTED
     assert rc_create(layers=random_net(rng, [9, 8, 10])) == _lib.E_UNSUPPORTED
     assert rc_create(layers=random_net(rng, [4, 513, 10])) == _lib.E_UNSUPPORTED
+    assert lib.payne_last_error(None).startswith(b"payne_specjac_create: ")        # the message of a create that had no context
     assert rc_create(layers=random_net(rng, [4, 512, 10])) == 0 and h.value
     lib.payne_specjac_destroy(h)
     assert rc_create(layers=random_net(rng, [8, 2, 10])) == 0 and h.value

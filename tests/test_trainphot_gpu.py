@@ -297,6 +297,7 @@ def test_return_codes_without_a_launch(lib, g19):
     for dims in ([6, 513, 8], [6, 16, 513], [33, 16, 8], [6, 8]):                                 # the forward's limits
         rc, hh = make_trainer(lib, random_net(rng, dims))
         assert rc == _lib.E_UNSUPPORTED and not hh.value, dims
+        assert lib.payne_last_error(None).startswith(b"payne_lnmlp_train_create: "), dims         # the message of a create that had no context
     d, keep = make_desc(random_net(rng, [6] + [8] * 8))
     d.n_layers = 9
     o = _lib.LnmlpTrainOpts()

@@ -316,6 +316,7 @@ def test_return_codes_without_a_launch(lib, g20):
     for dims in ([6, 513, 8], [33, 16, 8], [6, 8], [6, 16, 65537]):                               # the limits
         rc, hh = make_trainer(lib, random_net(rng, dims), "SMLP", max_rows=8)
         assert rc == _lib.E_UNSUPPORTED and not hh.value, dims
+        assert lib.payne_last_error(None).startswith(b"payne_specmlp_train_create: "), dims       # the message of a create that had no context
     rc, hh = make_trainer(lib, random_net(rng, [32, 512, 513]), "LinNet", max_rows=8)             # D_out alone may pass 512
     assert rc == 0
     lib.payne_specmlp_train_destroy(hh)

@@ -5,12 +5,9 @@
 //   One 256-thread workgroup per 64 rows of x.  The rows' activations live in LDS, fp32 [64][stride], from the input
 //   conversion to the last layer's output; stride = the widest padded row + 4 floats, so that the 16-byte operand reads of 16
 //   rows and the 4-byte LayerNorm reads of 8 rows x 4 threads fall on different banks.
-//   A layer: wave w owns the 32-column tiles w, w + 4, ... of the layer's output (NT of them at most, the template argument)
-//   for both 32-row halves: 2 NT accumulators of v_mfma_f32_32x32x2_f32, exact fp32, one tile column after the other.  Per
-//   block of 8 inputs a lane reads 16 bytes of each half's activations from LDS and 16 bytes of the tile's weights from
-//   global memory (the stored order of lnmlp_core.hpp: 1 KiB contiguous per wave; a layer is at most 256 KiB, the same for
-//   every workgroup, so it stays in L2), four matrix steps on each half; the blocks go two a turn, each one's operands
-//   requested before the other's matrix steps are issued, so a load has eight matrix steps to arrive behind.
+//   A layer: the product of the image with the layer's stored weights is mlp_tile.hpp's tile_product (wave w owns the 32-column
+//   tiles w, w + 4, ..., NT of them at most, the template argument; a layer is at most 256 KiB, the same for every workgroup, so
+//   it stays in L2).
 //   After the last block: barrier (every wave has read the image), bias added and the tiles written over the image, barrier,
 //   then four threads a row take LayerNorm's two sums over the row's true width and apply gain, bias and SiLU to every
 //   fourth element in place, barrier.  After the last layer the image's first D_out columns go to y instead, through the
@@ -20,12 +17,11 @@
 
 #include "../../include/payne_hip.h"
 #include "lnmlp_core.hpp"
+#include "mlp_tile.hpp"
 
 using namespace payne;
 
 namespace {
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 template <int NT>
 __global__ void __launch_bounds__(lnmlp::kThreads) payne_lnmlp_kernel(const double* __restrict__ x, long long ld_x, int N,
@@ -48,80 +44,11 @@ __global__ void __launch_bounds__(lnmlp::kThreads) payne_lnmlp_kernel(const doub
   }
   __syncthreads();
 
-  // this lane's operand rows: row (lane & 31) of either half, inputs 4 (lane >> 5) .. + 3 of a block
-  const float* a_lo = act + (lane & 31) * stride + 4 * (lane >> 5);
-  const float* a_hi = a_lo + lnmlp::kTile * stride;
-
   for (int l = 0; l < net.n_layers; ++l) {
     const lnmlp::LayerArgs L = net.L[l];
     const int KB = lnmlp::k_blocks(L.n_in), nct = lnmlp::col_tiles(L.n_out);
     const bool last = l + 1 == net.n_layers;
-
-    f32x16 acc[NT][2];
-#pragma unroll
-    for (int t = 0; t < NT; ++t)
-#pragma unroll
-      for (int h = 0; h < 2; ++h)
-#pragma unroll
-        for (int i = 0; i < 16; ++i) acc[t][h][i] = 0.0f;
-
-    // one tile column at a time: both halves' accumulators, the block's eight inputs of either half re-read from LDS
-#pragma unroll
-    for (int t = 0; t < NT; ++t) {
-      const int ct = wave + lnmlp::kWaves * t;
-      if (ct < nct) {                                               // (the same in every lane of the wave)
-        const float* wp = L.w + lnmlp::packed_index(ct, 0, lane, 0, KB);
-        f32x16 c0 = acc[t][0], c1 = acc[t][1];
-        // two blocks a turn, P and Q: each one's operands are requested before the other's matrix steps are issued
-        auto ld = [&](int kb, float4& lo, float4& hi, float4& wv) {
-          lo = *reinterpret_cast<const float4*>(a_lo + kb * lnmlp::kKBlock);
-          hi = *reinterpret_cast<const float4*>(a_hi + kb * lnmlp::kKBlock);
-          wv = *reinterpret_cast<const float4*>(wp + (size_t)kb * (lnmlp::kWave * 4));
-        };
-        auto steps = [&](const float4& lo, const float4& hi, const float4& wv) {
-          c0 = __builtin_amdgcn_mfma_f32_32x32x2f32(lo.x, wv.x, c0, 0, 0, 0);
-          c1 = __builtin_amdgcn_mfma_f32_32x32x2f32(hi.x, wv.x, c1, 0, 0, 0);
-          c0 = __builtin_amdgcn_mfma_f32_32x32x2f32(lo.y, wv.y, c0, 0, 0, 0);
-          c1 = __builtin_amdgcn_mfma_f32_32x32x2f32(hi.y, wv.y, c1, 0, 0, 0);
-          c0 = __builtin_amdgcn_mfma_f32_32x32x2f32(lo.z, wv.z, c0, 0, 0, 0);
-          c1 = __builtin_amdgcn_mfma_f32_32x32x2f32(hi.z, wv.z, c1, 0, 0, 0);
-          c0 = __builtin_amdgcn_mfma_f32_32x32x2f32(lo.w, wv.w, c0, 0, 0, 0);
-          c1 = __builtin_amdgcn_mfma_f32_32x32x2f32(hi.w, wv.w, c1, 0, 0, 0);
-        };
-        float4 plo, phi, pw, qlo, qhi, qw;
-        ld(0, plo, phi, pw);
-        for (int kb = 0; kb < KB; kb += 2) {
-          const bool two = kb + 1 < KB;
-          ld(two ? kb + 1 : kb, qlo, qhi, qw);
-          __builtin_amdgcn_sched_barrier(0);
-          steps(plo, phi, pw);
-          __builtin_amdgcn_sched_barrier(0);
-          ld(kb + 2 < KB ? kb + 2 : kb, plo, phi, pw);
-          __builtin_amdgcn_sched_barrier(0);
-          if (two) steps(qlo, qhi, qw);
-          __builtin_amdgcn_sched_barrier(0);
-        }
-        acc[t][0] = c0;
-        acc[t][1] = c1;
-      }
-    }
-
-    __syncthreads();                                                // every wave has read the image it is about to overwrite
-#pragma unroll
-    for (int t = 0; t < NT; ++t) {
-      const int ct = wave + lnmlp::kWaves * t;
-      if (ct < nct) {
-        const int col = ct * lnmlp::kTile + (lane & 31);
-        const float bias = L.b[col];
-        float* zc = act + 4 * (lane >> 5) * stride + col;
-#pragma unroll
-        for (int h = 0; h < 2; ++h)
-#pragma unroll
-          for (int i = 0; i < 16; ++i)                              // the instruction's result map: column on the lane, rows in the registers
-            zc[(h * lnmlp::kTile + (i & 3) + 8 * (i >> 2)) * stride] = acc[t][h][i] + bias;
-      }
-    }
-    __syncthreads();
+    mlp::tile_product<NT>(act, stride, L.w, KB, nct, L.b, lane, wave);
 
     if (last) {  // the image's first D_out columns to y through the output conversion, rows below N only
       const int n = L.n_out;
@@ -165,7 +92,7 @@ int launch(const double* x, int ld_x, int N, float* y, int ld_y, const lnmlp::Ne
 
 }  // namespace
 
-// Called by payne_lnmlp_eval (payne_hip.hip) with checked arguments, N >= 1, on the handle's device.
+// Called by payne_lnmlp_eval (mlp_api.hip) with checked arguments, N >= 1, on the handle's device.
 int payne_lnmlp_launch(const lnmlp::NetArgs& net, const double* x, int ld_x, int N, float* y, int ld_y, void* stream) {
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   int max_ct = 0;
@@ -173,7 +100,5 @@ int payne_lnmlp_launch(const lnmlp::NetArgs& net, const double* x, int ld_x, int
     const int c = lnmlp::col_tiles(net.L[l].n_out);
     max_ct = c > max_ct ? c : max_ct;
   }
-  if (max_ct <= lnmlp::kWaves) return launch<1>(x, ld_x, N, y, ld_y, net, st);
-  if (max_ct <= 2 * lnmlp::kWaves) return launch<2>(x, ld_x, N, y, ld_y, net, st);
-  return launch<4>(x, ld_x, N, y, ld_y, net, st);
+  return mlp::with_tiles_per_wave(max_ct, [&](auto nt) { return launch<decltype(nt)::value>(x, ld_x, N, y, ld_y, net, st); });
 }

@@ -1,7 +1,7 @@
 // k_specjac.hip -- the spectral networks' output together with its Jacobian with respect to the labels (payne_specjac_eval), and
 // the Fisher matrices of rows of such derivatives (payne_fisher_batch).  The arithmetic is specjac_core.hpp, which runs on the
-// host too (tests/emul/specjac_emul.cpp).  The matrix product is k_specmlp_train.hip's (tile_mac / tile_store), written here again:
-// that unit stays as it is, and this one adds the bias to a tile's primal rows only.
+// host too (tests/emul/specjac_emul.cpp).  The matrix product is mlp_tile.hpp's; this unit has the bias added to a tile's primal
+// rows only.
 //
 //   payne_specjac_hidden_kernel  one 256-thread workgroup per S = 64 / (1 + D_in) stars, k_lnmlp.hip's tile and LDS image: fp32
 //     [64][stride].  Row m * S + s is star s's primal (m = 0: the encoded labels) or its tangent of label m - 1 (the unit vector), so
@@ -18,101 +18,12 @@
 
 #include "../../include/payne_hip.h"
 #include "specjac_core.hpp"
+#include "mlp_tile.hpp"
 
 using namespace payne;
 namespace sj = payne::specjac;
 
 namespace {
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-
-template <int NT>
-struct TileAcc {
-  f32x16 v[NT][2];
-};
-
-template <int NT>
-__device__ __forceinline__ void tile_zero(TileAcc<NT>& acc) {
-#pragma unroll
-  for (int t = 0; t < NT; ++t)
-#pragma unroll
-    for (int h = 0; h < 2; ++h)
-#pragma unroll
-      for (int i = 0; i < 16; ++i) acc.v[t][h][i] = 0.0f;
-}
-
-// acc += act[64][8 KB inputs a row] times the stored weights w (KB k-blocks a column tile), wave `wave` on the column tiles wave,
-// wave + 4, ... below nct: the matrix steps of k_lnmlp.hip's layer product in its order.  Reads the image only; no barrier.
-template <int NT>
-__device__ __forceinline__ void tile_mac(TileAcc<NT>& acc, const float* act, int stride, const float* __restrict__ w, int KB, int nct,
-                                         int lane, int wave) {
-  const float* a_lo = act + (lane & 31) * stride + 4 * (lane >> 5);
-  const float* a_hi = a_lo + sj::kTile * stride;
-#pragma unroll
-  for (int t = 0; t < NT; ++t) {
-    const int ct = wave + sj::kWaves * t;
-    if (ct < nct) {
-      const float* wp = w + sj::packed_index(ct, 0, lane, 0, KB);
-      f32x16 c0 = acc.v[t][0], c1 = acc.v[t][1];
-      auto ld = [&](int kb, float4& lo, float4& hi, float4& wv) {
-        lo = *reinterpret_cast<const float4*>(a_lo + kb * sj::kKBlock);
-        hi = *reinterpret_cast<const float4*>(a_hi + kb * sj::kKBlock);
-        wv = *reinterpret_cast<const float4*>(wp + (size_t)kb * (sj::kWave * 4));
-      };
-      auto steps = [&](const float4& lo, const float4& hi, const float4& wv) {
-        c0 = __builtin_amdgcn_mfma_f32_32x32x2f32(lo.x, wv.x, c0, 0, 0, 0);
-        c1 = __builtin_amdgcn_mfma_f32_32x32x2f32(hi.x, wv.x, c1, 0, 0, 0);
-        c0 = __builtin_amdgcn_mfma_f32_32x32x2f32(lo.y, wv.y, c0, 0, 0, 0);
-        c1 = __builtin_amdgcn_mfma_f32_32x32x2f32(hi.y, wv.y, c1, 0, 0, 0);
-        c0 = __builtin_amdgcn_mfma_f32_32x32x2f32(lo.z, wv.z, c0, 0, 0, 0);
-        c1 = __builtin_amdgcn_mfma_f32_32x32x2f32(hi.z, wv.z, c1, 0, 0, 0);
-        c0 = __builtin_amdgcn_mfma_f32_32x32x2f32(lo.w, wv.w, c0, 0, 0, 0);
-        c1 = __builtin_amdgcn_mfma_f32_32x32x2f32(hi.w, wv.w, c1, 0, 0, 0);
-      };
-      float4 plo, phi, pw, qlo, qhi, qw;
-      ld(0, plo, phi, pw);
-      for (int kb = 0; kb < KB; kb += 2) {                          // two blocks a turn, as in k_lnmlp.hip
-        const bool two = kb + 1 < KB;
-        ld(two ? kb + 1 : kb, qlo, qhi, qw);
-        __builtin_amdgcn_sched_barrier(0);
-        steps(plo, phi, pw);
-        __builtin_amdgcn_sched_barrier(0);
-        ld(kb + 2 < KB ? kb + 2 : kb, plo, phi, pw);
-        __builtin_amdgcn_sched_barrier(0);
-        if (two) steps(qlo, qhi, qw);
-        __builtin_amdgcn_sched_barrier(0);
-      }
-      acc.v[t][0] = c0;
-      acc.v[t][1] = c1;
-    }
-  }
-}
-
-// The tile row of accumulator element i of half h in this lane (the matrix instruction's output layout)
-__device__ __forceinline__ int acc_row(int h, int i, int lane) { return h * sj::kTile + (i & 3) + 8 * (i >> 2) + 4 * (lane >> 5); }
-
-// The accumulators into the image, columns 32 ct .. of act[64][stride]; the bias is added to the rows below `bias_rows` (a tile's
-// primal rows).  The caller puts a barrier before (every wave has read the image) and after.
-template <int NT>
-__device__ __forceinline__ void tile_store(const TileAcc<NT>& acc, float* act, int stride, int nct, const float* __restrict__ bias,
-                                           int bias_rows, int lane, int wave) {
-#pragma unroll
-  for (int t = 0; t < NT; ++t) {
-    const int ct = wave + sj::kWaves * t;
-    if (ct < nct) {
-      const int col = ct * sj::kTile + (lane & 31);
-      const float b = bias[col];
-#pragma unroll
-      for (int h = 0; h < 2; ++h)
-#pragma unroll
-        for (int i = 0; i < 16; ++i) {
-          const int r = acc_row(h, i, lane);
-          const float v = acc.v[t][h][i];
-          act[r * stride + col] = r < bias_rows ? v + b : v;
-        }
-    }
-  }
-}
 
 // ---- launch 1: the hidden layers, primal and tangents ------------------------------------------------------------------------
 template <int NT>
@@ -133,13 +44,7 @@ __global__ void __launch_bounds__(sj::kThreads) payne_specjac_hidden_kernel(cons
   __syncthreads();
   for (int l = 0; l + 1 < net.n_layers; ++l) {
     const sj::JacLayer& L = net.L[l];
-    const int nct = sj::col_tiles(L.n_out);
-    TileAcc<NT> acc;
-    tile_zero(acc);
-    tile_mac<NT>(acc, act, stride, L.w, sj::k_blocks(L.n_in), nct, lane, wave);
-    __syncthreads();                                                // every wave has read the image it is about to overwrite
-    tile_store<NT>(acc, act, stride, nct, L.b, S, lane, wave);
-    __syncthreads();
+    mlp::tile_product<NT>(act, stride, L.w, sj::k_blocks(L.n_in), sj::col_tiles(L.n_out), L.b, lane, wave, S);
     for (int idx = tid; idx < S * L.n_out; idx += sj::kThreads) {   // one thread a (star, unit); the padding columns stay zero
       const int s = idx / L.n_out, j = idx - s * L.n_out;
       sj::unit_forward(act + s * stride + j, act + (S + s) * stride + j, S * stride, d_in, net.act);
@@ -175,9 +80,9 @@ __global__ void __launch_bounds__(sj::kThreads) payne_specjac_out_kernel(float* 
   __syncthreads();
   const int ct = blockIdx.y * sj::kWaves + wave;
   if (ct >= sj::col_tiles(d_out)) return;
-  TileAcc<1> acc;
-  tile_zero(acc);
-  tile_mac<1>(acc, act, stride, L.w + sj::packed_index(ct, 0, 0, 0, KB), KB, 1, lane, 0);   // (this wave's one column tile)
+  mlp::TileAcc<1> acc;
+  mlp::tile_zero(acc);
+  mlp::tile_mac<1>(acc, act, stride, L.w + sj::packed_index(ct, 0, 0, 0, KB), KB, 0, KB, 1, lane, 0);   // (this wave's one column tile)
   const int col = ct * sj::kTile + (lane & 31);
   if (col >= d_out) return;
   const float b = L.b[col];
@@ -186,7 +91,7 @@ __global__ void __launch_bounds__(sj::kThreads) payne_specjac_out_kernel(float* 
   for (int h = 0; h < 2; ++h)
 #pragma unroll
     for (int i = 0; i < 16; ++i)
-      sj::store_output(acc.v[0][h][i], acc_row(h, i, lane), d_in, star0, N, col, b, net.scale, y, ld_y, jac, ld_j);
+      sj::store_output(acc.v[0][h][i], mlp::acc_row(h, i, lane), d_in, star0, N, col, b, net.scale, y, ld_y, jac, ld_j);
 }
 
 // ---- Fisher matrices -----------------------------------------------------------------------------------------------------
@@ -235,11 +140,11 @@ int launch_hidden(const sj::JacNet& net, const double* x, int ld_x, int N, int s
   return hipGetLastError() == hipSuccess ? PAYNE_OK : PAYNE_E_HIP;
 }
 
-// column tiles a wave of the hidden launch: 1, 2 or 4
-int hidden_form(const sj::JacNet& net) {
+// the widest hidden layer's column tiles
+int hidden_tiles(const sj::JacNet& net) {
   int m = 0;
   for (int l = 0; l + 1 < net.n_layers; ++l) m = sj::max_of(m, sj::col_tiles(net.L[l].n_out));
-  return m <= sj::kWaves ? 1 : m <= 2 * sj::kWaves ? 2 : 4;
+  return m;
 }
 size_t hidden_lds(const sj::JacNet& net) { return (size_t)sj::kTileRows * (size_t)sj::jac_hidden_stride(net) * sizeof(float); }
 size_t out_lds(const sj::JacNet& net) { return (size_t)sj::kTileRows * (size_t)sj::jac_out_stride(net) * sizeof(float); }
@@ -248,22 +153,20 @@ size_t out_lds(const sj::JacNet& net) { return (size_t)sj::kTileRows * (size_t)s
 
 // Called once by payne_specjac_create on the handle's device: the two kernels this network launches may use their images' LDS.
 int payne_specjac_prepare(const sj::JacNet& net) {
-  const int form = hidden_form(net);
   const size_t lds = hidden_lds(net);
-  const int rc = form == 1 ? prepare_hidden<1>(lds) : form == 2 ? prepare_hidden<2>(lds) : prepare_hidden<4>(lds);
+  const int rc = mlp::with_tiles_per_wave(hidden_tiles(net), [&](auto nt) { return prepare_hidden<decltype(nt)::value>(lds); });
   if (rc) return rc;
   return hipFuncSetAttribute(reinterpret_cast<const void*>(payne_specjac_out_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
                              (int)out_lds(net)) == hipSuccess ? PAYNE_OK : PAYNE_E_HIP;
 }
 
-// Called by payne_specjac_eval (payne_hip.hip) with checked arguments, 1 <= N <= the stars the workspace holds, on the handle's
+// Called by payne_specjac_eval (mlp_api.hip) with checked arguments, 1 <= N <= the stars the workspace holds, on the handle's
 // device: y [N][ld_y] (or NULL) and jac [N][D_in][ld_j] of the N stars x [N][ld_x].
 int payne_specjac_launch(const sj::JacNet& net, const double* x, int ld_x, int N, float* y, int ld_y, float* jac, int ld_j, void* stream) {
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  const int form = hidden_form(net), stride = sj::jac_hidden_stride(net);
+  const int stride = sj::jac_hidden_stride(net);
   const size_t lds = hidden_lds(net);
-  const int rc = form == 1 ? launch_hidden<1>(net, x, ld_x, N, stride, lds, st)
-                           : form == 2 ? launch_hidden<2>(net, x, ld_x, N, stride, lds, st) : launch_hidden<4>(net, x, ld_x, N, stride, lds, st);
+  const int rc = mlp::with_tiles_per_wave(hidden_tiles(net), [&](auto nt) { return launch_hidden<decltype(nt)::value>(net, x, ld_x, N, stride, lds, st); });
   if (rc) return rc;
   const dim3 grid((unsigned)sj::tiles_of(N, net.L[0].n_in), (unsigned)sj::out_chunks(net.L[net.n_layers - 1].n_out));
   hipLaunchKernelGGL(payne_specjac_out_kernel, grid, dim3(sj::kThreads), out_lds(net), st, y, (long long)ld_y, jac, (long long)ld_j, N,

@@ -159,6 +159,7 @@ struct TrainLayer {
   float p;                                                        // dropout after this block, 0 = none
 };
 struct TrainNet {
+  static constexpr int kHiddenVecs = 3;                           // per-column vectors of a hidden layer; the slabs' stride
   int n_layers;
   TrainLayer L[kMaxLayers];
   double* loss_slab;                                              // [tiles]

@@ -31,6 +31,7 @@
 #include "post_seq.hpp"
 #include "ns_core.hpp"
 #include "queue_block.hpp"
+#include "api_error.hpp"
 
 using namespace payne;
 
@@ -40,10 +41,6 @@ using namespace payne;
 
 #include "sed_kernel.hpp"
 #include "select.hpp"
-#include "lnmlp_core.hpp"
-#include "lnmlp_train_core.hpp"
-#include "specmlp_train_core.hpp"
-#include "specjac_core.hpp"
 
 // photometry-only fits: lnL = -0.5 chi2_sed
 __global__ void payne_photonly_kernel(const double* mags, const double* obs, const double* err, int F, int B, double* lnl) {
@@ -225,8 +222,9 @@ static int dev_alloc(payne_ctx* c, size_t n, V** out, std::vector<void*>& bag, b
   return PAYNE_OK;
 }
 
+void payne::set_create_error(const std::string& msg) { g_create_error = msg; }
 static int fail(payne_ctx* c, int code, const std::string& msg) {
-  if (c) c->err = msg; else g_create_error = msg;
+  if (c) c->err = msg; else set_create_error(msg);
   return code;
 }
 
@@ -2064,669 +2062,6 @@ extern "C" int payne_bc_batch(payne_ctx* c, const double* x, int B, double* bc, 
   if (rc) return rc;
   if (!c->has_phot) return fail(c, PAYNE_E_INVALID, "context has no photometric model");
   return run_sed(c, x, 6, 2, B, bc, reinterpret_cast<hipStream_t>(stream));
-}
-
-// ---- photometric LayerNorm + SiLU networks (photANN_new): the handle; the kernel is k_lnmlp.hip ---------------------------
-int payne_lnmlp_launch(const payne::lnmlp::NetArgs& net, const double* x, int ld_x, int N, float* y, int ld_y, void* stream);
-
-struct payne_lnmlp {
-  int device = 0;
-  payne::lnmlp::NetArgs net{};
-  std::vector<void*> owned;
-};
-
-extern "C" void payne_lnmlp_destroy(payne_lnmlp* h) {
-  if (!h) return;
-  int prev = 0;
-  (void)hipGetDevice(&prev);
-  if (hipSetDevice(h->device) == hipSuccess)
-    for (void* p : h->owned) (void)hipFree(p);
-  (void)hipSetDevice(prev);
-  delete h;
-}
-
-extern "C" int payne_lnmlp_create(int device, const payne_lnmlp_desc* d, payne_lnmlp** out) {
-  namespace ln = payne::lnmlp;
-  static_assert(PAYNE_LNMLP_MAX_LAYERS == ln::kMaxLayers && PAYNE_LNMLP_MAX_IN == ln::kMaxIn && PAYNE_LNMLP_MAX_WIDTH == ln::kMaxWidth,
-                "payne_hip.h and lnmlp_core.hpp disagree on the limits");
-  if (!d || !out) return fail(nullptr, PAYNE_E_INVALID, "payne_lnmlp_create: null descriptor or handle pointer");
-  *out = nullptr;
-  if (d->n_layers < 2 || d->n_layers > ln::kMaxLayers) return fail(nullptr, PAYNE_E_UNSUPPORTED, "payne_lnmlp_create: 2 to 8 linear layers");
-  for (int l = 0; l < d->n_layers; ++l) {
-    const payne_lnmlp_layer& L = d->layers[l];
-    const bool last = l + 1 == d->n_layers;
-    if (L.n_in < 1 || L.n_out < 1 || !L.w || !L.b || (l > 0 && L.n_in != d->layers[l - 1].n_out))
-      return fail(nullptr, PAYNE_E_INVALID, "payne_lnmlp_create: layer " + std::to_string(l) + ": bad widths or null weights");
-    if (last ? (L.ln_gain || L.ln_bias) : (!L.ln_gain || !L.ln_bias))
-      return fail(nullptr, PAYNE_E_INVALID, "payne_lnmlp_create: LayerNorm gain and bias on every layer but the last");
-  }
-  if (!d->in_mid != !d->in_std || !d->out_mid != !d->out_std)
-    return fail(nullptr, PAYNE_E_INVALID, "payne_lnmlp_create: a normalisation needs both mid and std");
-  if (d->layers[0].n_in > ln::kMaxIn) return fail(nullptr, PAYNE_E_UNSUPPORTED, "payne_lnmlp_create: more than 32 inputs");
-  for (int l = 0; l < d->n_layers; ++l)
-    if (d->layers[l].n_out > ln::kMaxWidth) return fail(nullptr, PAYNE_E_UNSUPPORTED, "payne_lnmlp_create: a width above 512");
-
-  int prev = 0;
-  (void)hipGetDevice(&prev);
-  if (hipSetDevice(device) != hipSuccess) return fail(nullptr, PAYNE_E_HIP, "payne_lnmlp_create: hipSetDevice");
-  payne_lnmlp* h = new payne_lnmlp;
-  h->device = device;
-  bool ok = true;
-  auto upload = [&](const void* src, size_t bytes) -> void* {
-    void* p = nullptr;
-    if (!ok || hipMalloc(&p, bytes) != hipSuccess) { ok = false; return nullptr; }
-    h->owned.push_back(p);
-    if (hipMemcpy(p, src, bytes, hipMemcpyHostToDevice) != hipSuccess) ok = false;
-    return p;
-  };
-  auto padded = [&](const float* src, int n, int n_pad) {
-    std::vector<float> v((size_t)n_pad, 0.0f);
-    memcpy(v.data(), src, (size_t)n * sizeof(float));
-    return static_cast<const float*>(upload(v.data(), v.size() * sizeof(float)));
-  };
-  h->net.n_layers = d->n_layers;
-  for (int l = 0; l < d->n_layers; ++l) {
-    const payne_lnmlp_layer& L = d->layers[l];
-    ln::LayerArgs& A = h->net.L[l];
-    const int n_pad = ln::col_tiles(L.n_out) * ln::kTile;
-    std::vector<float> pk(ln::packed_floats(L.n_in, L.n_out));
-    ln::pack_weights(L.w, L.n_in, L.n_out, pk.data());
-    A.w = static_cast<const float*>(upload(pk.data(), pk.size() * sizeof(float)));
-    A.b = padded(L.b, L.n_out, n_pad);
-    A.gain = L.ln_gain ? padded(L.ln_gain, L.n_out, n_pad) : nullptr;
-    A.beta = L.ln_bias ? padded(L.ln_bias, L.n_out, n_pad) : nullptr;
-    A.n_in = L.n_in;
-    A.n_out = L.n_out;
-  }
-  const int d_in = d->layers[0].n_in, d_out = d->layers[d->n_layers - 1].n_out;
-  if (d->in_mid) {
-    h->net.in_mid = static_cast<const double*>(upload(d->in_mid, (size_t)d_in * sizeof(double)));
-    h->net.in_std = static_cast<const double*>(upload(d->in_std, (size_t)d_in * sizeof(double)));
-  }
-  if (d->out_mid) {
-    h->net.out_mid = static_cast<const double*>(upload(d->out_mid, (size_t)d_out * sizeof(double)));
-    h->net.out_std = static_cast<const double*>(upload(d->out_std, (size_t)d_out * sizeof(double)));
-  }
-  (void)hipSetDevice(prev);
-  if (!ok) {
-    payne_lnmlp_destroy(h);
-    return fail(nullptr, PAYNE_E_HIP, "payne_lnmlp_create: copying the network to the device failed");
-  }
-  *out = h;
-  return PAYNE_OK;
-}
-
-extern "C" int payne_lnmlp_eval(payne_lnmlp* h, const double* x_dev, int ld_x, int N, float* y_dev, int ld_y, void* stream) {
-  if (!h || N < 0) return PAYNE_E_INVALID;
-  if (ld_x < h->net.L[0].n_in || ld_y < h->net.L[h->net.n_layers - 1].n_out) return PAYNE_E_INVALID;
-  if (N == 0) return PAYNE_OK;
-  if (!x_dev || !y_dev) return PAYNE_E_INVALID;
-  int prev = 0;
-  (void)hipGetDevice(&prev);
-  if (hipSetDevice(h->device) != hipSuccess) return PAYNE_E_HIP;
-  const int rc = payne_lnmlp_launch(h->net, x_dev, ld_x, N, y_dev, ld_y, stream);
-  (void)hipSetDevice(prev);
-  return rc;
-}
-
-// ---- training the photometric networks (trainphot.TrainMod): the handle; the kernels are k_lnmlp_train.hip ----------------
-int payne_lnmlp_train_launch(const payne::lnmlp::TrainNet& net, const float* x, int ld_x, const float* t, int ld_t, int N, int train,
-                             unsigned long long seed, unsigned long long step, float scale, void* stream);
-int payne_lnmlp_train_update(const payne::lnmlp::TrainNet& net, int N, const payne::lnmlp::RadamStep& rs, void* stream);
-int payne_lnmlp_train_loss_sum(const payne::lnmlp::TrainNet& net, int N, double* acc, int first, double denom, double* out, void* stream);
-
-struct payne_lnmlp_train {
-  int device = 0;
-  payne::lnmlp::TrainNet net{};
-  payne_lnmlp_train_opts opts{};
-  int rows = 0;                                                     // the workspace's rows: max_rows rounded up to the tile
-  long long t = 0;                                                  // steps taken
-  double* loss_acc = nullptr;
-  void* last_stream = nullptr;
-  std::vector<void*> owned;
-};
-
-extern "C" void payne_lnmlp_train_destroy(payne_lnmlp_train* h) {
-  if (!h) return;
-  int prev = 0;
-  (void)hipGetDevice(&prev);
-  if (hipSetDevice(h->device) == hipSuccess) {
-    (void)hipDeviceSynchronize();
-    for (void* p : h->owned) (void)hipFree(p);
-  }
-  (void)hipSetDevice(prev);
-  delete h;
-}
-
-extern "C" int payne_lnmlp_train_create(int device, const payne_lnmlp_desc* d, const payne_lnmlp_train_opts* o, payne_lnmlp_train** out) {
-  namespace ln = payne::lnmlp;
-  if (!d || !o || !out) return fail(nullptr, PAYNE_E_INVALID, "payne_lnmlp_train_create: null descriptor, options or handle pointer");
-  *out = nullptr;
-  if (d->n_layers < 2 || d->n_layers > ln::kMaxLayers) return fail(nullptr, PAYNE_E_UNSUPPORTED, "payne_lnmlp_train_create: 2 to 8 linear layers");
-  for (int l = 0; l < d->n_layers; ++l) {
-    const payne_lnmlp_layer& L = d->layers[l];
-    const bool last = l + 1 == d->n_layers;
-    if (L.n_in < 1 || L.n_out < 1 || !L.w || !L.b || (l > 0 && L.n_in != d->layers[l - 1].n_out))
-      return fail(nullptr, PAYNE_E_INVALID, "payne_lnmlp_train_create: layer " + std::to_string(l) + ": bad widths or null weights");
-    if (last ? (L.ln_gain || L.ln_bias) : (!L.ln_gain || !L.ln_bias))
-      return fail(nullptr, PAYNE_E_INVALID, "payne_lnmlp_train_create: LayerNorm gain and bias on every layer but the last");
-  }
-  if (d->in_mid || d->in_std || d->out_mid || d->out_std)
-    return fail(nullptr, PAYNE_E_INVALID, "payne_lnmlp_train_create: training data arrive normalised; the descriptor must hold no norms");
-  for (int l = 0; l < ln::kMaxLayers; ++l)
-    if (!(o->dropout_p[l] >= 0.0 && o->dropout_p[l] < 1.0))
-      return fail(nullptr, PAYNE_E_INVALID, "payne_lnmlp_train_create: dropout_p outside [0, 1)");
-  if (o->max_rows < 1 || !(o->lr > 0.0) || !(o->beta1 >= 0.0 && o->beta1 < 1.0) || !(o->beta2 >= 0.0 && o->beta2 < 1.0) || !(o->eps >= 0.0))
-    return fail(nullptr, PAYNE_E_INVALID, "payne_lnmlp_train_create: max_rows < 1 or an optimiser constant out of range");
-  if (d->layers[0].n_in > ln::kMaxIn) return fail(nullptr, PAYNE_E_UNSUPPORTED, "payne_lnmlp_train_create: more than 32 inputs");
-  for (int l = 0; l < d->n_layers; ++l)
-    if (d->layers[l].n_out > ln::kMaxWidth) return fail(nullptr, PAYNE_E_UNSUPPORTED, "payne_lnmlp_train_create: a width above 512");
-
-  int prev = 0;
-  (void)hipGetDevice(&prev);
-  if (hipSetDevice(device) != hipSuccess) return fail(nullptr, PAYNE_E_HIP, "payne_lnmlp_train_create: hipSetDevice");
-  payne_lnmlp_train* h = new payne_lnmlp_train;
-  h->device = device;
-  h->opts = *o;
-  h->rows = (o->max_rows + ln::kTileRows - 1) / ln::kTileRows * ln::kTileRows;
-  const size_t rows = (size_t)h->rows, tiles = rows / ln::kTileRows;
-  bool ok = true;
-  auto zeros = [&](size_t bytes) -> void* {
-    void* p = nullptr;
-    if (!ok || hipMalloc(&p, bytes) != hipSuccess) { ok = false; return nullptr; }
-    h->owned.push_back(p);
-    if (hipMemset(p, 0, bytes) != hipSuccess) ok = false;
-    return p;
-  };
-  auto floats = [&](size_t n) { return static_cast<float*>(zeros(n * sizeof(float))); };
-  auto put = [&](float* dst, const float* src, size_t n) {
-    if (ok && hipMemcpy(dst, src, n * sizeof(float), hipMemcpyHostToDevice) != hipSuccess) ok = false;
-  };
-  h->net.n_layers = d->n_layers;
-  for (int l = 0; l < d->n_layers; ++l) {
-    const payne_lnmlp_layer& L = d->layers[l];
-    ln::TrainLayer& A = h->net.L[l];
-    const size_t nw = (size_t)L.n_in * L.n_out, npad = (size_t)ln::pad32(L.n_out), kpad = (size_t)ln::pad32(L.n_in);
-    A.n_in = L.n_in;
-    A.n_out = L.n_out;
-    A.p = l + 1 < d->n_layers ? (float)o->dropout_p[l] : 0.0f;
-    A.wm = floats(nw);
-    A.gw = floats(nw);
-    A.mw = floats(nw);
-    A.vw = floats(nw);
-    A.wp = floats(ln::packed_floats(L.n_in, L.n_out));
-    A.wt = floats(ln::packed_floats(L.n_out, L.n_in));
-    A.vec = floats(3 * npad);
-    A.gvec = floats(3 * npad);
-    A.mvec = floats(3 * npad);
-    A.vvec = floats(3 * npad);
-    if (l == 0) A.a_in = floats(rows * kpad);                       // (a hidden block's output is the next layer's a_in, below)
-    A.xh = floats(rows * npad);
-    A.rs = floats(rows);
-    A.dz = floats(rows * npad);
-    A.slab = floats(tiles * 3 * npad);
-    if (l + 1 < d->n_layers) h->net.L[l + 1].a_in = floats(rows * npad);
-    std::vector<float> pk(ln::packed_floats(L.n_in, L.n_out)), tr(nw), pt(ln::packed_floats(L.n_out, L.n_in));
-    ln::pack_weights(L.w, L.n_in, L.n_out, pk.data());
-    for (int n = 0; n < L.n_out; ++n)
-      for (int k = 0; k < L.n_in; ++k) tr[(size_t)k * L.n_out + n] = L.w[(size_t)n * L.n_in + k];
-    ln::pack_weights(tr.data(), L.n_out, L.n_in, pt.data());
-    if (ok) {
-      put(A.wm, L.w, nw);
-      put(A.wp, pk.data(), pk.size());
-      put(A.wt, pt.data(), pt.size());
-      put(A.vec, L.b, (size_t)L.n_out);
-      if (L.ln_gain) put(A.vec + npad, L.ln_gain, (size_t)L.n_out);
-      if (L.ln_bias) put(A.vec + 2 * npad, L.ln_bias, (size_t)L.n_out);
-    }
-  }
-  h->net.loss_slab = static_cast<double*>(zeros(tiles * sizeof(double)));
-  h->loss_acc = static_cast<double*>(zeros(sizeof(double)));
-  (void)hipSetDevice(prev);
-  if (!ok) {
-    payne_lnmlp_train_destroy(h);
-    return fail(nullptr, PAYNE_E_HIP, "payne_lnmlp_train_create: allocating or copying to the device failed");
-  }
-  *out = h;
-  return PAYNE_OK;
-}
-
-static int lnmlp_train_check(payne_lnmlp_train* h, const float* x_dev, int ld_x, const float* t_dev, int ld_t, int N) {
-  if (!h || N < 0) return PAYNE_E_INVALID;
-  if (ld_x < h->net.L[0].n_in || ld_t < h->net.L[h->net.n_layers - 1].n_out) return PAYNE_E_INVALID;
-  if (N > 0 && (!x_dev || !t_dev)) return PAYNE_E_INVALID;
-  return PAYNE_OK;
-}
-
-extern "C" int payne_lnmlp_train_step(payne_lnmlp_train* h, const float* x_dev, int ld_x, const float* t_dev, int ld_t, int N,
-                                      double* loss_dev, void* stream) {
-  namespace ln = payne::lnmlp;
-  int rc = lnmlp_train_check(h, x_dev, ld_x, t_dev, ld_t, N);
-  if (rc) return rc;
-  if (N > h->opts.max_rows) return PAYNE_E_INVALID;
-  if (N == 0) return PAYNE_OK;
-  int prev = 0;
-  (void)hipGetDevice(&prev);
-  if (hipSetDevice(h->device) != hipSuccess) return PAYNE_E_HIP;
-  const int d_out = h->net.L[h->net.n_layers - 1].n_out;
-  h->last_stream = stream;
-  rc = payne_lnmlp_train_launch(h->net, x_dev, ld_x, t_dev, ld_t, N, 1, h->opts.seed, (unsigned long long)h->t,
-                                ln::loss_grad_scale(N, d_out), stream);
-  if (!rc && loss_dev) rc = payne_lnmlp_train_loss_sum(h->net, N, h->loss_acc, 1, (double)N * (double)d_out, loss_dev, stream);
-  if (!rc) {
-    rc = payne_lnmlp_train_update(h->net, N, ln::radam_scalars(h->opts.lr, h->opts.beta1, h->opts.beta2, h->opts.eps, h->t + 1), stream);
-    h->t += 1;
-  }
-  (void)hipSetDevice(prev);
-  return rc;
-}
-
-extern "C" int payne_lnmlp_train_loss(payne_lnmlp_train* h, const float* x_dev, int ld_x, const float* t_dev, int ld_t, int N,
-                                      double* loss_dev, void* stream) {
-  int rc = lnmlp_train_check(h, x_dev, ld_x, t_dev, ld_t, N);
-  if (rc) return rc;
-  if (N == 0) return PAYNE_OK;
-  if (!loss_dev) return PAYNE_E_INVALID;
-  int prev = 0;
-  (void)hipGetDevice(&prev);
-  if (hipSetDevice(h->device) != hipSuccess) return PAYNE_E_HIP;
-  const int d_out = h->net.L[h->net.n_layers - 1].n_out;
-  h->last_stream = stream;
-  for (int r0 = 0; r0 < N && !rc; r0 += h->rows) {                  // the workspace's rows a launch
-    const int n = N - r0 < h->rows ? N - r0 : h->rows;
-    rc = payne_lnmlp_train_launch(h->net, x_dev + (size_t)r0 * (size_t)ld_x, ld_x, t_dev + (size_t)r0 * (size_t)ld_t, ld_t, n, 0, 0, 0,
-                                  0.0f, stream);
-    if (!rc) rc = payne_lnmlp_train_loss_sum(h->net, n, h->loss_acc, r0 == 0, r0 + n == N ? (double)N * (double)d_out : 0.0, loss_dev, stream);
-  }
-  (void)hipSetDevice(prev);
-  return rc;
-}
-
-extern "C" int payne_lnmlp_train_get(payne_lnmlp_train* h, int what, payne_lnmlp_desc* host_out) {
-  namespace ln = payne::lnmlp;
-  if (!h || !host_out || (what != PAYNE_LNMLP_PARAMS && what != PAYNE_LNMLP_GRADS) || host_out->n_layers != h->net.n_layers)
-    return PAYNE_E_INVALID;
-  for (int l = 0; l < h->net.n_layers; ++l) {
-    const payne_lnmlp_layer& L = host_out->layers[l];
-    const bool last = l + 1 == h->net.n_layers;
-    if (L.n_in != h->net.L[l].n_in || L.n_out != h->net.L[l].n_out || !L.w || !L.b || (!last && (!L.ln_gain || !L.ln_bias)))
-      return PAYNE_E_INVALID;
-  }
-  int prev = 0;
-  (void)hipGetDevice(&prev);
-  if (hipSetDevice(h->device) != hipSuccess) return PAYNE_E_HIP;
-  bool ok = hipStreamSynchronize(reinterpret_cast<hipStream_t>(h->last_stream)) == hipSuccess;
-  auto take = [&](const float* dst, const float* src, size_t n) {
-    if (ok && hipMemcpy(const_cast<float*>(dst), src, n * sizeof(float), hipMemcpyDeviceToHost) != hipSuccess) ok = false;
-  };
-  for (int l = 0; l < h->net.n_layers; ++l) {
-    const payne_lnmlp_layer& L = host_out->layers[l];
-    const ln::TrainLayer& A = h->net.L[l];
-    const size_t npad = (size_t)ln::pad32(A.n_out);
-    const float* vec = what == PAYNE_LNMLP_PARAMS ? A.vec : A.gvec;
-    take(L.w, what == PAYNE_LNMLP_PARAMS ? A.wm : A.gw, (size_t)A.n_in * A.n_out);
-    take(L.b, vec, (size_t)A.n_out);
-    if (l + 1 < h->net.n_layers) {
-      take(L.ln_gain, vec + npad, (size_t)A.n_out);
-      take(L.ln_bias, vec + 2 * npad, (size_t)A.n_out);
-    }
-  }
-  (void)hipSetDevice(prev);
-  return ok ? PAYNE_OK : PAYNE_E_HIP;
-}
-
-extern "C" long long payne_lnmlp_train_steps(payne_lnmlp_train* h) { return h ? h->t : -1; }
-
-extern "C" int payne_lnmlp_dropout_mask(unsigned long long seed, unsigned long long step, int layer, int n_rows, int n_cols, double p,
-                                        unsigned char* out_host) {
-  if (!out_host || n_rows < 0 || n_cols < 0 || layer < 0 || !(p >= 0.0 && p < 1.0)) return PAYNE_E_INVALID;
-  for (int r = 0; r < n_rows; ++r)
-    for (int c = 0; c < n_cols; ++c)
-      out_host[(size_t)r * (size_t)n_cols + (size_t)c] = payne::lnmlp::keep(seed, step, layer, r, c, (float)p) ? 1 : 0;
-  return PAYNE_OK;
-}
-
-// ---- training the spectral networks (trainspec.TrainMod): the handle; the kernels are k_specmlp_train.hip -------------------
-int payne_specmlp_train_forward(const payne::specmlp::SpecNet& net, const float* x, int ld_x, const float* t, int ld_t, float* y, int ld_y,
-                                int N, int train, void* stream);
-int payne_specmlp_train_backward(const payne::specmlp::SpecNet& net, int N, const payne::lnmlp::RadamStep& rs, void* stream);
-int payne_specmlp_train_loss_sum(const payne::specmlp::SpecNet& net, int N, double* acc, int first, double* out, void* stream);
-
-struct payne_specmlp_train {
-  int device = 0;
-  payne::specmlp::SpecNet net{};
-  payne_specmlp_train_opts opts{};
-  int rows = 0;                                                     // the workspace's rows: max_rows rounded up to the tile
-  long long t = 0;                                                  // steps taken
-  double* loss_acc = nullptr;
-  void* last_stream = nullptr;
-  std::vector<void*> owned;
-};
-
-extern "C" void payne_specmlp_train_destroy(payne_specmlp_train* h) {
-  if (!h) return;
-  int prev = 0;
-  (void)hipGetDevice(&prev);
-  if (hipSetDevice(h->device) == hipSuccess) {
-    (void)hipDeviceSynchronize();
-    for (void* p : h->owned) (void)hipFree(p);
-  }
-  (void)hipSetDevice(prev);
-  delete h;
-}
-
-extern "C" int payne_specmlp_train_create(int device, const payne_specmlp_desc* d, const payne_specmlp_train_opts* o, payne_specmlp_train** out) {
-  namespace sp = payne::specmlp;
-  if (!d || !o || !out) return fail(nullptr, PAYNE_E_INVALID, "payne_specmlp_train_create: null descriptor, options or handle pointer");
-  *out = nullptr;
-  if (d->n_layers < 2 || d->n_layers > sp::kMaxLayers) return fail(nullptr, PAYNE_E_UNSUPPORTED, "payne_specmlp_train_create: 2 to 8 linear layers");
-  for (int l = 0; l < d->n_layers; ++l) {
-    const payne_specmlp_layer& L = d->layers[l];
-    if (L.n_in < 1 || L.n_out < 1 || !L.w || !L.b || (l > 0 && L.n_in != d->layers[l - 1].n_out))
-      return fail(nullptr, PAYNE_E_INVALID, "payne_specmlp_train_create: layer " + std::to_string(l) + ": bad widths or null weights");
-  }
-  if (d->act != PAYNE_SPECMLP_LEAKY && d->act != PAYNE_SPECMLP_SIGMOID)
-    return fail(nullptr, PAYNE_E_INVALID, "payne_specmlp_train_create: the activation is PAYNE_SPECMLP_LEAKY or PAYNE_SPECMLP_SIGMOID");
-  if (o->max_rows < 1 || !(o->lr > 0.0) || !(o->beta1 >= 0.0 && o->beta1 < 1.0) || !(o->beta2 >= 0.0 && o->beta2 < 1.0) || !(o->eps >= 0.0))
-    return fail(nullptr, PAYNE_E_INVALID, "payne_specmlp_train_create: max_rows < 1 or an optimiser constant out of range");
-  if (d->layers[0].n_in > sp::kMaxIn) return fail(nullptr, PAYNE_E_UNSUPPORTED, "payne_specmlp_train_create: more than 32 inputs");
-  for (int l = 0; l + 1 < d->n_layers; ++l)
-    if (d->layers[l].n_out > sp::kMaxWidth) return fail(nullptr, PAYNE_E_UNSUPPORTED, "payne_specmlp_train_create: a hidden width above 512");
-  if (d->layers[d->n_layers - 1].n_out > sp::kMaxOut) return fail(nullptr, PAYNE_E_UNSUPPORTED, "payne_specmlp_train_create: more than 65536 outputs");
-
-  int prev = 0;
-  (void)hipGetDevice(&prev);
-  if (hipSetDevice(device) != hipSuccess) return fail(nullptr, PAYNE_E_HIP, "payne_specmlp_train_create: hipSetDevice");
-  payne_specmlp_train* h = new payne_specmlp_train;
-  h->device = device;
-  h->opts = *o;
-  h->rows = (o->max_rows + sp::kTileRows - 1) / sp::kTileRows * sp::kTileRows;
-  const size_t rows = (size_t)h->rows, tiles = rows / sp::kTileRows;
-  bool ok = true;
-  auto zeros = [&](size_t bytes) -> void* {
-    void* p = nullptr;
-    if (!ok || hipMalloc(&p, bytes) != hipSuccess) { ok = false; return nullptr; }
-    h->owned.push_back(p);
-    if (hipMemset(p, 0, bytes) != hipSuccess) ok = false;
-    return p;
-  };
-  auto floats = [&](size_t n) { return static_cast<float*>(zeros(n * sizeof(float))); };
-  auto put = [&](float* dst, const float* src, size_t n) {
-    if (ok && hipMemcpy(dst, src, n * sizeof(float), hipMemcpyHostToDevice) != hipSuccess) ok = false;
-  };
-  h->net.n_layers = d->n_layers;
-  h->net.act = d->act == PAYNE_SPECMLP_SIGMOID ? sp::kActSigmoid : sp::kActLeaky;
-  for (int l = 0; l < d->n_layers; ++l) {
-    const payne_specmlp_layer& L = d->layers[l];
-    sp::SpecLayer& A = h->net.L[l];
-    const size_t nw = (size_t)L.n_in * L.n_out, npad = (size_t)sp::pad32(L.n_out), kpad = (size_t)sp::pad32(L.n_in);
-    A.n_in = L.n_in;
-    A.n_out = L.n_out;
-    A.wm = floats(nw);
-    A.gw = floats(nw);
-    A.mw = floats(nw);
-    A.vw = floats(nw);
-    A.wp = floats(sp::packed_floats(L.n_in, L.n_out));
-    A.wt = floats(sp::packed_floats(L.n_out, L.n_in));
-    A.vec = floats(npad);
-    A.gvec = floats(npad);
-    A.mvec = floats(npad);
-    A.vvec = floats(npad);
-    if (l == 0) A.a_in = floats(rows * kpad);                       // (a hidden block's output is the next layer's a_in, below)
-    A.dz = floats(rows * npad);
-    A.slab = floats(tiles * npad);
-    if (l + 1 < d->n_layers) h->net.L[l + 1].a_in = floats(rows * npad);
-    std::vector<float> pk(sp::packed_floats(L.n_in, L.n_out)), tr(nw), pt(sp::packed_floats(L.n_out, L.n_in));
-    sp::pack_weights(L.w, L.n_in, L.n_out, pk.data());
-    for (int n = 0; n < L.n_out; ++n)
-      for (int k = 0; k < L.n_in; ++k) tr[(size_t)k * L.n_out + n] = L.w[(size_t)n * L.n_in + k];
-    sp::pack_weights(tr.data(), L.n_out, L.n_in, pt.data());
-    if (ok) {
-      put(A.wm, L.w, nw);
-      put(A.wp, pk.data(), pk.size());
-      put(A.wt, pt.data(), pt.size());
-      put(A.vec, L.b, (size_t)L.n_out);
-    }
-  }
-  h->net.loss_slab = static_cast<double*>(zeros(tiles * (size_t)sp::out_chunks(d->layers[d->n_layers - 1].n_out) * sizeof(double)));
-  h->loss_acc = static_cast<double*>(zeros(sizeof(double)));
-  (void)hipSetDevice(prev);
-  if (!ok) {
-    payne_specmlp_train_destroy(h);
-    return fail(nullptr, PAYNE_E_HIP, "payne_specmlp_train_create: allocating or copying to the device failed");
-  }
-  *out = h;
-  return PAYNE_OK;
-}
-
-static int specmlp_train_check(payne_specmlp_train* h, const float* x_dev, int ld_x, const float* t_dev, int ld_t, int N) {
-  if (!h || N < 0) return PAYNE_E_INVALID;
-  if (ld_x < h->net.L[0].n_in || ld_t < h->net.L[h->net.n_layers - 1].n_out) return PAYNE_E_INVALID;
-  if (N > 0 && (!x_dev || !t_dev)) return PAYNE_E_INVALID;
-  return PAYNE_OK;
-}
-
-extern "C" int payne_specmlp_train_step(payne_specmlp_train* h, const float* x_dev, int ld_x, const float* t_dev, int ld_t, int N,
-                                        double* loss_dev, void* stream) {
-  int rc = specmlp_train_check(h, x_dev, ld_x, t_dev, ld_t, N);
-  if (rc) return rc;
-  if (N > h->opts.max_rows) return PAYNE_E_INVALID;
-  if (N == 0) return PAYNE_OK;
-  int prev = 0;
-  (void)hipGetDevice(&prev);
-  if (hipSetDevice(h->device) != hipSuccess) return PAYNE_E_HIP;
-  h->last_stream = stream;
-  rc = payne_specmlp_train_forward(h->net, x_dev, ld_x, t_dev, ld_t, nullptr, 0, N, 1, stream);
-  if (!rc && loss_dev) rc = payne_specmlp_train_loss_sum(h->net, N, h->loss_acc, 1, loss_dev, stream);
-  if (!rc) {
-    rc = payne_specmlp_train_backward(h->net, N, payne::lnmlp::radam_scalars(h->opts.lr, h->opts.beta1, h->opts.beta2, h->opts.eps, h->t + 1),
-                                      stream);
-    h->t += 1;
-  }
-  (void)hipSetDevice(prev);
-  return rc;
-}
-
-extern "C" int payne_specmlp_train_loss(payne_specmlp_train* h, const float* x_dev, int ld_x, const float* t_dev, int ld_t, int N,
-                                        double* loss_dev, void* stream) {
-  int rc = specmlp_train_check(h, x_dev, ld_x, t_dev, ld_t, N);
-  if (rc) return rc;
-  if (N == 0) return PAYNE_OK;
-  if (!loss_dev) return PAYNE_E_INVALID;
-  int prev = 0;
-  (void)hipGetDevice(&prev);
-  if (hipSetDevice(h->device) != hipSuccess) return PAYNE_E_HIP;
-  h->last_stream = stream;
-  for (int r0 = 0; r0 < N && !rc; r0 += h->rows) {                  // the workspace's rows a pass
-    const int n = N - r0 < h->rows ? N - r0 : h->rows;
-    rc = payne_specmlp_train_forward(h->net, x_dev + (size_t)r0 * (size_t)ld_x, ld_x, t_dev + (size_t)r0 * (size_t)ld_t, ld_t, nullptr, 0, n,
-                                     0, stream);
-    if (!rc) rc = payne_specmlp_train_loss_sum(h->net, n, h->loss_acc, r0 == 0, r0 + n == N ? loss_dev : nullptr, stream);
-  }
-  (void)hipSetDevice(prev);
-  return rc;
-}
-
-extern "C" int payne_specmlp_train_predict(payne_specmlp_train* h, const float* x_dev, int ld_x, int N, float* y_dev, int ld_y, void* stream) {
-  if (!h || N < 0) return PAYNE_E_INVALID;
-  if (ld_x < h->net.L[0].n_in || ld_y < h->net.L[h->net.n_layers - 1].n_out) return PAYNE_E_INVALID;
-  if (N == 0) return PAYNE_OK;
-  if (!x_dev || !y_dev) return PAYNE_E_INVALID;
-  int prev = 0, rc = PAYNE_OK;
-  (void)hipGetDevice(&prev);
-  if (hipSetDevice(h->device) != hipSuccess) return PAYNE_E_HIP;
-  h->last_stream = stream;
-  for (int r0 = 0; r0 < N && !rc; r0 += h->rows) {
-    const int n = N - r0 < h->rows ? N - r0 : h->rows;
-    rc = payne_specmlp_train_forward(h->net, x_dev + (size_t)r0 * (size_t)ld_x, ld_x, nullptr, 0, y_dev + (size_t)r0 * (size_t)ld_y, ld_y, n, 0,
-                                     stream);
-  }
-  (void)hipSetDevice(prev);
-  return rc;
-}
-
-extern "C" int payne_specmlp_train_set_lr(payne_specmlp_train* h, double lr) {
-  if (!h || !(lr > 0.0) || !std::isfinite(lr)) return PAYNE_E_INVALID;
-  h->opts.lr = lr;
-  return PAYNE_OK;
-}
-
-extern "C" int payne_specmlp_train_get(payne_specmlp_train* h, int what, payne_specmlp_desc* host_out) {
-  if (!h || !host_out || (what != PAYNE_SPECMLP_PARAMS && what != PAYNE_SPECMLP_GRADS) || host_out->n_layers != h->net.n_layers)
-    return PAYNE_E_INVALID;
-  for (int l = 0; l < h->net.n_layers; ++l) {
-    const payne_specmlp_layer& L = host_out->layers[l];
-    if (L.n_in != h->net.L[l].n_in || L.n_out != h->net.L[l].n_out || !L.w || !L.b) return PAYNE_E_INVALID;
-  }
-  int prev = 0;
-  (void)hipGetDevice(&prev);
-  if (hipSetDevice(h->device) != hipSuccess) return PAYNE_E_HIP;
-  bool ok = hipStreamSynchronize(reinterpret_cast<hipStream_t>(h->last_stream)) == hipSuccess;
-  auto take = [&](const float* dst, const float* src, size_t n) {
-    if (ok && hipMemcpy(const_cast<float*>(dst), src, n * sizeof(float), hipMemcpyDeviceToHost) != hipSuccess) ok = false;
-  };
-  for (int l = 0; l < h->net.n_layers; ++l) {
-    const payne_specmlp_layer& L = host_out->layers[l];
-    const payne::specmlp::SpecLayer& A = h->net.L[l];
-    take(L.w, what == PAYNE_SPECMLP_PARAMS ? A.wm : A.gw, (size_t)A.n_in * A.n_out);
-    take(L.b, what == PAYNE_SPECMLP_PARAMS ? A.vec : A.gvec, (size_t)A.n_out);
-  }
-  (void)hipSetDevice(prev);
-  return ok ? PAYNE_OK : PAYNE_E_HIP;
-}
-
-extern "C" long long payne_specmlp_train_steps(payne_specmlp_train* h) { return h ? h->t : -1; }
-
-// ---- label gradients of the spectral networks and Fisher matrices: the handle; the kernels are k_specjac.hip -----------------
-int payne_specjac_launch(const payne::specjac::JacNet& net, const double* x, int ld_x, int N, float* y, int ld_y, float* jac, int ld_j,
-                         void* stream);
-int payne_specjac_prepare(const payne::specjac::JacNet& net);
-int payne_fisher_launch(const float* rows, int ld, int K, int n, int B, const double* w, double* F, void* stream);
-
-struct payne_specjac {
-  int device = 0;
-  payne::specjac::JacNet net{};                                     // (scale: the physical one, 1 / (xmax - xmin))
-  int stars = 0;                                                    // the workspace's stars: max_rows rounded up to whole tiles
-  std::vector<void*> owned;
-};
-
-extern "C" void payne_specjac_destroy(payne_specjac* h) {
-  if (!h) return;
-  int prev = 0;
-  (void)hipGetDevice(&prev);
-  if (hipSetDevice(h->device) == hipSuccess) {
-    (void)hipDeviceSynchronize();
-    for (void* p : h->owned) (void)hipFree(p);
-  }
-  (void)hipSetDevice(prev);
-  delete h;
-}
-
-extern "C" int payne_specjac_create(int device, const payne_specmlp_desc* d, const double* xmin, const double* xmax, int max_rows,
-                                    payne_specjac** out) {
-  namespace sj = payne::specjac;
-  if (!d || !xmin || !xmax || !out) return fail(nullptr, PAYNE_E_INVALID, "payne_specjac_create: null descriptor, xmin, xmax or handle pointer");
-  *out = nullptr;
-  if (d->n_layers < 2 || d->n_layers > sj::kMaxLayers) return fail(nullptr, PAYNE_E_UNSUPPORTED, "payne_specjac_create: 2 to 8 linear layers");
-  for (int l = 0; l < d->n_layers; ++l) {
-    const payne_specmlp_layer& L = d->layers[l];
-    if (L.n_in < 1 || L.n_out < 1 || !L.w || !L.b || (l > 0 && L.n_in != d->layers[l - 1].n_out))
-      return fail(nullptr, PAYNE_E_INVALID, "payne_specjac_create: layer " + std::to_string(l) + ": bad widths or null weights");
-  }
-  if (d->act != PAYNE_SPECMLP_LEAKY && d->act != PAYNE_SPECMLP_SIGMOID)
-    return fail(nullptr, PAYNE_E_INVALID, "payne_specjac_create: the activation is PAYNE_SPECMLP_LEAKY or PAYNE_SPECMLP_SIGMOID");
-  if (max_rows < 1) return fail(nullptr, PAYNE_E_INVALID, "payne_specjac_create: max_rows < 1");
-  const int d_in = d->layers[0].n_in;
-  if (d_in > sj::kMaxLabels) return fail(nullptr, PAYNE_E_UNSUPPORTED, "payne_specjac_create: more than 8 labels");
-  for (int l = 0; l + 1 < d->n_layers; ++l)
-    if (d->layers[l].n_out > sj::kMaxWidth) return fail(nullptr, PAYNE_E_UNSUPPORTED, "payne_specjac_create: a hidden width above 512");
-  if (d->layers[d->n_layers - 1].n_out > sj::kMaxOut) return fail(nullptr, PAYNE_E_UNSUPPORTED, "payne_specjac_create: more than 65536 outputs");
-  for (int k = 0; k < d_in; ++k)
-    if (!std::isfinite(xmin[k]) || !std::isfinite(xmax[k]) || xmin[k] == xmax[k])
-      return fail(nullptr, PAYNE_E_INVALID, "payne_specjac_create: label " + std::to_string(k) + ": xmin / xmax not finite or equal");
-
-  int prev = 0;
-  (void)hipGetDevice(&prev);
-  if (hipSetDevice(device) != hipSuccess) return fail(nullptr, PAYNE_E_HIP, "payne_specjac_create: hipSetDevice");
-  payne_specjac* h = new payne_specjac;
-  h->device = device;
-  const int tiles = sj::tiles_of(max_rows, d_in);
-  h->stars = tiles * sj::stars_per_tile(d_in);
-  bool ok = true;
-  auto floats = [&](size_t n) -> float* {
-    void* p = nullptr;
-    if (!ok || hipMalloc(&p, n * sizeof(float)) != hipSuccess) { ok = false; return nullptr; }
-    h->owned.push_back(p);
-    if (hipMemset(p, 0, n * sizeof(float)) != hipSuccess) ok = false;
-    return static_cast<float*>(p);
-  };
-  h->net.n_layers = d->n_layers;
-  h->net.act = d->act == PAYNE_SPECMLP_SIGMOID ? sj::kActSigmoid : sj::kActLeaky;
-  for (int l = 0; l < d->n_layers; ++l) {
-    const payne_specmlp_layer& L = d->layers[l];
-    std::vector<float> pk(sj::packed_floats(L.n_in, L.n_out));
-    sj::pack_weights(L.w, L.n_in, L.n_out, pk.data());
-    float* w = floats(pk.size());
-    float* b = floats((size_t)sj::pad32(L.n_out));
-    if (ok && (hipMemcpy(w, pk.data(), pk.size() * sizeof(float), hipMemcpyHostToDevice) != hipSuccess ||
-               hipMemcpy(b, L.b, (size_t)L.n_out * sizeof(float), hipMemcpyHostToDevice) != hipSuccess))
-      ok = false;
-    h->net.L[l].w = w;
-    h->net.L[l].b = b;
-    h->net.L[l].n_in = L.n_in;
-    h->net.L[l].n_out = L.n_out;
-  }
-  for (int k = 0; k < sj::kMaxLabels; ++k) {
-    h->net.xmin[k] = k < d_in ? xmin[k] : 0.0;
-    h->net.xmax[k] = k < d_in ? xmax[k] : 1.0;
-    h->net.scale[k] = sj::label_scale(h->net.xmin[k], h->net.xmax[k]);
-  }
-  h->net.a_last = floats((size_t)tiles * sj::kTileRows * (size_t)sj::pad32(d->layers[d->n_layers - 1].n_in));
-  if (ok && payne_specjac_prepare(h->net) != PAYNE_OK) ok = false;
-  (void)hipSetDevice(prev);
-  if (!ok) {
-    payne_specjac_destroy(h);
-    return fail(nullptr, PAYNE_E_HIP, "payne_specjac_create: allocating, copying to the device or reserving LDS failed");
-  }
-  *out = h;
-  return PAYNE_OK;
-}
-
-extern "C" int payne_specjac_eval(payne_specjac* h, const double* labels_dev, int ld_x, int N, float* y_dev, int ld_y, float* jac_dev,
-                                  int ld_j, unsigned flags, void* stream) {
-  namespace sj = payne::specjac;
-  if (!h || N < 0 || (flags & ~PAYNE_JAC_ENCODED)) return PAYNE_E_INVALID;
-  const int d_in = h->net.L[0].n_in, d_out = h->net.L[h->net.n_layers - 1].n_out;
-  if (ld_x < d_in || ld_j < d_out || (y_dev && ld_y < d_out)) return PAYNE_E_INVALID;
-  if (N == 0) return PAYNE_OK;
-  if (!labels_dev || !jac_dev) return PAYNE_E_INVALID;
-  int prev = 0, rc = PAYNE_OK;
-  (void)hipGetDevice(&prev);
-  if (hipSetDevice(h->device) != hipSuccess) return PAYNE_E_HIP;
-  sj::JacNet net = h->net;
-  if (flags & PAYNE_JAC_ENCODED)
-    for (int k = 0; k < sj::kMaxLabels; ++k) net.scale[k] = 1.0f;
-  for (int r0 = 0; r0 < N && !rc; r0 += h->stars) {                 // the workspace's stars a pass
-    const int n = N - r0 < h->stars ? N - r0 : h->stars;
-    rc = payne_specjac_launch(net, labels_dev + (size_t)r0 * (size_t)ld_x, ld_x, n, y_dev ? y_dev + (size_t)r0 * (size_t)ld_y : nullptr, ld_y,
-                              jac_dev + (size_t)r0 * (size_t)d_in * (size_t)ld_j, ld_j, stream);
-  }
-  (void)hipSetDevice(prev);
-  return rc;
-}
-
-extern "C" int payne_fisher_batch(int device, const float* rows_dev, int ld, int K, int n, int B, const double* w_dev, double* F_dev,
-                                  void* stream) {
-  if (K < 1 || n < 1 || B < 0 || ld < n) return PAYNE_E_INVALID;
-  if (K > payne::specjac::kMaxFisherRows) return PAYNE_E_UNSUPPORTED;
-  if (B == 0) return PAYNE_OK;
-  if (!rows_dev || !w_dev || !F_dev) return PAYNE_E_INVALID;
-  int prev = 0;
-  (void)hipGetDevice(&prev);
-  if (hipSetDevice(device) != hipSuccess) return PAYNE_E_HIP;
-  const int rc = payne_fisher_launch(rows_dev, ld, K, n, B, w_dev, F_dev, stream);
-  (void)hipSetDevice(prev);
-  return rc;
 }
 
 // ---- per-kernel timing ---------------------------------------------------------

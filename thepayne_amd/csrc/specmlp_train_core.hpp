@@ -90,6 +90,7 @@ struct SpecLayer {
   int n_in, n_out;
 };
 struct SpecNet {
+  static constexpr int kHiddenVecs = 1;                             // per-column vectors of a hidden layer; the slabs' stride
   int n_layers;
   int act;
   SpecLayer L[kMaxLayers];
