@@ -207,9 +207,9 @@ def test_turn_kernel_releases_once_and_exchanges_inside_the_wave(tmp_path):
     import re
     import subprocess
     from thepayne_amd import build
-    asm = tmp_path / "payne_hip.s"
+    asm = tmp_path / "sampler_api.s"
     cmd = [build._hipcc()] + [f for f in build.HIPCC_FLAGS if f != "-fPIC"] + ["-I", os.path.join(build.ROOT, "include"), "-S", "--cuda-device-only",
-                                                                           os.path.join(build.CSRC, "payne_hip.hip"), "-o", str(asm)]
+                                                                           os.path.join(build.CSRC, "sampler_api.hip"), "-o", str(asm)]
     res = subprocess.run(cmd, capture_output=True, text=True)
     assert res.returncode == 0, res.stderr[-2000:]
     text = asm.read_text()

@@ -435,6 +435,17 @@ def test_device_rwalk_with_one_ellipsoid_per_chain(tmp_path):
     a = prop.rwalk(U0, V0, lp0, A[:1], 1.0, -np.inf, 3, seed=77)
     b = prop.rwalk(U0, V0, lp0, A[0], 1.0, -np.inf, 3, seed=77)
     assert np.array_equal(a[0], b[0]) and np.array_equal(a[2], b[2])
+    # ... and so is the walk in ONE native call (payne_rwalk_batch: payne_rwalk_begin and its steps); 5 chains: no multiple of the 4
+    # a workgroup walks
+    import ctypes as C
+    from thepayne_amd.sampler.device import _seed64
+    parts = prop.rwalk(U0[:5], V0[:5], lp0[:5], A[0], 1.0, -np.inf, 3, seed=77)
+    K, pu, pv, pl, _, _, _, ip, st = prop._stage_chains(U0[:5], V0[:5], lp0[:5], A[0], None, None)
+    rc = prop.lib.payne_rwalk_batch(prop._handle, pu, pv, pl, K, prop._st_ax.ctypes.data_as(C.POINTER(C.c_double)), 1.0, -np.inf, 3,
+                                    _seed64(77), ip, ip + 4 * K, st)
+    assert rc == 0
+    whole = prop.rwalk_finish()
+    assert whole[3].sum() > 0 and all(np.array_equal(x, y) for x, y in zip(whole, parts))
     with pytest.raises(RuntimeError):
         prop.rwalk(U0, V0, lp0, A, 1.0, -np.inf, 1, seed=1, ell=np.full(64, 3, dtype=np.int32))
     prop.close()

@@ -14,7 +14,7 @@
 #include <vector>
 
 #include "../../include/payne_hip.h"
-#include "api_error.hpp"
+#include "ctx_api.hpp"
 #include "mlp_desc.hpp"
 #include "specjac_core.hpp"
 

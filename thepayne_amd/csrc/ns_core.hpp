@@ -1,4 +1,5 @@
-// ns_core.hpp -- host-side bookkeeping of the static nested sampler (no GPU code).
+// ns_core.hpp -- host-side bookkeeping of the static nested sampler (no GPU code).  It DEFINES extern "C" entry points: the library
+// includes it once, in sampler_api.hip.
 //
 // The reference hands its three callables to dynesty and consumes one 15-tuple per
 // iteration (Payne/fitting/fitstar.py:309-338).  With proposals generated K at a time on the

@@ -1,6 +1,6 @@
 // sampler_kernels.hpp -- the sampler step on the device: prior transform and ln-prior
 // (Payne/fitting/prior.py:126-465), theta rows, random-walk proposals (one wave per chain).
-// Device functions only (no kernels): included by sampler_kernels.hpp (payne_hip.hip) and by post_kernels.hpp, whose
+// Device functions only (no kernels): included by sampler_kernels.hpp (sampler_api.hip) and by post_kernels.hpp, whose
 // likelihood-only kernel runs a chain's next step at its tail.
 #pragma once
 #include "../../include/payne_hip.h"

@@ -1,5 +1,5 @@
 // sampler_kernels.hpp -- the sampler step's kernels (device functions: sampler_core.hpp), then the queue's: its staging block's two
-// transfers and the turn between two queues (payne_ns_turn_kernel).  Included once by payne_hip.hip.
+// transfers and the turn between two queues (payne_ns_turn_kernel).  Included once, by sampler_api.hip.
 #pragma once
 #include "sampler_core.hpp"
 
