@@ -173,7 +173,7 @@ def _bf16_rne(x):
 
 def test_three_bf16_parts_hold_an_fp32_value_exactly():
     """The output layer multiplies operands split as x1 = bf16(x), x2 = bf16(x - x1), x3 = bf16(x - x1 - x2)
-    (thepayne_amd/csrc/dense_kernels.hpp, split3).  The claim its accuracy rests on: the three parts sum to x EXACTLY
+    (thepayne_amd/csrc/dense_kernels.hpp, split3; the six products of the parts: Bf16x3::products, csrc/out_tile.hpp).  The claim its accuracy rests on: the three parts sum to x EXACTLY
     (24 significant bits = 8 + 8 + 8, with the signs of the remainders absorbing the rounding), and the six partial products
     the kernel keeps differ from the full product by less than 2^-22 |a b|."""
     rng = np.random.default_rng(0)

@@ -63,6 +63,7 @@ struct DenseParams {
 #define PAYNE_D3_LEAD_TYPES const unsigned long long*, const unsigned short*, const unsigned short*, unsigned, unsigned, unsigned, int, int, int, int, unsigned
 #define PAYNE_D3_LEAD_ARGS(p) (p).sel, (p).Xp, (p).Wp, (unsigned)(p).plane_x, (unsigned)(p).plane_w, ((unsigned)(p).grid_m | ((unsigned)(p).grid_n << 16)), \
                               (p).N, (p).B, (p).ldp, (p).K, (unsigned)(p).sel_seq
+#define PAYNE_D3_LEAD_NAMES lead_sel, lead_Xp, lead_Wp, lead_plane_x, lead_plane_w, lead_grid, lead_N, lead_B, lead_ldp, lead_K, lead_sel_seq
 #ifdef PAYNE_STAMPS
 #ifdef PAYNE_STAMPS_ENDS_ONLY   /* stamps 0 / 5 / 15 only: the phases in between keep their production shape */
 #define HK_STAMP(k) do { if (((k) == 0 || (k) == 5 || (k) == 15) && p.stamps && threadIdx.x == 0) p.stamps[(size_t)blockIdx.x * 16 + (k)] = __builtin_amdgcn_s_memtime(); } while (0)
@@ -106,6 +107,10 @@ __device__ __forceinline__ float act_apply(float z, int act) {
 // would be waited for at the very next barrier; here only the LDS counter is drained and the loads
 // stay in flight (the compiler still waits on vmcnt before the first use of their registers).
 __device__ __forceinline__ void lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
+
+// What the output layer's plane-operand kernels below share -- arguments, tile, operand forms and their products, swizzle, fragments:
+// each written once there.
+#include "out_tile.hpp"
 
 template <int BM, int BN, int BK>
 constexpr size_t dense_lds_bytes() { return (size_t)(2 * (BM + BN) * (BK + 4) + BM * PAYNE_MAX_LABELS) * sizeof(float); }
@@ -516,7 +521,6 @@ __global__ void __launch_bounds__(128 * WN) payne_dense_dma_kernel(DenseParams p
 // waves 0-3 move five, waves 4-7 four); 16-byte chunk c of tile row r sits at chunk c ^ ((r >> 2) & 3): the sixteen lanes of a
 // fragment read cover sixteen different bank groups.
 // ----------------------------------------------------------------------------
-typedef __bf16 bf16x8_t __attribute__((ext_vector_type(8)));
 __device__ __forceinline__ unsigned short bf16_bits(__bf16 v) { return __builtin_bit_cast(unsigned short, v); }
 __device__ __forceinline__ void split3(float x, unsigned short& h, unsigned short& m, unsigned short& l) {
   const __bf16 b1 = (__bf16)x;
@@ -549,7 +553,6 @@ __global__ void __launch_bounds__(256) payne_split3_kernel(const float* __restri
 // (payne_ctx_create; a row's scale comes back in the epilogue), the activations by one power of two per context, calibrated at
 // payne_ctx_create on the label box (corners, centre, 64 points) with a factor of 8 to spare (what lies beyond saturates; NaN stays NaN).
 // ----------------------------------------------------------------------------
-typedef _Float16 f16x8_t __attribute__((ext_vector_type(8)));
 __device__ __forceinline__ unsigned short f16_bits(_Float16 v) { return __builtin_bit_cast(unsigned short, v); }
 __device__ __forceinline__ void split2h(float x, float scale, unsigned short& h1, unsigned short& h2) {
   float X = x * scale;                                     // (a power of two: exact)
@@ -599,21 +602,16 @@ template <int KD> constexpr size_t d2_lds_bytes() { return (size_t)d2_ns<KD>() *
 template <int NK, int KD>
 __global__ void __launch_bounds__(512) payne_dense_dma2h_kernel(PAYNE_D3_LEAD_PARAMS, DenseParams p_) {
   DenseParams p = p_;
-  p.sel = lead_sel; p.Xp = lead_Xp; p.Wp = lead_Wp; p.plane_x = lead_plane_x; p.plane_w = lead_plane_w;
-  p.grid_m = (int)(lead_grid & 0xffffu); p.grid_n = (int)(lead_grid >> 16); p.N = lead_N; p.B = lead_B; p.ldp = lead_ldp; p.K = lead_K;
+  out_args(p, PAYNE_D3_LEAD_NAMES);
   constexpr int NS = d2_ns<KD>(), AHEAD = NS - 1, STAGE = d2_stage<KD>();
   constexpr int ROWB = 2 * KD, CPR = ROWB / 16, RPP = 1024 / ROWB;          // bytes a row, chunks a row, rows a piece
   constexpr int A_PLANE = 64 * ROWB, B_PLANE = 128 * ROWB, NPA = 64 / RPP, NPB = 128 / RPP, PW = 2 * (NPA + NPB) / 8;   // pieces a wave: 3 | 6
   constexpr int KS = KD / 16;                              // 16-deep matrix steps a stage
-  auto sw = [](int row) { return KD == 64 ? ((row >> 1) & 7) : ((row >> 2) & 3); };
   extern __shared__ __attribute__((aligned(16))) unsigned char d2_sm[];
-  if (p.sel != nullptr && (unsigned)*p.sel == lead_sel_seq) {
-    p.Wp = p.Wp_alt; p.plane_w = p.plane_w_alt; p.bias = p.bias_alt; p.bias_shift = p.bias_shift_alt; p.N = p.N_alt; p.ldy = p.ldy_alt;
-    p.rscale = p.rscale_alt;
-  }
+  // (out_tile's arithmetic, written out: through the function this kernel's prologue is scheduled differently)
   const int ntiles = p.grid_m * p.grid_n;
   int t = blockIdx.x;
-  if ((ntiles & 7) == 0) t = (t & 7) * (ntiles >> 3) + (t >> 3);      // XCD-aware order (see payne_dense_kernel)
+  if ((ntiles & 7) == 0) t = (t & 7) * (ntiles >> 3) + (t >> 3);      // XCD-aware order
   const int m0 = (t % p.grid_m) * 64, n0 = (t / p.grid_m) * 128;
   if (n0 >= p.N) return;
   const int tid = threadIdx.x, lane = tid & 63;
@@ -639,7 +637,7 @@ __global__ void __launch_bounds__(512) payne_dense_dma2h_kernel(PAYNE_D3_LEAD_PA
     const int pl = isA ? (KD == 64 ? j : wave >> 2) : (KD == 64 ? jb >> 1 : jb);
     const int blk = isA ? (KD == 64 ? wave : wave & 3) : (KD == 64 ? 2 * wave + (jb & 1) : wave);
     const int row = RPP * blk + lrow;
-    const int c = lchunk ^ sw(row);                        // which 16-byte chunk of the row belongs in this lane's slot
+    const int c = lchunk ^ out_sw<ROWB>(row);                        // which 16-byte chunk of the row belongs in this lane's slot
     const int top = isA ? p.B - 1 - m0 : p.N - 1 - n0;     // (scalar) last real row of the tile
     const int r = (isA ? m0 : n0) + (row < top ? row : top);
     sbase[j] = isA ? reinterpret_cast<const unsigned char*>(p.Xp) + 2 * (size_t)pl * p.plane_x
@@ -662,26 +660,10 @@ __global__ void __launch_bounds__(512) payne_dense_dma2h_kernel(PAYNE_D3_LEAD_PA
 #pragma unroll
   for (int r = 0; r < 16; ++r) acc[r] = 0.f;
   const int Ra = wm0 + (lane & 31), Rb = wn0 + (lane & 31), h = lane >> 5;
-  const int sa = sw(Ra), sb = sw(Rb);
-  struct Frag { f16x8_t a[KS][2], b[KS][2]; };
-  auto frags = [&](int stage, Frag& f) {
-    const unsigned char* As = d2_sm + stage * STAGE;
-    const unsigned char* Bs = As + 2 * A_PLANE;
-#pragma unroll
-    for (int ks = 0; ks < KS; ++ks) {
-      const int c = 2 * ks + h;
-#pragma unroll
-      for (int pl = 0; pl < 2; ++pl) {
-        f.a[ks][pl] = *reinterpret_cast<const f16x8_t*>(As + pl * A_PLANE + Ra * ROWB + 16 * (c ^ sa));
-        f.b[ks][pl] = *reinterpret_cast<const f16x8_t*>(Bs + pl * B_PLANE + Rb * ROWB + 16 * (c ^ sb));
-      }
-    }
-  };
-  auto products = [&](const Frag& f, int ks) {             // smallest partial products first
-    acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(f.a[ks][1], f.b[ks][0], acc, 0, 0, 0);
-    acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(f.a[ks][0], f.b[ks][1], acc, 0, 0, 0);
-    acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(f.a[ks][0], f.b[ks][0], acc, 0, 0, 0);
-  };
+  const int sa = out_sw<ROWB>(Ra), sb = out_sw<ROWB>(Rb);
+  typedef OutFrag<F16x2, ROWB> Frag;
+  auto frags = [&](int stage, Frag& f) { out_frags<F16x2, ROWB, 128>(f, d2_sm + stage * STAGE, d2_sm + stage * STAGE + 2 * A_PLANE, Ra, Rb, sa, sb, h); };
+  auto products = [&](const Frag& f, int ks) { F16x2::products(acc, f.a[ks], f.b[ks]); };
   const int nk = NK > 0 ? NK : p.K / KD;                   // padded: exact
   const int k_tail = (p.k_real > 0 ? p.k_real : p.K) - (nk - 1) * KD;
   const int ks_last = __builtin_amdgcn_readfirstlane((k_tail + 15) >> 4);   // the zero-padded 16-deep steps of the last stage are skipped
@@ -791,24 +773,15 @@ template <int NK> constexpr size_t d2hh_lds_bytes() { return (size_t)NK * 16384 
 template <int NK>
 __global__ void __launch_bounds__(512) payne_dense_dma2hh_kernel(PAYNE_D3_LEAD_PARAMS, DenseParams p_) {
   DenseParams p = p_;
-  p.sel = lead_sel; p.Xp = lead_Xp; p.Wp = lead_Wp; p.plane_x = lead_plane_x; p.plane_w = lead_plane_w;
-  p.grid_m = (int)(lead_grid & 0xffffu); p.grid_n = (int)(lead_grid >> 16); p.N = lead_N; p.B = lead_B; p.ldp = lead_ldp; p.K = lead_K;
+  out_args(p, PAYNE_D3_LEAD_NAMES);
   constexpr int KD = 64, ROWB = 2 * KD, CPR = ROWB / 16, RPP = 1024 / ROWB;      // bytes a row, chunks a row (8), rows a piece (8)
   constexpr int PLANE = 64 * ROWB, STAGE = 2 * PLANE;                            // a 64-row plane (8 KB); two planes: an A stage, a B-half stage
   constexpr int NSB = 3, AHEAD = 2, KS = KD / 16, NT = 2 * NK;                   // ring slots, stages requested ahead, matrix steps a stage, stages
   constexpr int RING = NK * STAGE;
-  auto sw = [](int row) { return (row >> 1) & 7; };
   extern __shared__ __attribute__((aligned(16))) unsigned char d2_sm[];
-  if (p.sel != nullptr && (unsigned)*p.sel == lead_sel_seq) {
-    p.Wp = p.Wp_alt; p.plane_w = p.plane_w_alt; p.bias = p.bias_alt; p.bias_shift = p.bias_shift_alt; p.N = p.N_alt; p.ldy = p.ldy_alt;
-    p.rscale = p.rscale_alt;
-  }
-  const int ntiles = p.grid_m * p.grid_n;
-  int t = blockIdx.x;
-  if ((ntiles & 7) == 0) t = (t & 7) * (ntiles >> 3) + (t >> 3);      // XCD-aware order (see payne_dense_kernel)
-  const int m0 = (t % p.grid_m) * 64, n0 = (t / p.grid_m) * 128;
-  if (n0 >= p.N) return;
-  const int tid = threadIdx.x, lane = tid & 63;
+  const OutTile T = out_tile(p.grid_m, p.grid_m * p.grid_n);
+  if (T.n0 >= p.N) return;
+  const int m0 = T.m0, n0 = T.n0, tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int half = wave >> 2, w4 = wave & 3;                          // which half of the tile's outputs this wave multiplies
   const int wm0 = (w4 >> 1) * 32, wn0 = 64 * half + (w4 & 1) * 32;
@@ -823,7 +796,7 @@ __global__ void __launch_bounds__(512) payne_dense_dma2hh_kernel(PAYNE_D3_LEAD_P
     {
       const bool isA = j < 2;
       const int pl = j & 1, blk = wave;
-      const int row = RPP * blk + lrow, c = lchunk ^ sw(row);
+      const int row = RPP * blk + lrow, c = lchunk ^ out_sw<ROWB>(row);
       const int top = isA ? p.B - 1 - m0 : p.N - 1 - n0;
       const int r = (isA ? m0 : n0) + (row < top ? row : top);
       sb1[j] = isA ? reinterpret_cast<const unsigned char*>(p.Xp) + 2 * (size_t)pl * p.plane_x
@@ -833,7 +806,7 @@ __global__ void __launch_bounds__(512) payne_dense_dma2hh_kernel(PAYNE_D3_LEAD_P
     }
     {
       const int pl = j >> 1, blk = 2 * w4 + (j & 1);
-      const int row = RPP * blk + lrow, c = lchunk ^ sw(row);
+      const int row = RPP * blk + lrow, c = lchunk ^ out_sw<ROWB>(row);
       const int top = p.N - 1 - n0;
       const int r = n0 + (64 + row < top ? 64 + row : top);
       sb2[j] = reinterpret_cast<const unsigned char*>(p.Wp) + 2 * (size_t)pl * p.plane_w;
@@ -859,26 +832,12 @@ __global__ void __launch_bounds__(512) payne_dense_dma2hh_kernel(PAYNE_D3_LEAD_P
 #pragma unroll
   for (int r = 0; r < 16; ++r) acc[r] = 0.f;
   const int Ra = wm0 + (lane & 31), Rb = (w4 & 1) * 32 + (lane & 31), h = lane >> 5;      // rows inside the stage's A block / B-half slot
-  const int sa = sw(Ra), sb = sw(Rb);
-  struct Frag { f16x8_t a[KS][2], b[KS][2]; };
-  auto frags = [&](int q, Frag& f) {                          // stage q's operands of this wave's 32 x 32 block
-    const unsigned char* As = d2_sm + (q < NK ? q : q - NK) * STAGE;
-    const unsigned char* Bs = d2_sm + RING + (q % NSB) * STAGE;
-#pragma unroll
-    for (int ks = 0; ks < KS; ++ks) {
-      const int c = 2 * ks + h;
-#pragma unroll
-      for (int pl = 0; pl < 2; ++pl) {
-        f.a[ks][pl] = *reinterpret_cast<const f16x8_t*>(As + pl * PLANE + Ra * ROWB + 16 * (c ^ sa));
-        f.b[ks][pl] = *reinterpret_cast<const f16x8_t*>(Bs + pl * PLANE + Rb * ROWB + 16 * (c ^ sb));
-      }
-    }
+  const int sa = out_sw<ROWB>(Ra), sb = out_sw<ROWB>(Rb);
+  typedef OutFrag<F16x2, ROWB> Frag;
+  auto frags = [&](int q, Frag& f) {                          // stage q's operands of this wave's 32 x 32 block: resident A, ring B
+    out_frags<F16x2, ROWB, 64>(f, d2_sm + (q < NK ? q : q - NK) * STAGE, d2_sm + RING + (q % NSB) * STAGE, Ra, Rb, sa, sb, h);
   };
-  auto products = [&](const Frag& f, int ks) {             // smallest partial products first (payne_dense_dma2h_kernel's order)
-    acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(f.a[ks][1], f.b[ks][0], acc, 0, 0, 0);
-    acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(f.a[ks][0], f.b[ks][1], acc, 0, 0, 0);
-    acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(f.a[ks][0], f.b[ks][0], acc, 0, 0, 0);
-  };
+  auto products = [&](const Frag& f, int ks) { F16x2::products(acc, f.a[ks], f.b[ks]); };      // (payne_dense_dma2h_kernel's order)
   const int k_tail = (p.k_real > 0 ? p.k_real : p.K) - (NK - 1) * KD;
   const int ks_last = __builtin_amdgcn_readfirstlane((k_tail + 15) >> 4);   // the zero-padded 16-deep steps of a pass's last stage are skipped
   auto stage_products = [&](const Frag& f, bool last) {
@@ -983,23 +942,19 @@ constexpr int D3_STAGE = 3 * (64 + 128) * 64;              // bytes per stage
 template <int NS> constexpr size_t d3_lds_bytes() { return (size_t)NS * D3_STAGE; }
 template <int NK, int NS, bool PIPE>
 __global__ void __launch_bounds__(512) payne_dense_dma3_kernel(PAYNE_D3_LEAD_PARAMS, DenseParams p_) {
-  // (what the prologue's addresses hang off arrives in registers at wave start: the leading scalar parameters, preloaded --
-  //  -mllvm -amdgpu-kernarg-preload-count; read from the kernarg segment they are 400-700 cycles in front of the first request)
+  // (the unpacking of out_args, written out: through the function this kernel's registers come out numbered differently)
   DenseParams p = p_;
   p.sel = lead_sel; p.Xp = lead_Xp; p.Wp = lead_Wp; p.plane_x = lead_plane_x; p.plane_w = lead_plane_w;
   p.grid_m = (int)(lead_grid & 0xffffu); p.grid_n = (int)(lead_grid >> 16); p.N = lead_N; p.B = lead_B; p.ldp = lead_ldp; p.K = lead_K;
   constexpr int D3_NS = NS, AHEAD = PIPE ? D3_NS - 1 : 1;
   static_assert((PIPE && NS >= 3) || (!PIPE && NS == 2 && NK == 0), "ring depth / schedule");
   extern __shared__ __attribute__((aligned(16))) unsigned char d3_sm[];
-  if (p.sel != nullptr && (unsigned)*p.sel == lead_sel_seq) {   // (a scalar load and a uniform branch; launches without the word skip both)
+  if (p.sel != nullptr && (unsigned)*p.sel == lead_sel_seq) {
     p.Wp = p.Wp_alt; p.plane_w = p.plane_w_alt; p.bias = p.bias_alt; p.bias_shift = p.bias_shift_alt; p.N = p.N_alt; p.ldy = p.ldy_alt;
   }
-  const int ntiles = p.grid_m * p.grid_n;
-  int t = blockIdx.x;
-  if ((ntiles & 7) == 0) t = (t & 7) * (ntiles >> 3) + (t >> 3);      // XCD-aware order (see payne_dense_kernel)
-  const int m0 = (t % p.grid_m) * 64, n0 = (t / p.grid_m) * 128;
-  if (n0 >= p.N) return;                                     // (the grid was sized for the wider of the two output layers)
-  const int tid = threadIdx.x, lane = tid & 63;
+  const OutTile T = out_tile(p.grid_m, p.grid_m * p.grid_n);
+  if (T.n0 >= p.N) return;                                   // (the grid was sized for the wider of the two output layers)
+  const int m0 = T.m0, n0 = T.n0, tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int wm0 = (wave >> 2) * 32, wn0 = (wave & 3) * 32;
   const bool five = wave < 4;                              // pieces this wave moves per stage: 5 (waves 0-3) or 4
@@ -1039,29 +994,10 @@ __global__ void __launch_bounds__(512) payne_dense_dma3_kernel(PAYNE_D3_LEAD_PAR
 #pragma unroll
   for (int r = 0; r < 16; ++r) acc[r] = 0.f;
   const int Ra = wm0 + (lane & 31), Rb = wn0 + (lane & 31), h = lane >> 5;
-  const int sa = (Ra >> 2) & 3, sb = (Rb >> 2) & 3;
-  struct Frag { bf16x8_t a[2][3], b[2][3]; };
-  auto frags = [&](int stage, Frag& f) {
-    const unsigned char* As = d3_sm + stage * D3_STAGE;
-    const unsigned char* Bs = As + 3 * 4096;
-#pragma unroll
-    for (int ks = 0; ks < 2; ++ks) {                       // two 16-deep matrix steps per 32-deep stage
-      const int c = 2 * ks + h;
-#pragma unroll
-      for (int pl = 0; pl < 3; ++pl) {
-        f.a[ks][pl] = *reinterpret_cast<const bf16x8_t*>(As + pl * 4096 + Ra * 64 + 16 * (c ^ sa));
-        f.b[ks][pl] = *reinterpret_cast<const bf16x8_t*>(Bs + pl * 8192 + Rb * 64 + 16 * (c ^ sb));
-      }
-    }
-  };
-  auto products = [&](const Frag& f, int ks) {             // smallest partial products first
-    acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(f.a[ks][2], f.b[ks][0], acc, 0, 0, 0);
-    acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(f.a[ks][1], f.b[ks][1], acc, 0, 0, 0);
-    acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(f.a[ks][0], f.b[ks][2], acc, 0, 0, 0);
-    acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(f.a[ks][1], f.b[ks][0], acc, 0, 0, 0);
-    acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(f.a[ks][0], f.b[ks][1], acc, 0, 0, 0);
-    acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(f.a[ks][0], f.b[ks][0], acc, 0, 0, 0);
-  };
+  const int sa = out_sw<64>(Ra), sb = out_sw<64>(Rb);
+  typedef OutFrag<Bf16x3, 64> Frag;                        // two 16-deep matrix steps per 32-deep stage
+  auto frags = [&](int stage, Frag& f) { out_frags<Bf16x3, 64, 128>(f, d3_sm + stage * D3_STAGE, d3_sm + stage * D3_STAGE + 3 * 4096, Ra, Rb, sa, sb, h); };
+  auto products = [&](const Frag& f, int ks) { Bf16x3::products(acc, f.a[ks], f.b[ks]); };
   const int nk = NK > 0 ? NK : p.K / 32;                   // padded: exact
   const int k_tail = (p.k_real > 0 ? p.k_real : p.K) - (nk - 1) * 32;
   const bool last_both = __builtin_amdgcn_readfirstlane(k_tail > 16 ? 1 : 0) != 0;   // the zero-padded half of the last step is skipped
@@ -1178,12 +1114,9 @@ __global__ void __launch_bounds__(512) payne_dense_dma3f_kernel(PAYNE_D3_LEAD_PA
   if (p.sel != nullptr && (unsigned)*p.sel == lead_sel_seq) {
     Wf = p.W_alt; p.bias = p.bias_alt; p.bias_shift = p.bias_shift_alt; p.N = p.N_alt; p.ldy = p.ldy_alt;
   }
-  const int ntiles = p.grid_m * p.grid_n;
-  int t = blockIdx.x;
-  if ((ntiles & 7) == 0) t = (t & 7) * (ntiles >> 3) + (t >> 3);      // XCD-aware order (see payne_dense_kernel)
-  const int m0 = (t % p.grid_m) * 64, n0 = (t / p.grid_m) * 128;
-  if (n0 >= p.N) return;
-  const int tid = threadIdx.x, lane = tid & 63;
+  const OutTile T = out_tile(p.grid_m, p.grid_m * p.grid_n);
+  if (T.n0 >= p.N) return;
+  const int m0 = T.m0, n0 = T.n0, tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int wm0 = (wave >> 2) * 32, wn0 = (wave & 3) * 32;
   const bool two = wave < 4;                               // A pieces this wave moves per stage: 2 (waves 0-3) or 1
@@ -1261,29 +1194,10 @@ __global__ void __launch_bounds__(512) payne_dense_dma3f_kernel(PAYNE_D3_LEAD_PA
 #pragma unroll
   for (int r = 0; r < 16; ++r) acc[r] = 0.f;
   const int Ra = wm0 + (lane & 31), Rb = wn0 + (lane & 31), h = lane >> 5;
-  const int sa = (Ra >> 2) & 3, sb = (Rb >> 2) & 3;
-  struct Frag { bf16x8_t a[2][3], b[2][3]; };
-  auto frags = [&](int stage, Frag& f) {
-    const unsigned char* As = d3_sm + stage * D3_STAGE;
-    const unsigned char* Bs = As + 3 * 4096;
-#pragma unroll
-    for (int ks = 0; ks < 2; ++ks) {
-      const int c = 2 * ks + h;
-#pragma unroll
-      for (int pl = 0; pl < 3; ++pl) {
-        f.a[ks][pl] = *reinterpret_cast<const bf16x8_t*>(As + pl * 4096 + Ra * 64 + 16 * (c ^ sa));
-        f.b[ks][pl] = *reinterpret_cast<const bf16x8_t*>(Bs + pl * 8192 + Rb * 64 + 16 * (c ^ sb));
-      }
-    }
-  };
-  auto products = [&](const Frag& f, int ks) {             // smallest partial products first
-    acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(f.a[ks][2], f.b[ks][0], acc, 0, 0, 0);
-    acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(f.a[ks][1], f.b[ks][1], acc, 0, 0, 0);
-    acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(f.a[ks][0], f.b[ks][2], acc, 0, 0, 0);
-    acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(f.a[ks][1], f.b[ks][0], acc, 0, 0, 0);
-    acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(f.a[ks][0], f.b[ks][1], acc, 0, 0, 0);
-    acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(f.a[ks][0], f.b[ks][0], acc, 0, 0, 0);
-  };
+  const int sa = out_sw<64>(Ra), sb = out_sw<64>(Rb);
+  typedef OutFrag<Bf16x3, 64> Frag;
+  auto frags = [&](int stage, Frag& f) { out_frags<Bf16x3, 64, 128>(f, d3_sm + stage * D3_STAGE, d3_sm + stage * D3_STAGE + 3 * 4096, Ra, Rb, sa, sb, h); };
+  auto products = [&](const Frag& f, int ks) { Bf16x3::products(acc, f.a[ks], f.b[ks]); };
   constexpr int nk = NK;
   const int k_tail = (p.k_real > 0 ? p.k_real : p.K) - (nk - 1) * 32;
   const bool last_both = __builtin_amdgcn_readfirstlane(k_tail > 16 ? 1 : 0) != 0;
@@ -1398,8 +1312,9 @@ constexpr size_t b3_lds_bytes(bool h2 = false) { return (size_t)B3_NS * b3_stage
 template <bool H2>
 __global__ void __launch_bounds__(512) payne_dense_big3_kernel(DenseParams p) {
   // H2: operands as two fp16 planes, three products a block (see payne_dense_dma2h_kernel); else three bf16 planes, six products
-  constexpr int NPL = H2 ? 2 : 3, B3_STAGE = b3_stage(H2);
-  typedef typename std::conditional<H2, f16x8_t, bf16x8_t>::type frag_t;
+  typedef typename std::conditional<H2, F16x2, Bf16x3>::type Form;
+  typedef typename Form::frag_t frag_t;
+  constexpr int NPL = Form::kPlanes, B3_STAGE = b3_stage(H2);
   extern __shared__ __attribute__((aligned(16))) unsigned char b3_sm[];
   const int ntiles = p.grid_m * p.grid_n;
   // workgroup b sits on XCD b & 7 (round-robin dispatch); XCD x takes tiles [x per, (x + 1) per), its workgroups stride through them
@@ -1474,18 +1389,7 @@ __global__ void __launch_bounds__(512) payne_dense_big3_kernel(DenseParams p) {
 #pragma unroll
       for (int j = 0; j < 2; ++j) {
         f32x16 a = acc[i][j];
-        if constexpr (H2) {
-          a = __builtin_amdgcn_mfma_f32_32x32x16_f16(f.a[i][1], f.b[j][0], a, 0, 0, 0);
-          a = __builtin_amdgcn_mfma_f32_32x32x16_f16(f.a[i][0], f.b[j][1], a, 0, 0, 0);
-          a = __builtin_amdgcn_mfma_f32_32x32x16_f16(f.a[i][0], f.b[j][0], a, 0, 0, 0);
-        } else {
-        a = __builtin_amdgcn_mfma_f32_32x32x16_bf16(f.a[i][2], f.b[j][0], a, 0, 0, 0);
-        a = __builtin_amdgcn_mfma_f32_32x32x16_bf16(f.a[i][1], f.b[j][1], a, 0, 0, 0);
-        a = __builtin_amdgcn_mfma_f32_32x32x16_bf16(f.a[i][0], f.b[j][2], a, 0, 0, 0);
-        a = __builtin_amdgcn_mfma_f32_32x32x16_bf16(f.a[i][1], f.b[j][0], a, 0, 0, 0);
-        a = __builtin_amdgcn_mfma_f32_32x32x16_bf16(f.a[i][0], f.b[j][1], a, 0, 0, 0);
-        a = __builtin_amdgcn_mfma_f32_32x32x16_bf16(f.a[i][0], f.b[j][0], a, 0, 0, 0);
-        }
+        Form::products(a, f.a[i], f.b[j]);
         acc[i][j] = a;
       }
   };
