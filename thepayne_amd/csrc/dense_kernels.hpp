@@ -6,6 +6,7 @@
 
 #include "sed_core.hpp"
 #include "sampler_core.hpp"
+#include "out_plan.hpp"
 
 // ============================================================================
 // dense layer on the matrix cores
@@ -282,7 +283,7 @@ __global__ void __launch_bounds__(256) payne_dense_kernel(DenseParams p) {
 //     tile row r sits at chunk c ^ ((r >> 1) & 7) -- the lane simply FETCHES the chunk that belongs
 //     in its slot.
 //   * nothing can be masked on the way, so both operands must be zero-padded in k to a multiple
-//     of 32 in memory (X: the hidden buffers' pitch; W: ctx->w_out_pad) and rows are clamped.
+//     of 32 in memory (X: the hidden buffers' pitch; W: the context's OutOperands::pad) and rows are clamped.
 // ----------------------------------------------------------------------------
 // ring stages NS (NS - 1 requested ahead): at WN = 4 four of 32 columns = 96 KB -- one workgroup per CU, for launches of at
 // most one tile per CU (C2: 256 tiles) -- or three = 72 KB, two workgroups per CU, which cover each other's first loads and
@@ -1305,7 +1306,7 @@ __global__ void __launch_bounds__(512) payne_dense_dma3f_kernel(PAYNE_D3_LEAD_PA
 // (two lanes per row), 36 pieces: waves 0-3 move five, waves 4-7 four; the two 16-byte chunks of tile row r are swapped where
 // bit 4 of r is set: the sixteen lanes a ds_read_b128 serves together then cover sixteen different bank groups.
 // ----------------------------------------------------------------------------
-constexpr int B3_TM = 128, B3_TN = 256, B3_NS = 4;
+constexpr int B3_NS = 4;                                                   // (B3_TM x B3_TN: out_plan.hpp, where the launch is planned)
 constexpr int B3_A_PLANE = B3_TM * 32, B3_B_PLANE = B3_TN * 32;            // bytes per plane and stage
 constexpr int b3_stage(bool h2) { return (h2 ? 2 : 3) * (B3_A_PLANE + B3_B_PLANE); }
 constexpr size_t b3_lds_bytes(bool h2 = false) { return (size_t)B3_NS * b3_stage(h2); }

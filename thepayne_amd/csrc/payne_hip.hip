@@ -66,26 +66,30 @@ struct payne_ctx {
   float* hid[2] = {nullptr, nullptr};
   int ld_hid = 0;
   float* raw = nullptr;
-  const float* w_out_pad = nullptr;     // output layer's weights [N][w_out_kp], k zero-padded to a multiple of 32 (LDS-DMA kernel)
-  const float* w_hid_pad[PAYNE_MAX_LAYERS] = {};   // hidden layers: [N][ld_hid] copies, zero beyond K (hk_tile's LDS-DMA staging)
+  // The output layer's operand set: one for pixel rows, one for the same layer restated for rows in the frequency domain
+  // (host_tables.hpp freq_rows: what the likelihood and the predictions past stage 0 run when the post kernel can start from the
+  // transform, freq_ok).  pad: fp32 [rows][w_out_kp], k zero-padded to a multiple of 32 (the LDS-DMA kernels; payne_dense_dma3f_kernel
+  // splits it on the way into LDS); p3: three bf16 planes [3][rows][w_out_kp]; h2: two fp16 planes [2][rows][w_out_kp] with row n
+  // scaled by 2^e[n], rscale[n] = 2^-e[n] / act_scale; bias with bias_shift subtracted (the pixel rows are kept shifted by -1).
+  struct OutOperands { const float* pad = nullptr; unsigned short* p3 = nullptr; unsigned short* h2 = nullptr; const float* rscale = nullptr;
+                       const float* bias = nullptr; float bias_shift = 0.f; int rows = 0; };
+  OutOperands out_pix, out_frq;
+  bool freq_ok = false;
   int w_out_kp = 0;
+  const float* w_hid_pad[PAYNE_MAX_LAYERS] = {};   // hidden layers: [N][ld_hid] copies, zero beyond K (hk_tile's LDS-DMA staging)
   bool dma_ok = false;                  // hidden buffers are zero beyond the last hidden width
-  // 3 x bf16 planes for payne_dense_dma3_kernel: the output layer's weights [3][N][w_out_kp], the last hidden layer's output
-  // [3][b_max][ld_hid] (written by the hidden-layer kernel's epilogue; zero beyond the hidden width)
-  unsigned short* w_out_p3 = nullptr; unsigned short* hid_p3 = nullptr;
-  // the same output layer restated for rows in the frequency domain (host_tables.hpp freq_rows): what the likelihood and the
-  // predictions past stage 0 run when the post kernel can start from the transform (freq_ok)
-  unsigned short* w_out_p3z = nullptr; const float* bias_z = nullptr; bool freq_ok = false;
-  const float* w_out_padz = nullptr;    // the restated layer as fp32 [n][w_out_kp] (payne_dense_dma3f_kernel splits it on the way into LDS)
-  // two fp16 planes an operand (payne_dense_dma2h_kernel): the weights' planes [2][n][w_out_kp] with row n scaled by 2^e[n], rscale[n] =
-  // 2^-e[n] / act_scale; act_scale: the power of two the last hidden layer is written with (calibrated on the label box; 0 = not available)
-  unsigned short* w_out_h2 = nullptr; unsigned short* w_out_h2z = nullptr; const float* rscale = nullptr; const float* rscalez = nullptr;
+  // the last hidden layer's output as the output layer's operand planes [3][b_max][ld_hid] (written by the hidden-layer kernel's
+  // epilogue; zero beyond the hidden width); act_scale: the power of two it is written with as fp16 pairs (calibrated on the label
+  // box; 0 = not available)
+  unsigned short* hid_p3 = nullptr;
   float act_scale = 0.f;
-  // the second layer on fp16 pairs (hk_tile_h2): its weights as two fp16 planes [2][n_out][304], rows scaled; rs1 = 2^-e / a0_scale
-  unsigned short* w1_h2 = nullptr; const float* rs1 = nullptr; float a0_scale = 0.f; int w1_rows = 0;
-  // ... and the hidden layers past the second (hk_tile_h2x): layer l's weights as planes, rs = 2^-e / hs[l - 1]; hs[l]: the power of two
-  // layer l's output is written with; hid_h2: the activations between two such layers as planes [2][b_max][304] (two buffers taking turns)
-  unsigned short* wl_h2[PAYNE_MAX_LAYERS] = {}; const float* rsl[PAYNE_MAX_LAYERS] = {}; float hs[PAYNE_MAX_LAYERS] = {};
+  // Hidden layer l = 1 .. n - 2 on fp16 pairs (hk_tile_h2, hk_tile_h2x): its weights as two fp16 planes [2][n_out][304], rows scaled;
+  // rs = 2^-e / in_scale; in_scale: the power of two its input activations are written with.  Layer 1 alone has them for a net with
+  // two hidden layers; hid_pairs_deep: every hidden layer has, and hid_h2 (the activations between two such layers as planes
+  // [2][b_max][304], two buffers taking turns) and chain_flags exist.
+  struct HidPairs { unsigned short* planes = nullptr; const float* rs = nullptr; float in_scale = 0.f; };
+  HidPairs hid_pairs[PAYNE_MAX_LAYERS];
+  bool hid_pairs_deep = false;
   unsigned short* hid_h2[2] = {nullptr, nullptr};
   // payne_dense_chain_kernel: the row blocks' hop counters [ceil(b_max / 32)][kChainMax] (never reset) and the calls made so far
   unsigned long long* chain_flags = nullptr; unsigned long long chain_calls = 0;
@@ -427,17 +431,6 @@ static int make_h2_planes(payne_ctx* c, const float* d_w, const std::vector<floa
   return PAYNE_OK;
 }
 
-// Which kernel the output layer gets: decided by plan_out (below run_net's NetRef) and by nothing else.  The forms, each falling
-// back to the one before it: the generic tile kernel | fp32 operands by LDS-DMA | three bf16 planes an operand, six products
-// (equal hidden widths) | two fp16 planes, three products (activations calibrated on the label box).
-enum class OutForm { Generic, F32Dma, Bf16x3, H2 };
-// What the variant bits ask for; payne_ctx_create builds the fp16 planes for OutForm::H2 only.
-static OutForm wanted_out_form(unsigned variant) {
-  if (variant & PAYNE_V_OUT_GENERIC) return OutForm::Generic;
-  if (variant & (PAYNE_V_OUT_F32 | PAYNE_V_OUT_BK64)) return OutForm::F32Dma;
-  if (variant & (PAYNE_V_OUT_BF16X3 | PAYNE_V_OUT_PLANES)) return OutForm::Bf16x3;
-  return OutForm::H2;
-}
 // The power of two a layer's activations are written with as fp16 pairs: their largest magnitude on the label box lands in
 // [2048, 4096] (a factor of 8 to spare below fp16's range); 0 where the calibration found nothing usable.
 static float h2_act_scale(double amax) {
@@ -461,6 +454,23 @@ static int layer_h2_planes(payne_ctx* c, const float* d_w, int n, int k, int kp,
   return rc;
 }
 
+// An output layer's operand planes from its padded fp32 weights o.pad [o.rows][w_out_kp]: the three bf16 planes (OutForm::Bf16x3) unless
+// they exist, and with h2_scale > 0 the two fp16 planes and rscale (OutForm::H2) for activations written at that scale.  h_w: the
+// weights' host copy (null: fetched).  Both sets come here twice: what is allocated between the two calls keeps its place.
+static int build_out_planes(payne_ctx* c, payne_ctx::OutOperands& o, const std::vector<float>* h_w, float h2_scale) {
+  const int kp = c->w_out_kp;
+  const size_t nw = (size_t)o.rows * kp;
+  if (!o.p3) {
+    if (int rc = dev_alloc(c, 3 * nw, &o.p3, c->owned)) return rc;
+    hipLaunchKernelGGL(payne_split3_kernel, dim3((unsigned)((nw + 255) / 256)), dim3(256), 0, nullptr, o.pad, nw, o.p3, nw);
+    const hipError_t he = hipDeviceSynchronize();
+    if (he != hipSuccess) return fail(c, PAYNE_E_HIP, std::string("weight split: ") + hipGetErrorString(he));
+  }
+  if (!(h2_scale > 0.f)) return PAYNE_OK;
+  if (h_w) return make_h2_planes(c, o.pad, *h_w, o.rows, kp, h2_scale, &o.h2, &o.rscale);
+  return layer_h2_planes(c, o.pad, o.rows, kp, kp, h2_scale, "output layer", &o.h2, &o.rscale);
+}
+
 // payne_ctx_create, step by step: each returns a PAYNE_E_* code with c->err set.
 // The dense kernels' operand copies of the spectral net (c->layers is filled in; maxh: the widest hidden layer).
 static int create_dense_operands(payne_ctx* c, const payne_model_desc* model, const payne_opts* opts, int maxh) {
@@ -473,7 +483,8 @@ static int create_dense_operands(payne_ctx* c, const payne_model_desc* model, co
   if ((rc = dev_alloc(c, (size_t)L.n_out * Kp, &wp, c->owned))) return rc;
   he = hipMemcpy2D(wp, (size_t)Kp * 4, L.w, (size_t)L.n_in * 4, (size_t)L.n_in * 4, L.n_out, hipMemcpyDeviceToDevice);
   if (he != hipSuccess) return fail(c, PAYNE_E_HIP, std::string("hipMemcpy2D: ") + hipGetErrorString(he));
-  c->w_out_pad = wp; c->w_out_kp = Kp;
+  c->w_out_kp = Kp;
+  c->out_pix.pad = wp; c->out_pix.bias = L.b; c->out_pix.bias_shift = kBase; c->out_pix.rows = L.n_out;
   // the activations' pad columns are zero only if no wider layer ever wrote them: all hidden widths equal
   bool same = model->n_layers >= 3;
   for (int l = 1; l + 1 < model->n_layers; ++l) same = same && model->layers[l].n_out == model->layers[0].n_out;
@@ -495,11 +506,7 @@ static int create_dense_operands(payne_ctx* c, const payne_model_desc* model, co
     }
   }
   // the output layer's weights as three bf16 planes (OutForm::Bf16x3) ...
-  const size_t nw = (size_t)L.n_out * Kp;
-  if ((rc = dev_alloc(c, 3 * nw, &c->w_out_p3, c->owned))) return rc;
-  hipLaunchKernelGGL(payne_split3_kernel, dim3((unsigned)((nw + 255) / 256)), dim3(256), 0, nullptr, wp, nw, c->w_out_p3, nw);
-  he = hipDeviceSynchronize();
-  if (he != hipSuccess) return fail(c, PAYNE_E_HIP, std::string("weight split: ") + hipGetErrorString(he));
+  if ((rc = build_out_planes(c, c->out_pix, nullptr, 0.f))) return rc;
   // ... and as two fp16 planes (OutForm::H2), the activations' scale calibrated on the label box.  The hidden layers' fp16 planes
   // need the same calibration: it is made unless neither form is asked for.
   const bool out_h2 = wanted_out_form(opts->variant) == OutForm::H2, hid_h2 = !(opts->variant & PAYNE_V_HID_F32);
@@ -509,27 +516,27 @@ static int create_dense_operands(payne_ctx* c, const payne_model_desc* model, co
   // the second layer's weights for hk_tile_h2: widths whose padded K is the tile's 304 columns
   const payne_layer& L1 = model->layers[1];
   if (h2_act_scale(amaxl[0]) > 0.f && L1.n_in > 288 && L1.n_in <= 304 && c->w_hid_pad[1] && hid_h2) {
-    c->a0_scale = h2_act_scale(amaxl[0]);
-    if ((rc = layer_h2_planes(c, L1.w, L1.n_out, L1.n_in, 304, c->a0_scale, "second layer", &c->w1_h2, &c->rs1))) return rc;
-    c->w1_rows = L1.n_out;
-    c->hs[0] = c->a0_scale;
+    payne_ctx::HidPairs* hp = c->hid_pairs;
+    hp[1].in_scale = h2_act_scale(amaxl[0]);
+    if ((rc = layer_h2_planes(c, L1.w, L1.n_out, L1.n_in, 304, hp[1].in_scale, "second layer", &hp[1].planes, &hp[1].rs))) return rc;
     // deeper nets (LinNet: five hidden layers): the layers past the second the same way, their activations handed on as planes
     bool deep = model->n_layers > 3;
     for (int l = 1; l + 1 < model->n_layers; ++l) deep = deep && h2_act_scale(amaxl[l]) > 0.f && model->layers[l].n_out == L1.n_out;
     if (deep) {
-      for (int l = 1; l + 1 < model->n_layers; ++l) c->hs[l] = h2_act_scale(amaxl[l]);
       for (int l = 2; l + 1 < model->n_layers; ++l) {
         const payne_layer& Ll = model->layers[l];
-        if ((rc = layer_h2_planes(c, Ll.w, Ll.n_out, Ll.n_in, 304, c->hs[l - 1], "hidden layer", &c->wl_h2[l], &c->rsl[l]))) return rc;
+        hp[l].in_scale = h2_act_scale(amaxl[l - 1]);
+        if ((rc = layer_h2_planes(c, Ll.w, Ll.n_out, Ll.n_in, 304, hp[l].in_scale, "hidden layer", &hp[l].planes, &hp[l].rs))) return rc;
       }
       for (int q = 0; q < 2; ++q)
         if ((rc = dev_alloc(c, (size_t)2 * opts->b_max * 304, &c->hid_h2[q], c->owned))) return rc;
       if ((rc = dev_alloc(c, (size_t)((opts->b_max + 31) / 32) * kChainMax, &c->chain_flags, c->owned))) return rc;
+      c->hid_pairs_deep = true;
     }
   }
   if (h2_act_scale(amax) > 0.f && out_h2) {
     c->act_scale = h2_act_scale(amax);
-    if ((rc = layer_h2_planes(c, wp, L.n_out, Kp, Kp, c->act_scale, "output layer", &c->w_out_h2, &c->rscale))) return rc;
+    if ((rc = build_out_planes(c, c->out_pix, nullptr, c->act_scale))) return rc;
   }
   return PAYNE_OK;
 }
@@ -545,7 +552,7 @@ static int create_freq_rows(payne_ctx* c, const payne_model_desc* model, const p
   // (a model grid of any other length -- what a trained network has: readc3k.py:441-447 -- is resampled by the rotation stage first,
   //  a static linear map as well: the LDS kernels' lengths take rows of the RESAMPLED spectrum's transform, freq_rs)
   const bool ident = T.rot_identity && T.n1 == model->npix;
-  if (((fixed || c->big_chip || c->big_chip2) && ident || (fixed && !ident)) && c->w_out_p3 && c->hid_p3 && !(opts->variant & PAYNE_V_ROWS_PIXEL)) {
+  if (((fixed || c->big_chip || c->big_chip2) && ident || (fixed && !ident)) && c->out_pix.p3 && c->hid_p3 && !(opts->variant & PAYNE_V_ROWS_PIXEL)) {
     const payne_layer& L = model->layers[model->n_layers - 1];
     const int K = L.n_in, Kp = c->w_out_kp, n = ident ? L.n_out : T.n1;
     std::vector<float> W((size_t)L.n_out * K), b((size_t)L.n_out), Wz, bz;
@@ -560,21 +567,12 @@ static int create_freq_rows(payne_ctx* c, const payne_model_desc* model, const p
     }
     std::vector<float> Wp((size_t)n * Kp, 0.f);
     for (int i = 0; i < n; ++i) std::copy(Wz.begin() + (size_t)i * K, Wz.begin() + (size_t)(i + 1) * K, Wp.begin() + (size_t)i * Kp);
-    const float* d_wp = nullptr;
-    std::vector<void*> tmp;
-    if ((rc = upload(c, Wp, &d_wp, c->owned))) return rc;      // (kept: the fp32 form is what the one-tile-per-CU kernel reads)
-    c->w_out_padz = d_wp;
-    const size_t nw = (size_t)n * Kp;
-    rc = dev_alloc(c, 3 * nw, &c->w_out_p3z, c->owned);
-    if (!rc) {
-      hipLaunchKernelGGL(payne_split3_kernel, dim3((unsigned)((nw + 255) / 256)), dim3(256), 0, nullptr, d_wp, nw, c->w_out_p3z, nw);
-      he = hipDeviceSynchronize();
-    }
-    for (void* q : tmp) (void)hipFree(q);
-    if (rc) return rc;
-    if (he != hipSuccess) return fail(c, PAYNE_E_HIP, std::string("weight split: ") + hipGetErrorString(he));
-    if ((rc = upload(c, bz, &c->bias_z, c->owned))) return rc;
-    if (c->w_out_h2 && (rc = make_h2_planes(c, d_wp, Wp, n, Kp, c->act_scale, &c->w_out_h2z, &c->rscalez))) return rc;
+    payne_ctx::OutOperands& o = c->out_frq;
+    o.rows = n; o.bias_shift = 0.f;                             // (the shift is in the restated bias)
+    if ((rc = upload(c, Wp, &o.pad, c->owned))) return rc;      // (kept: the fp32 form is what the one-tile-per-CU kernel reads)
+    if ((rc = build_out_planes(c, o, &Wp, 0.f))) return rc;
+    if ((rc = upload(c, bz, &o.bias, c->owned))) return rc;
+    if (c->out_pix.h2 && (rc = build_out_planes(c, o, &Wp, c->act_scale))) return rc;
     c->freq_ok = true;
   }
   return PAYNE_OK;
@@ -674,7 +672,7 @@ extern "C" int payne_ctx_create(const payne_model_desc* model, const payne_obs_d
     if (model->n_layers > 2) {
       if ((rc = dev_alloc(c, (size_t)opts->b_max * c->ld_hid, &c->hid[0], c->owned))) return bail(rc);
       if ((rc = dev_alloc(c, (size_t)opts->b_max * c->ld_hid, &c->hid[1], c->owned))) return bail(rc);
-      if (c->w_out_p3 && (rc = dev_alloc(c, (size_t)3 * opts->b_max * c->ld_hid, &c->hid_p3, c->owned))) return bail(rc);
+      if (c->out_pix.p3 && (rc = dev_alloc(c, (size_t)3 * opts->b_max * c->ld_hid, &c->hid_p3, c->owned))) return bail(rc);
     }
     if ((rc = dev_alloc(c, (size_t)opts->b_max * std::max(model->npix, T.n1 <= 16384 ? T.n1 : 0), &c->raw, c->owned, false))) return bail(rc);   // (rows of n1 values: freq_rs)
     if ((rc = dev_alloc(c, (size_t)opts->b_max, &c->prep, c->owned, false))) return bail(rc);
@@ -856,78 +854,69 @@ static void launch_dense(DenseParams& p, hipStream_t s) {
   PAYNE_LAUNCH_DENSE((payne_dense_kernel<BM, BN, BK, FUSE>), dim3(p.grid_m * p.grid_n), dim3(256), s, p);
 }
 
-// Output layer, LDS-DMA form (64 x 128 tiles, 512 threads, BK-deep stages; NK: k-steps fixed at compile time or 0; NS: ring;
-// PIPE: schedule -- see the kernel).
-template <int BK, int NK, int NS, bool PIPE>
-static void launch_out_dma_nk(DenseParams& p, hipStream_t s) {
-  constexpr int WN = 4;
-  PAYNE_LAUNCH_DENSE((payne_dense_dma_kernel<WN, BK, NK, NS, PIPE>), dim3(p.grid_m * p.grid_n), dim3(128 * WN), s, p);
-}
-// What plan_out decides.
-struct OutPlan {
-  OutForm form = OutForm::Generic;
-  int grid_m = 0, grid_n = 0;        // tiles of the launch (64 x 128; big: 128 x 256), every form but Generic
-  bool sel = false;                  // rows of the resampled grid, or pixel rows if the batch's records say so
-  bool big = false;                  // Bf16x3, H2: many whole 128 x 256 tiles, persistent workgroups (payne_dense_big3_kernel)
-  bool own_cu = false;               // a compute unit for every tile: the deep / pipelined schedules
-  bool fixed = false;                // 300-wide nets: the k-steps of the 320 padded columns counted at compile time
-  bool bk64 = false;                 // F32Dma: three 64-deep stages (PAYNE_V_OUT_BK64)
-  bool halves = false;               // H2, fixed, own_cu: the tile finished in two halves (payne_dense_dma2hh_kernel)
-  bool split_w = false;              // Bf16x3, fixed, own_cu: fp32 weights split on their way into LDS (payne_dense_dma3f_kernel)
-};
-// F32Dma: 64 x 128 tiles, 512 threads (payne_dense_dma_kernel<WN = 4, BK, NK, NS, PIPE>).
-static void launch_out_dma(payne_ctx* c, DenseParams& p, hipStream_t s, const OutPlan& plan) {
-  p.k_real = p.K;                                          // the layer's own width: the padded tail is skipped
-  p.W = c->w_out_pad; p.K = c->w_out_kp;                   // padded pitch; X's pitch (ld_hid) is a multiple of 32 too
-  p.grid_m = plan.grid_m; p.grid_n = plan.grid_n;
-#ifdef PAYNE_STAMPS
-  p.stamps = g_dense_stamps;
-#endif
-  if (plan.bk64) {                                         // (variant: three 64-deep stages)
-    if (plan.fixed) launch_out_dma_nk<64, 5, 3, true>(p, s); else launch_out_dma_nk<64, 0, 3, true>(p, s);
-  } else if (plan.own_cu) {                                // one tile per CU at most: the pipelined schedule, four stages
-    if (plan.fixed) launch_out_dma_nk<32, 10, 4, true>(p, s); else launch_out_dma_nk<32, 0, 4, true>(p, s);
-  } else {
-    launch_out_dma_nk<32, 0, 3, false>(p, s);              // many tiles per CU: two workgroups per CU, the plain schedule
-  }
-}
+static const payne_ctx::OutOperands& out_ops(const payne_ctx* c, bool freq) { return freq ? c->out_frq : c->out_pix; }
 
-// Bf16x3 and H2: operand planes.  Many whole 128 x 256 tiles (C5) take payne_dense_big3_kernel's persistent workgroups, everything else one
-// 64 x 128 tile a workgroup -- whatever the batch, the same products in the same order: a candidate's rows do not depend on how many
-// others share its batch.
-static void launch_out_planes(payne_ctx* c, DenseParams& p, hipStream_t s, const OutPlan& plan, bool freq) {
+// The output layer's launch: plan_out (out_plan.hpp) has named the kernel, nothing is decided here.  `p` arrives with the layer as
+// run_net describes every layer (W, K, bias, Y, ...); the form's operands are filled in once, in front of the switch.
+// F32Dma: 64 x 128 tiles, 512 threads, BK-deep stages (NK: k-steps fixed at compile time or 0; NS: ring; PIPE: schedule -- see the
+// kernel).  Bf16x3 and H2: operand planes; Big3*: persistent workgroups, one a compute unit.
+static void launch_out(payne_ctx* c, DenseParams& p, hipStream_t s, const OutPlan& plan, bool freq, unsigned long long rot_seq) {
+  const payne_ctx::OutOperands& o = out_ops(c, freq);
   const bool h2 = plan.form == OutForm::H2;
-  p.k_real = p.K;
-  p.K = c->w_out_kp;
-  p.Wp = h2 ? (freq ? c->w_out_h2z : c->w_out_h2) : (freq ? c->w_out_p3z : c->w_out_p3); p.plane_w = (size_t)p.N * c->w_out_kp;
-  if (h2) p.rscale = freq ? c->rscalez : c->rscale;
-  if (freq) { p.bias = c->bias_z; p.bias_shift = 0.f; }
-  p.Xp = c->hid_p3; p.plane_x = (size_t)c->opts.b_max * c->ld_hid; p.ldp = c->ld_hid;
-  p.grid_m = plan.grid_m; p.grid_n = plan.grid_n;
+  if (plan.form != OutForm::Generic) {
+    p.k_real = p.K;                                          // the layer's own width: the padded tail is skipped
+    p.K = c->w_out_kp;                                       // padded pitch; X's pitch (ld_hid) is a multiple of 32 too
+    p.grid_m = plan.grid_m; p.grid_n = plan.grid_n;
+  }
+  if (plan.form == OutForm::F32Dma) p.W = o.pad;
+  if (plan.form >= OutForm::Bf16x3) {
+    if (plan.sel) {                                          // rows of the resampled grid; pixels if the batch's records say so
+      const payne_ctx::OutOperands& alt = c->out_pix;
+      p.sel = c->rot_flag; p.sel_seq = rot_seq;
+      p.Wp_alt = h2 ? alt.h2 : alt.p3; p.plane_w_alt = (size_t)p.N * c->w_out_kp; p.bias_alt = alt.bias; p.bias_shift_alt = alt.bias_shift;
+      if (h2) p.rscale_alt = alt.rscale;
+      p.N_alt = p.N; p.ldy_alt = p.ldy;
+      p.N = c->T.n1; p.ldy = c->T.n1;
+    }
+    p.Wp = h2 ? o.h2 : o.p3; p.plane_w = (size_t)p.N * c->w_out_kp;
+    if (h2) p.rscale = o.rscale;
+    p.bias = o.bias; p.bias_shift = o.bias_shift;
+    p.Xp = c->hid_p3; p.plane_x = (size_t)c->opts.b_max * c->ld_hid; p.ldp = c->ld_hid;
+    if (plan.kernel == OutKernel::Dma3f10) {                 // the fp32 weights go through Wp's port
+      p.W_alt = c->out_pix.pad;
+      p.Wp = reinterpret_cast<const unsigned short*>(o.pad);
+    }
+  }
 #ifdef PAYNE_STAMPS
-  if (!(h2 && plan.big)) p.stamps = g_dense_stamps;
+  if (plan.form != OutForm::Generic && plan.kernel != OutKernel::Big3H2) p.stamps = g_dense_stamps;
 #endif
   const dim3 grid(p.grid_m * p.grid_n), block(512);
-  if (plan.big && h2) PAYNE_LAUNCH_DENSE(payne_dense_big3_kernel<true>, dim3(c->n_cu), dim3(512), s, p);
-  else if (plan.big) PAYNE_LAUNCH_DENSE(payne_dense_big3_kernel<false>, dim3(c->n_cu), block, s, p);       // half the operand bytes per product
-  // H2, 300-wide nets: five 64-deep steps when every tile has a compute unit to itself (C2: 144 KB of LDS a workgroup), ten 32-deep ones
-  // otherwise; other widths, and PAYNE_V_OUT_ROLLED: 32-deep steps counted at run time.  Same products in the same order in all three.
-  // (... finished in two halves: the left half's rows leave under the right half's products -- payne_dense_dma2hh_kernel, same rows to the bit)
-  else if (plan.halves) PAYNE_LAUNCH_DENSE((payne_dense_dma2hh_kernel<5>), grid, block, s, PAYNE_D3_LEAD_ARGS(p), p);
-  else if (h2 && plan.fixed && plan.own_cu) PAYNE_LAUNCH_DENSE((payne_dense_dma2h_kernel<5, 64>), grid, block, s, PAYNE_D3_LEAD_ARGS(p), p);
-  else if (h2 && plan.fixed) PAYNE_LAUNCH_DENSE((payne_dense_dma2h_kernel<10, 32>), grid, block, s, PAYNE_D3_LEAD_ARGS(p), p);
-  else if (h2) PAYNE_LAUNCH_DENSE((payne_dense_dma2h_kernel<0, 32>), grid, block, s, PAYNE_D3_LEAD_ARGS(p), p);
-  else if (!plan.own_cu) PAYNE_LAUNCH_DENSE((payne_dense_dma3_kernel<0, 2, false>), grid, block, s, PAYNE_D3_LEAD_ARGS(p), p);   // many tiles per CU
-  else if (plan.split_w) {
-    // the weights as fp32 through the port, split into the planes on their way into LDS (28 instead of 36 KB a step)
-    p.W_alt = c->w_out_pad;
-    const unsigned short* keep = p.Wp;
-    p.Wp = reinterpret_cast<const unsigned short*>(freq ? c->w_out_padz : c->w_out_pad);
-    PAYNE_LAUNCH_DENSE((payne_dense_dma3f_kernel<10>), grid, block, s, PAYNE_D3_LEAD_ARGS(p), p);
-    p.Wp = keep;
+  // (the fp32 ring's instantiations report the name their launch had inside its template)
+#define OUT_DMA(BK, NK, NS, PIPE)                                                                                                    \
+  PAYNE_LAUNCH_AS("(payne_dense_dma_kernel<WN, BK, NK, NS, PIPE>)", (payne_dense_dma_kernel<4, BK, NK, NS, PIPE>), grid, block,       \
+                  (DenseLds<(payne_dense_dma_kernel<4, BK, NK, NS, PIPE>)>::value), s, p)
+#define OUT_PLANES(kernel) PAYNE_LAUNCH_DENSE(kernel, grid, block, s, PAYNE_D3_LEAD_ARGS(p), p)
+  switch (plan.kernel) {
+    case OutKernel::GenericFused: launch_dense<64, 64, 32, true>(p, s); break;
+    case OutKernel::Generic:      launch_dense<64, 64, 32, false>(p, s); break;     // nets whose hidden widths differ, the continuum network
+    case OutKernel::Dma32Nk10Ns4: OUT_DMA(32, 10, 4, true); break;
+    case OutKernel::Dma32Ns4:     OUT_DMA(32, 0, 4, true); break;
+    case OutKernel::Dma32Ns3:     OUT_DMA(32, 0, 3, false); break;
+    case OutKernel::Dma64Nk5:     OUT_DMA(64, 5, 3, true); break;
+    case OutKernel::Dma64:        OUT_DMA(64, 0, 3, true); break;
+    case OutKernel::Big3H2:       PAYNE_LAUNCH_DENSE(payne_dense_big3_kernel<true>, dim3(c->n_cu), dim3(512), s, p); break;
+    case OutKernel::Big3:         PAYNE_LAUNCH_DENSE(payne_dense_big3_kernel<false>, dim3(c->n_cu), block, s, p); break;
+    case OutKernel::Dma2hh5:      OUT_PLANES((payne_dense_dma2hh_kernel<5>)); break;
+    case OutKernel::Dma2h5x64:    OUT_PLANES((payne_dense_dma2h_kernel<5, 64>)); break;
+    case OutKernel::Dma2h10x32:   OUT_PLANES((payne_dense_dma2h_kernel<10, 32>)); break;
+    case OutKernel::Dma2h0x32:    OUT_PLANES((payne_dense_dma2h_kernel<0, 32>)); break;
+    case OutKernel::Dma3f10:      OUT_PLANES((payne_dense_dma3f_kernel<10>)); break;
+    case OutKernel::Dma3Nk10Ns4:  OUT_PLANES((payne_dense_dma3_kernel<10, 4, true>)); break;
+    case OutKernel::Dma3Ns4:      OUT_PLANES((payne_dense_dma3_kernel<0, 4, true>)); break;
+    case OutKernel::Dma3Ns2:      OUT_PLANES((payne_dense_dma3_kernel<0, 2, false>)); break;
   }
-  else if (plan.fixed) PAYNE_LAUNCH_DENSE((payne_dense_dma3_kernel<10, 4, true>), grid, block, s, PAYNE_D3_LEAD_ARGS(p), p);
-  else PAYNE_LAUNCH_DENSE((payne_dense_dma3_kernel<0, 4, true>), grid, block, s, PAYNE_D3_LEAD_ARGS(p), p);
+#undef OUT_DMA
+#undef OUT_PLANES
 }
 
 // The hidden-layer kernel's leading arguments carry two 16-bit values a dword (n_prep: 15 bits): what does not fit is refused
@@ -985,13 +974,12 @@ static void launch_hidden(DenseParams& p, PrepArgs& pa, hipStream_t s, int n_cu 
 #undef PAYNE_HK_ARGS
 }
 
-// ANN forward for the batch -> c->raw [B][npix] (shifted by -1)
 // One network of the context: the spectral emulator or the continuum network.
 struct NetRef {
   const payne_layer* layers; int n_layers; int n_labels; const double* xmin; const double* xden;
   float* const* hid; int ld_hid; float* out; int ld_out; float out_shift;
   bool spectral;                      // the spectral net owns the DMA / bf16x3 operand copies and the prep records
-  bool freq = false;                  // spectral net: rows written in the frequency domain (c->w_out_p3z)
+  bool freq = false;                  // spectral net: rows written in the frequency domain (c->out_frq)
   bool sel = false;                   // ... as rows of the resampled grid, or pixel rows if the batch's records say so (freq_rs)
 };
 static NetRef spectral_net(const payne_ctx* c) {
@@ -1013,137 +1001,140 @@ struct BatchRows {
 };
 // A sampler's walk in progress asks the likelihood batch being enqueued to make the next step's proposals ahead (rwalk_spec_wave).
 struct SpecReq { const WalkTail* walk; const WalkState* w; int step, K; };      // (walk == null: no request)
-// The output layer's form for net N whatever domain its rows go out in (rows in the frequency domain need Bf16x3 or better).
-static OutForm out_form(const payne_ctx* c, const NetRef& N) {
-  OutForm f = wanted_out_form(c->opts.variant);
-  if (!(N.spectral && c->dma_ok && c->ld_hid >= c->w_out_kp)) return OutForm::Generic;       // hidden widths differ, the continuum network
-  if (f >= OutForm::Bf16x3 && !(c->w_out_p3 && c->hid_p3)) f = OutForm::F32Dma;
-  if (f == OutForm::H2) {
-    // (payne_dense_dma2h_kernel addresses an operand plane by 32-bit byte offsets: rows x pitch x 2 bytes below 2^31)
-    const unsigned long long plane_w = 2ull * (unsigned long long)std::max(N.layers[N.n_layers - 1].n_out, c->T.n1) * (unsigned long long)c->w_out_kp;
-    const unsigned long long plane_x = 2ull * (unsigned long long)c->opts.b_max * (unsigned long long)c->ld_hid;
-    if (plane_w >= (1ull << 31) || plane_x >= (1ull << 31) || !c->w_out_h2 || !(c->act_scale > 0.f)) f = OutForm::Bf16x3;
-  }
+// What plan_out and out_form (out_plan.hpp) read of this context for net N.
+static OutFacts out_facts(const payne_ctx* c, const NetRef& N) {
+  OutFacts f;
+  f.variant = c->opts.variant; f.n_cu = c->n_cu; f.b_max = c->opts.b_max; f.ld_hid = c->ld_hid; f.w_out_kp = c->w_out_kp; f.n1 = c->T.n1;
+  f.n_layers = N.n_layers; f.n_out = N.layers[N.n_layers - 1].n_out; f.spectral = N.spectral; f.freq = N.freq; f.sel = N.sel;
+  f.dma_ok = c->dma_ok; f.act_scale = c->act_scale;
+  f.p3 = c->out_pix.p3 && c->hid_p3; f.h2 = c->out_pix.h2; f.h2_freq = c->out_frq.h2; f.pad = c->out_pix.pad; f.pad_freq = c->out_frq.pad;
   return f;
 }
-// The output layer's kernel for a batch of B through net N (N.freq: the rows go out transformed; N.sel: ... of the resampled grid):
-// every variant bit and every shape that bears on it is tested here and in out_form.  DESIGN section 1 has the table.
-static OutPlan plan_out(const payne_ctx* c, const NetRef& N, int B) {
-  const unsigned v = c->opts.variant;
-  const int kp = c->w_out_kp, n_out = N.layers[N.n_layers - 1].n_out;
-  OutPlan o; o.sel = N.sel;
-  const int n_launch = o.sel ? c->T.n1 : n_out;             // (rows of the resampled grid: T.n1 values)
-  o.form = out_form(c, N);
-  if (o.form == OutForm::H2 && N.freq && !c->w_out_h2z) o.form = OutForm::Bf16x3;
-  if (o.form == OutForm::Generic) return o;
-  o.grid_m = (B + 63) / 64; o.grid_n = (n_launch + 127) / 128;
-  o.own_cu = o.grid_m * o.grid_n <= c->n_cu;
-  o.fixed = kp == 320 && !(v & PAYNE_V_OUT_ROLLED);        // H = 300 -> 320 columns
-  if (o.form == OutForm::F32Dma) { o.bk64 = kp % 64 == 0 && (v & PAYNE_V_OUT_BK64); return o; }
-  if (B % B3_TM == 0 && n_launch % B3_TN == 0 && (B / B3_TM) * (n_launch / B3_TN) >= 2 * c->n_cu && !(v & PAYNE_V_OUT_SMALL_TILES) && !o.sel) {
-    o.big = true; o.grid_m = B / B3_TM; o.grid_n = n_launch / B3_TN;
-    return o;
-  }
-  if (o.form == OutForm::H2) o.halves = o.fixed && o.own_cu && !(v & PAYNE_V_OUT_WHOLE_TILE);
-  else o.split_w = o.fixed && o.own_cu && (N.freq ? c->w_out_padz : c->w_out_pad) && !(v & PAYNE_V_OUT_PLANES) && (!o.sel || c->w_out_pad);
-  return o;
+
+// ---- one forward pass: run_net and its steps -------------------------------------------------------------------------
+// Layer l of net N for a batch of B as every launch starts from it; layer 1 with the label encoding and the first layer fused in.
+static DenseParams layer_params(const payne_ctx* c, const NetRef& N, int l, int B, const double* theta) {
+  DenseParams p{};
+  const payne_layer& L = N.layers[l];
+  const bool last = l == N.n_layers - 1;
+  p.W = L.w; p.K = L.n_in; p.bias = L.b; p.N = L.n_out; p.B = B; p.act = L.act;
+  p.bias_shift = last ? N.out_shift : 0.f;
+  p.Y = last ? N.out : N.hid[(l - 1) & 1];
+  p.ldy = last ? N.ld_out : N.ld_hid;
+  if (l > 1) { p.X = N.hid[(l - 2) & 1]; p.ldx = N.ld_hid; return p; }
+  const payne_layer& L0 = N.layers[0];
+  p.theta = theta; p.ld_theta = c->ncols;
+  p.W0 = L0.w; p.b0 = L0.b; p.n_labels = N.n_labels; p.act0 = L0.act; p.K0 = L0.n_out;
+  for (int d = 0; d < N.n_labels; ++d) { p.xmin[d] = N.xmin[d]; p.xden[d] = N.xden[d]; }
+  return p;
 }
-// `sed`: a joint likelihood's photometric nets ride in the first hidden-layer launch (sed_tile); *sed is cleared when they did.
+// What hidden layer l adds: its weights' copy at the activations' pitch (hk_tile's LDS-DMA staging), and where its output goes as
+// planes too -- the last one's as the output layer's operand (Bf16x3: three bf16 planes, H2: two fp16 planes), an earlier one's as the
+// next layer's where the hidden layers run on fp16 pairs (hk_tile_h2x).  True: the copy is there.
+static bool hidden_params(const payne_ctx* c, const NetRef& N, const OutPlan& plan, int l, DenseParams& p) {
+  if (l == N.n_layers - 2 && plan.form >= OutForm::Bf16x3) {
+    p.Yp = c->hid_p3; p.plane_y = (size_t)c->opts.b_max * c->ld_hid; p.ldp = c->ld_hid;
+    if (plan.form == OutForm::H2) { p.yp_half = 1; p.yp_scale = c->act_scale; }
+  } else if (l < N.n_layers - 2 && N.spectral && c->hid_pairs_deep) {
+    p.Yp = c->hid_h2[(l - 1) & 1]; p.plane_y = (size_t)c->opts.b_max * 304; p.ldp = 304; p.yp_half = 1; p.yp_scale = c->hid_pairs[l + 1].in_scale;
+  }
+  if (!(N.spectral && c->w_hid_pad[l] && N.ld_hid >= HK_PITCH)) return false;
+  p.Wd = c->w_hid_pad[l]; p.ldwd = N.ld_hid;
+  return true;
+}
+// Layers 0 and 1 in one launch, and what rides in it: the post kernel's records (pa.out), a joint likelihood's photometric tiles
+// (sed_tile), the walk's next proposals made ahead (spec_K of them; 0: none).  pairs: layer 1 on fp16 pairs (hk_tile_h2).
+static void first_launch(payne_ctx* c, const NetRef& N, hipStream_t s, DenseParams& p, PrepArgs& pa, bool sed_rides, int spec_K, const SpecReq& spec,
+                         bool pairs) {
+  if (sed_rides) { pa.P = c->P; pa.sed_mags = c->mags_ws; pa.sed_off = 8 + c->opts.npoly; pa.sed_photscale = c->opts.photscale; }
+  if (spec_K) { pa.spec_walk = spec.walk; pa.spec_w = *spec.w; pa.spec_step = spec.step; }
+  if (pairs) {
+    const payne_ctx::HidPairs& h = c->hid_pairs[1];
+    p.h2_tiles = 1; p.Wh = h.planes; p.plane_wh = (size_t)p.N * 304; p.rs1 = h.rs; p.a0_scale = h.in_scale;
+  }
+  ProfScope ps(c, s, 3);
+  launch_hidden<true>(p, pa, s, c->n_cu, spec_K, (c->opts.variant & PAYNE_V_HID_WAVES4) != 0);
+}
+static void hidden_launch(payne_ctx* c, const NetRef& N, int l, hipStream_t s, DenseParams& p) {
+  PrepArgs pa{};
+  if (N.spectral && c->hid_pairs_deep) {                    // both operands as planes
+    const payne_ctx::HidPairs& h = c->hid_pairs[l];
+    p.h2_tiles = 1; p.Wh = h.planes; p.plane_wh = (size_t)p.N * 304; p.rs1 = h.rs;
+    p.Xp = c->hid_h2[(l - 2) & 1]; p.plane_x = (size_t)c->opts.b_max * 304;
+  }
+  ProfScope ps(c, s, 3);
+  launch_hidden<false>(p, pa, s);
+}
+// Layers 2 .. n - 2 in ONE launch: hand-offs inside a 32-candidate row block (payne_dense_chain_kernel; opt-in: a hop costs more
+// than a launch on this machine, NOTES R6.10).
+static void chain_launch(payne_ctx* c, const NetRef& N, const OutPlan& plan, int B, hipStream_t s) {
+  const int n = N.n_layers;
+  ChainParams cp{};
+  cp.n = n - 3;
+  for (int q = 2; q <= n - 2; ++q) {
+    const payne_layer& Lq = N.layers[q];
+    cp.Wh[q - 2] = c->hid_pairs[q].planes; cp.rs[q - 2] = c->hid_pairs[q].rs; cp.bias[q - 2] = Lq.b; cp.act[q - 2] = Lq.act;
+    cp.out_scale[q - 2] = (q == n - 2) ? c->act_scale : c->hid_pairs[q + 1].in_scale;
+  }
+  cp.buf[0] = c->hid_h2[0]; cp.buf[1] = c->hid_h2[1]; cp.plane_x = (size_t)c->opts.b_max * 304;
+  cp.first_in = 0;                                          // (layer 1 wrote hid_h2[0]: hidden_params, (l - 1) & 1 at l = 1)
+  cp.Yp_last = c->hid_p3; cp.plane_y_last = (size_t)c->opts.b_max * c->ld_hid; cp.ldp_last = c->ld_hid; cp.half_last = plan.form == OutForm::H2 ? 1 : 0;
+  cp.flags = c->chain_flags; cp.grid_n = (N.layers[2].n_out + 31) / 32;
+  cp.target0 = c->chain_calls * (unsigned long long)cp.grid_n;
+  cp.B = B; cp.N = N.layers[2].n_out; cp.grid_m = (B + 31) / 32; cp.grid_m_max = (c->opts.b_max + 31) / 32;
+  ++c->chain_calls;
+  ProfScope ps(c, s, 3);
+  PAYNE_LAUNCH_DENSE(payne_dense_chain_kernel, dim3(cp.grid_m_max * cp.grid_n), dim3(256), s, cp);
+}
+static void out_launch(payne_ctx* c, const NetRef& N, const OutPlan& plan, hipStream_t s, unsigned long long rot_seq, DenseParams& p) {
+  ProfScope ps(c, s, 0);
+  launch_out(c, p, s, plan, N.freq, rot_seq);
+}
+
+// ANN forward for the batch -> N.out [B][ld_out] (the spectral net: c->raw, shifted by -1): the first launch; the chain or the hidden
+// layers 2 .. n - 2; the output layer.  A two-layer net is the output layer alone, the labels fused in (OutKernel::GenericFused).
+// `sed`: a joint likelihood's photometric nets ride in the first launch; *sed is cleared when they did.
 // `R` (the spectral net's): gets the records and whether the walk's proposals `spec` went along; R->rot_seq is read where plan.sel.
 static int run_net(payne_ctx* c, const NetRef& N, const OutPlan& plan, const double* theta, int B, double instr_factor, hipStream_t s,
                    BatchRows* R = nullptr, bool* sed = nullptr, const SpecReq& spec = SpecReq{}) {
   const int n = N.n_layers;
-  const bool use3 = plan.form >= OutForm::Bf16x3, use2h = plan.form == OutForm::H2;   // (the last hidden layer writes that form's planes)
-  for (int l = 1; l < n; ++l) {
-    DenseParams p{};
-    const payne_layer& L = N.layers[l];
-    const bool last = (l == n - 1);
-    p.W = L.w; p.K = L.n_in; p.bias = L.b; p.N = L.n_out; p.B = B; p.act = L.act;
-    p.bias_shift = last ? N.out_shift : 0.f;
-    p.Y = last ? N.out : N.hid[(l - 1) & 1];
-    p.ldy = last ? N.ld_out : N.ld_hid;
-    if (use3 && l == n - 2) {
-      p.Yp = c->hid_p3; p.plane_y = (size_t)c->opts.b_max * c->ld_hid; p.ldp = c->ld_hid;
-      if (use2h) { p.yp_half = 1; p.yp_scale = c->act_scale; }
-    }
-    // hidden layers past the second on fp16 pairs (hk_tile_h2x): layer l hands its activations to layer l + 1 as planes
-    const bool chain = N.spectral && c->hid_h2[0] && c->w1_h2 && c->w1_rows == N.layers[1].n_out;
-    if (chain && !last && l + 1 <= n - 2 && c->wl_h2[l + 1]) {
-      p.Yp = c->hid_h2[(l - 1) & 1]; p.plane_y = (size_t)c->opts.b_max * 304; p.ldp = 304; p.yp_half = 1; p.yp_scale = c->hs[l];
-    }
-    ProfScope ps(c, s, last ? 0 : 3);
-    if (l == 1) {
-      const payne_layer& L0 = N.layers[0];
-      p.theta = theta; p.ld_theta = c->ncols;
-      p.W0 = L0.w; p.b0 = L0.b; p.n_labels = N.n_labels; p.act0 = L0.act; p.K0 = L0.n_out;
-      for (int d = 0; d < N.n_labels; ++d) { p.xmin[d] = N.xmin[d]; p.xden[d] = N.xden[d]; }
-      PrepArgs pa{};
-      pa.T = c->T; pa.T.raw_freq = N.freq ? 1 : 0; pa.instr_factor = instr_factor;      // (the tables are read by the records' writers only)
-      pa.out = (N.spectral && c->prep && c->obs_bound && !(c->opts.variant & PAYNE_V_NO_PREP)) ? c->prep : nullptr;
-      if (plan.sel) { pa.rot_flag = c->rot_flag; pa.rot_seq = R->rot_seq; }
-      if (!last && sed && *sed && N.spectral && sed_tile_ok(c->P.H) && !(c->opts.variant & PAYNE_V_SED_OWN_LAUNCH)) {
-        pa.P = c->P; pa.sed_mags = c->mags_ws; pa.sed_off = 8 + c->opts.npoly; pa.sed_photscale = c->opts.photscale;
-        *sed = false;
-      }
-      // the walk's next proposals ride along when this batch's post kernel will run the chain step at its tail (run_post)
-      const int spec_K = (!last && N.spectral && spec.walk && pa.out && c->lean_available && !c->big_ws) ? spec.K : 0;
-      if (spec_K) { pa.spec_walk = spec.walk; pa.spec_w = *spec.w; pa.spec_step = spec.step; }
-      if (!last && N.spectral && c->w_hid_pad[1] && N.ld_hid >= HK_PITCH) { p.Wd = c->w_hid_pad[1]; p.ldwd = N.ld_hid; }
-      if (!last && N.spectral && p.Wd && c->w1_h2 && c->w1_rows == p.N && p.K <= 304 &&
-          (unsigned long long)B * (unsigned)c->ncols * 8ull < (1ull << 31)) {                // the second layer on fp16 pairs (hk_tile_h2: 32-bit byte offsets into theta)
-        p.h2_tiles = 1; p.Wh = c->w1_h2; p.plane_wh = (size_t)c->w1_rows * 304; p.rs1 = c->rs1; p.a0_scale = c->a0_scale;
-      }
-      if (!last && !hk_lead_fits(p.B, p.N, p.K, p.K0, 0, p.ldwd, p.ld_theta, spec_K))
+  const unsigned v = c->opts.variant;
+  const unsigned long long rot_seq = plan.sel ? R->rot_seq : 0;
+  DenseParams out = layer_params(c, N, n - 1, B, theta);
+  if (n > 2) {
+    DenseParams p = layer_params(c, N, 1, B, theta);
+    const bool dma_l1 = hidden_params(c, N, plan, 1, p);
+    const bool records = N.spectral && c->prep && c->obs_bound && !(v & PAYNE_V_NO_PREP);
+    const bool sed_rides = sed && *sed && N.spectral && sed_tile_ok(c->P.H) && !(v & PAYNE_V_SED_OWN_LAUNCH);
+    // (proposals ahead: when this batch's post kernel will run the chain step at its tail, run_post)
+    const int spec_K = (N.spectral && spec.walk && records && c->lean_available && !c->big_ws) ? spec.K : 0;
+    // (hk_tile_h2: 32-bit byte offsets into theta)
+    const bool pairs_l1 = dma_l1 && c->hid_pairs[1].planes && p.K <= 304 && (unsigned long long)B * (unsigned)c->ncols * 8ull < (1ull << 31);
+    // layers 2 .. n - 2 as one launch: asked for, three at least, all on fp16 pairs, a workgroup slot for every tile of the largest batch
+    const bool chained = N.spectral && c->hid_pairs_deep && plan.form >= OutForm::Bf16x3 && n - 2 >= 3 && (v & PAYNE_V_HID_CHAIN) &&
+                         ((c->opts.b_max + 31) / 32) * ((N.layers[2].n_out + 31) / 32) <= 2 * c->n_cu && n - 3 <= kChainMax;
+    for (int l = 1; l <= (chained ? 1 : n - 2); ++l) {     // what the packed arguments cannot hold is refused before anything is launched
+      const payne_layer& L = N.layers[l];
+      const int ldwd = (N.spectral && c->w_hid_pad[l] && N.ld_hid >= HK_PITCH) ? N.ld_hid : 0;
+      if (!(l == 1 ? hk_lead_fits(B, L.n_out, L.n_in, p.K0, 0, ldwd, p.ld_theta, spec_K) : hk_lead_fits(B, L.n_out, L.n_in, 0, N.ld_hid, ldwd, 0, 0)))
         return fail(c, PAYNE_E_UNSUPPORTED, "batch x hidden width beyond what the hidden-layer kernel's packed arguments hold (65 535 tiles of 32 x 32)");
-      if (last) launch_dense<64, 64, 32, true>(p, s);
-      else launch_hidden<true>(p, pa, s, c->n_cu, spec_K, (c->opts.variant & PAYNE_V_HID_WAVES4) != 0);
-      if (!last && R) { R->prep = pa.out; R->spec = spec_K != 0; }
-    } else if (!last && chain && use3 && l == 2 && n - 2 >= 3 && c->chain_flags && (c->opts.variant & PAYNE_V_HID_CHAIN) &&
-               ((c->opts.b_max + 31) / 32) * ((N.layers[2].n_out + 31) / 32) <= 2 * c->n_cu && n - 3 <= kChainMax &&
-               [&] { for (int q = 2; q <= n - 2; ++q) if (!c->wl_h2[q]) return false; return true; }()) {
-      // layers 2 .. n - 2 in ONE launch: hand-offs inside a 32-candidate row block (payne_dense_chain_kernel; opt-in: a hop costs more
-      // than a launch on this machine, NOTES R6.10)
-      ChainParams cp{};
-      cp.n = n - 3;
-      for (int q = 2; q <= n - 2; ++q) {
-        const payne_layer& Lq = N.layers[q];
-        cp.Wh[q - 2] = c->wl_h2[q]; cp.rs[q - 2] = c->rsl[q]; cp.bias[q - 2] = Lq.b; cp.act[q - 2] = Lq.act;
-        cp.out_scale[q - 2] = (q == n - 2) ? c->act_scale : c->hs[q];
-      }
-      cp.buf[0] = c->hid_h2[0]; cp.buf[1] = c->hid_h2[1]; cp.plane_x = (size_t)c->opts.b_max * 304;
-      cp.first_in = 0;                                      // (layer 1 wrote hid_h2[0]: run_net above, (l - 1) & 1 at l = 1)
-      cp.Yp_last = c->hid_p3; cp.plane_y_last = (size_t)c->opts.b_max * c->ld_hid; cp.ldp_last = c->ld_hid; cp.half_last = use2h ? 1 : 0;
-      cp.flags = c->chain_flags; cp.grid_n = (N.layers[2].n_out + 31) / 32;
-      cp.target0 = c->chain_calls * (unsigned long long)cp.grid_n;
-      cp.B = B; cp.N = N.layers[2].n_out; cp.grid_m = (B + 31) / 32; cp.grid_m_max = (c->opts.b_max + 31) / 32;
-      ++c->chain_calls;
-      PAYNE_LAUNCH_DENSE(payne_dense_chain_kernel, dim3(cp.grid_m_max * cp.grid_n), dim3(256), s, cp);
-      l = n - 2;                                            // (the loop goes on with the output layer)
-    } else {
-      p.X = N.hid[(l - 2) & 1]; p.ldx = N.ld_hid;
-      PrepArgs pa{};
-      if (!last && N.spectral && c->w_hid_pad[l] && N.ld_hid >= HK_PITCH) { p.Wd = c->w_hid_pad[l]; p.ldwd = N.ld_hid; }
-      if (chain && !last && c->wl_h2[l]) {                                   // both operands as planes
-        p.h2_tiles = 1; p.Wh = c->wl_h2[l]; p.plane_wh = (size_t)N.layers[l].n_out * 304; p.rs1 = c->rsl[l];
-        p.Xp = c->hid_h2[(l - 2) & 1]; p.plane_x = (size_t)c->opts.b_max * 304;
-      }
-      if (!last && !hk_lead_fits(p.B, p.N, p.K, 0, p.ldx, p.ldwd, 0, 0))
-        return fail(c, PAYNE_E_UNSUPPORTED, "batch x hidden width beyond what the hidden-layer kernel's packed arguments hold (65 535 tiles of 32 x 32)");
-      if (!last) launch_hidden<false>(p, pa, s);
-      else if (use3) {
-        if (plan.sel) {                                      // rows of the resampled grid; pixels if the batch's records say so
-          p.sel = c->rot_flag; p.sel_seq = R->rot_seq;
-          p.Wp_alt = c->w_out_p3; p.plane_w_alt = (size_t)p.N * c->w_out_kp; p.bias_alt = p.bias; p.bias_shift_alt = p.bias_shift;
-          p.N_alt = p.N; p.ldy_alt = p.ldy;
-          p.N = c->T.n1; p.ldy = c->T.n1;
-          if (use2h) { p.Wp_alt = c->w_out_h2; p.rscale_alt = c->rscale; }
-        }
-        launch_out_planes(c, p, s, plan, N.freq);
-      }
-      else if (plan.form == OutForm::F32Dma) launch_out_dma(c, p, s, plan);
-      else launch_dense<64, 64, 32, false>(p, s);            // nets whose hidden widths differ, the continuum network
     }
+    PrepArgs pa{};
+    pa.T = c->T; pa.T.raw_freq = N.freq ? 1 : 0; pa.instr_factor = instr_factor;      // (the tables are read by the records' writers only)
+    pa.out = records ? c->prep : nullptr;
+    if (plan.sel) { pa.rot_flag = c->rot_flag; pa.rot_seq = rot_seq; }
+    first_launch(c, N, s, p, pa, sed_rides, spec_K, spec, pairs_l1);
+    if (sed_rides) *sed = false;
+    if (R) { R->prep = pa.out; R->spec = spec_K != 0; }
+    if (chained) chain_launch(c, N, plan, B, s);
+    else
+      for (int l = 2; l <= n - 2; ++l) {
+        p = layer_params(c, N, l, B, theta);
+        hidden_params(c, N, plan, l, p);
+        hidden_launch(c, N, l, s, p);
+      }
   }
+  out_launch(c, N, plan, s, rot_seq, out);
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) return fail(c, PAYNE_E_HIP, std::string("dense launch: ") + hipGetErrorString(e));
   return PAYNE_OK;
@@ -1229,7 +1220,7 @@ static int run_ann(payne_ctx* c, const double* theta, int B, double instr_factor
                    bool* sed = nullptr, bool pixels = false, const SpecReq& spec = SpecReq{}) {
   NetRef N = spectral_net(c);
   // (the continuum multiplies pixel by pixel; the form: the launch that reads the restated weights is the one that runs)
-  N.freq = c->freq_ok && !pixels && !(c->has_cont && with_cont) && out_form(c, N) >= OutForm::Bf16x3;
+  N.freq = c->freq_ok && !pixels && !(c->has_cont && with_cont) && out_form(out_facts(c, N)) >= OutForm::Bf16x3;
   // rows of a resampled grid need this batch's records (their writers report a candidate that does not rotate) and a first layer
   // fused into the hidden-layer launch (>= 3 layers), and the plain post kernel behind them
   if (N.freq && c->freq_rs && !(c->prep && c->obs_bound && !(c->opts.variant & PAYNE_V_NO_PREP) && c->n_layers >= 3 && !c->has_lsf)) N.freq = false;
@@ -1237,10 +1228,10 @@ static int run_ann(payne_ctx* c, const double* theta, int B, double instr_factor
   *R = BatchRows{};
   R->rows = c->raw; R->ld = N.sel ? c->T.n1 : c->T.npix; R->freq = N.freq; R->sel = N.sel;
   if (N.sel) R->rot_seq = ++c->rot_seq;
-  int rc = run_net(c, N, plan_out(c, N, B), theta, B, instr_factor, s, R, sed, spec);
+  int rc = run_net(c, N, plan_out(out_facts(c, N), B), theta, B, instr_factor, s, R, sed, spec);
   if (rc || !c->has_cont || !with_cont) return rc;
   const NetRef C = continuum_net(c);
-  if ((rc = run_net(c, C, plan_out(c, C, B), theta, B, instr_factor, s))) return rc;
+  if ((rc = run_net(c, C, plan_out(out_facts(c, C), B), theta, B, instr_factor, s))) return rc;
   int npc2 = 1;
   while (npc2 < c->cn_npix) npc2 <<= 1;
   if (npc2 > 4096 || (c->opts.variant & PAYNE_V_SELECT_MEDIAN)) npc2 = 0;     // median by selection instead of an LDS sort
@@ -1387,7 +1378,7 @@ extern "C" int payne_predict_batch(payne_ctx* c, const double* theta, int B, int
     if (!c->has_cont) return fail(c, PAYNE_E_INVALID, "no continuum network bound");
     if (ld_out < c->cn_npix) return fail(c, PAYNE_E_INVALID, "ld_out too small");
     const NetRef C = continuum_net(c);
-    if ((rc = run_net(c, C, plan_out(c, C, B), theta, B, 1.0, s))) return rc;
+    if ((rc = run_net(c, C, plan_out(out_facts(c, C), B), theta, B, 1.0, s))) return rc;
     hipError_t he = hipMemcpy2DAsync(out, (size_t)ld_out * 4, c->cont_raw, (size_t)c->cn_npix * 4, (size_t)c->cn_npix * 4, B,
                                      hipMemcpyDeviceToDevice, s);
     if (he != hipSuccess) return fail(c, PAYNE_E_HIP, std::string("hipMemcpy2DAsync: ") + hipGetErrorString(he));

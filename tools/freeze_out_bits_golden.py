@@ -15,7 +15,7 @@ synth.make_yst_net's and np.random.default_rng's seeds alone.  The shapes are th
                        checked stores); npix = 200: the second 128-column tile is ragged (column clamp, col < N)
     H = 300 / 100      320 padded columns, the k-steps counted at compile time, the last stage cut at 300 / 128 padded columns,
                        k-steps counted at run time, the tail cut at the seventh 16-deep step
-    variants           which of the kernels a shape gets (plan_out, payne_hip.hip); V_OUT_F32 (and V_OUT_BK64) for the fp32 ring
+    variants           which of the kernels a shape gets (plan_out, csrc/out_plan.hpp); V_OUT_F32 (and V_OUT_BK64) for the fp32 ring
     npix = 1024 + obs  rows in the frequency domain (the restated weights, no bias shift)
     512 x 4224         8 x 33 = 264 tiles of 64 x 128: more than the 256 compute units, and 4224 is no multiple of 256 -- the
                        kernels for a compute unit that works through several tiles
