@@ -494,6 +494,68 @@ int payne_specjac_eval(payne_specjac* h, const double* labels_dev, int ld_x, int
 void payne_specjac_destroy(payne_specjac* h);
 int payne_fisher_batch(int device, const float* rows_dev, int ld, int K, int n, int B, const double* w_dev, double* F_dev, void* stream);
 
+/* ---- batched Levenberg-Marquardt: least-squares fits of K parameters for many stars at once ----
+ * payne_lmfit_*: the state of B independent fits and the step that advances all of them, one launch an iteration.  The caller
+ * evaluates the model and its derivatives at the handle's trial points (payne_specjac_eval + payne_smooth_batch, say) and hands the
+ * rows to payne_lmfit_update; nothing else is needed between two iterations and nothing waits.  Per star, with R the [K+1][n] matrix
+ * of the K derivative rows and the residual row flux - model, both in fp64, G = R diag(w) R^T holds the normal matrix A = J^T W J
+ * (G[i][j], i, j < K), the gradient g = J^T W r (G[k][K]) and chi^2 (G[K][K]).  G is one accumulator tile of the fp64 matrix
+ * instruction, four pixels an instruction; each of the workgroup's four waves sums a contiguous stripe of pixels and the four
+ * partial tiles are added in wave order: no atomics, the same inputs give the same bits, and a star's bits do not depend on the
+ * batch it is in.  A pixel with w == 0 contributes nothing whatever the rows or the flux hold there (getspec is NaN outside the
+ * model's range); any other NaN reaches chi^2.  Then one thread per star (csrc/lmfit_core.hpp, fp64):
+ *   decide   the trial is accepted at the star's first evaluation, or when its chi^2 is finite and <= the best so far.  Accepted:
+ *            x_best = x_trial, G becomes the stored matrix, lambda = max(lambda / down, lambda_min).  Rejected: the stored matrix
+ *            stays, lambda = min(lambda * up, lambda_max).  chi^2 not finite at the first evaluation: PAYNE_LMFIT_NAN.
+ *   solve    S = diag(A_kk^-1/2); (S A S + lambda I) u = S g by Cholesky; delta = S u.  An A_kk that is not positive and finite, a
+ *            pivot that is not positive or a delta that is not finite: PAYNE_LMFIT_SINGULAR.
+ *   trial    x_trial = clip(x_best + delta, lo, hi); bit k of at_bound says that parameter k was clipped.
+ *   stop     with the step actually taken, dx = x_trial - x_best: after an acceptance with max_k |dx_k| sqrt(A_kk) < xtol
+ *            PAYNE_LMFIT_CONVERGED; after a rejection of a trial made with lambda == lambda_max PAYNE_LMFIT_STALLED; after
+ *            `maxiter` evaluations PAYNE_LMFIT_MAXITER (in this order).
+ * A star that is no longer PAYNE_LMFIT_RUNNING is skipped by every later update and its x_trial equals its x_best.
+ * payne_lmfit_create: K parameters, room for max_stars stars.  opts NULL: the defaults (lambda0 1e-3, down 10, up 10, lambda_min
+ * 1e-12, lambda_max 1e8, xtol 1e-3, maxiter 50).  lambda0 == 0 with lambda_min == 0 is plain Gauss-Newton.
+ *   PAYNE_E_INVALID      null out, K < 1, max_stars < 1, an option that is not finite, lambda0 < 0, lambda_min < 0, lambda_max <
+ *                        lambda_min, lambda0 outside [lambda_min, lambda_max], down < 1, up < 1, xtol < 0, maxiter < 1
+ *   PAYNE_E_UNSUPPORTED  K > 15
+ * payne_lmfit_begin: x0_dev DEVICE fp64 [B][K]; lo, hi HOST fp64 [K], the box.  Every star becomes RUNNING with lambda0, no
+ * evaluation behind it and x_trial = clip(x0) (at_bound says where).  B stays the handle's batch until the next begin.
+ *   PAYNE_E_INVALID      null handle / lo / hi, B outside 0 .. max_stars, null x0_dev with B > 0, lo >= hi or not finite
+ * payne_lmfit_trial: the DEVICE pointer of x_trial, fp64 [B][K] (NULL for a null handle); it stays valid for the handle's life.
+ * payne_lmfit_update: rows_dev DEVICE fp32 [B][1 + K][ld], row 0 the model at the star's x_trial and row 1 + k its derivative with
+ * respect to parameter k; flux_dev DEVICE fp32 [B][ld_f]; w_dev DEVICE fp64 [B][ld_f], the star's own 1 / sigma^2; n pixels.
+ * Rows and flux are read 16 bytes a lane where ld and ld_f are multiples of four and the pointers 16-byte aligned, element by
+ * element otherwise (the same bits).
+ *   PAYNE_E_INVALID      null handle, n < 1, ld < n, ld_f < n, null rows_dev / flux_dev / w_dev with B > 0
+ * payne_lmfit_result: DEVICE pointers, any may be NULL: x_best fp64 [B][K], chisq fp64 [B] (of x_best), A fp64 [B][K][K] and g fp64
+ * [B][K] (at x_best), lambda fp64 [B], status int [B], niter int [B] (evaluations), at_bound unsigned [B].  Copies on `stream`.
+ *   PAYNE_E_INVALID      null handle
+ * B == 0 succeeds and does nothing; every call is enqueued on `stream` and does not wait.  payne_lmfit_destroy: NULL is allowed. */
+#define PAYNE_LMFIT_RUNNING 0
+#define PAYNE_LMFIT_CONVERGED 1
+#define PAYNE_LMFIT_STALLED 2
+#define PAYNE_LMFIT_MAXITER 3
+#define PAYNE_LMFIT_SINGULAR 4
+#define PAYNE_LMFIT_NAN 5
+#define PAYNE_LMFIT_MAX_K 15
+
+typedef struct payne_lmfit_opts {
+  double lambda0, down, up, lambda_min, lambda_max, xtol;
+  int maxiter;
+} payne_lmfit_opts;
+
+typedef struct payne_lmfit payne_lmfit;
+
+int payne_lmfit_create(int device, int K, int max_stars, const payne_lmfit_opts* opts, payne_lmfit** out);
+int payne_lmfit_begin(payne_lmfit* h, const double* x0_dev, const double* lo, const double* hi, int B, void* stream);
+double* payne_lmfit_trial(payne_lmfit* h);
+int payne_lmfit_update(payne_lmfit* h, const float* rows_dev, int ld, const float* flux_dev, const double* w_dev, int ld_f, int n,
+                       void* stream);
+int payne_lmfit_result(payne_lmfit* h, double* x_best, double* chisq, double* A, double* g, double* lambda, int* status, int* niter,
+                       unsigned* at_bound, void* stream);
+void payne_lmfit_destroy(payne_lmfit* h);
+
 /* Magnitudes for B parameter vectors: FastPayneSEDPredict.sed
  * (Payne/predict/predictsed.py:75-103).  pars: device fp64 [B][9] =
  * logt, logg, feh, afe, av, rv, logl, dist, logA  (NaN = kwarg absent; the

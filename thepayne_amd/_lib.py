@@ -40,7 +40,8 @@ SYMBOLS = ["payne_version", "payne_ctx_create", "payne_ctx_set_obs", "payne_ctx_
            "payne_lnmlp_train_destroy", "payne_lnmlp_dropout_mask",
            "payne_specmlp_train_create", "payne_specmlp_train_step", "payne_specmlp_train_loss", "payne_specmlp_train_predict",
            "payne_specmlp_train_set_lr", "payne_specmlp_train_get", "payne_specmlp_train_steps", "payne_specmlp_train_destroy",
-           "payne_specjac_create", "payne_specjac_eval", "payne_specjac_destroy", "payne_fisher_batch"]
+           "payne_specjac_create", "payne_specjac_eval", "payne_specjac_destroy", "payne_fisher_batch",
+           "payne_lmfit_create", "payne_lmfit_begin", "payne_lmfit_trial", "payne_lmfit_update", "payne_lmfit_result", "payne_lmfit_destroy"]
 
 PAYNE_MAX_DIM, PAYNE_MAX_FIXED = 24, 16
 PRIOR_UNIFORM, PRIOR_GAUSSIAN, PRIOR_TGAUSSIAN, PRIOR_EXP, PRIOR_TEXP, PRIOR_LOGUNIFORM, PRIOR_TABLE = range(7)
@@ -102,7 +103,19 @@ class SpecmlpTrainOpts(C.Structure):
     _fields_ = [("lr", C.c_double), ("beta1", C.c_double), ("beta2", C.c_double), ("eps", C.c_double), ("max_rows", C.c_int)]
 
 
+class LmfitOpts(C.Structure):
+    """payne_lmfit_opts; the defaults are the header's."""
+    _fields_ = [("lambda0", C.c_double), ("down", C.c_double), ("up", C.c_double), ("lambda_min", C.c_double), ("lambda_max", C.c_double),
+                ("xtol", C.c_double), ("maxiter", C.c_int)]
+
+    def __init__(self, lambda0=1e-3, down=10.0, up=10.0, lambda_min=1e-12, lambda_max=1e8, xtol=1e-3, maxiter=50):
+        super(LmfitOpts, self).__init__(float(lambda0), float(down), float(up), float(lambda_min), float(lambda_max), float(xtol), int(maxiter))
+
+
 JAC_ENCODED = 1
+LMFIT_RUNNING, LMFIT_CONVERGED, LMFIT_STALLED, LMFIT_MAXITER, LMFIT_SINGULAR, LMFIT_NAN = range(6)
+LMFIT_STATUS_NAMES = ("RUNNING", "CONVERGED", "STALLED", "MAXITER", "SINGULAR", "NAN")
+LMFIT_MAX_K = 15
 SPECJAC_MAX_LABELS, FISHER_MAX_ROWS = 8, 16
 
 
@@ -244,6 +257,18 @@ def load(path=None):
     lib.payne_specjac_destroy.restype = None
     lib.payne_fisher_batch.argtypes = [C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
     lib.payne_fisher_batch.restype = C.c_int
+    lib.payne_lmfit_create.argtypes = [C.c_int, C.c_int, C.c_int, C.POINTER(LmfitOpts), C.POINTER(ctxp)]
+    lib.payne_lmfit_create.restype = C.c_int
+    lib.payne_lmfit_begin.argtypes = [ctxp, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
+    lib.payne_lmfit_begin.restype = C.c_int
+    lib.payne_lmfit_trial.argtypes = [ctxp]
+    lib.payne_lmfit_trial.restype = C.c_void_p
+    lib.payne_lmfit_update.argtypes = [ctxp, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p]
+    lib.payne_lmfit_update.restype = C.c_int
+    lib.payne_lmfit_result.argtypes = [ctxp] + [C.c_void_p] * 9
+    lib.payne_lmfit_result.restype = C.c_int
+    lib.payne_lmfit_destroy.argtypes = [ctxp]
+    lib.payne_lmfit_destroy.restype = None
     lib.payne_ctx_destroy.argtypes = [ctxp]
     lib.payne_ctx_destroy.restype = None
     lib.payne_last_error.argtypes = [ctxp]

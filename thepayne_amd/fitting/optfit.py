@@ -1,0 +1,295 @@
+"""Least-squares point estimates of the stellar labels for many spectra on one wavelength grid: batched Levenberg-Marquardt on
+the GPU.
+
+``OptFit.fit`` minimises, per star, chi^2 = sum_p w_p (flux_p - model_p(x))^2 over the labels of the spectral network (and, with
+``fit_vrad``, the radial velocity) inside a box, at the star's own fixed Vrot, Inst_R (and Vrad).  One iteration is three enqueued
+steps and nothing in between: the network and its Jacobian at every star's trial point (payne_specjac_eval), the engine's
+broadening and resampling applied to those rows (payne_smooth_batch), and one launch that forms every star's normal equations on
+the fp64 matrix instruction and takes its damped step (payne_lmfit_update: include/payne_hip.h states the rules).  The host looks
+at the stars' status only every ``check_every`` iterations.
+
+The model whose chi^2 is minimised is payne_specjac_eval's y pushed through payne_smooth_batch, so that the model and its
+Jacobian come from the same arithmetic.  This is NOT the likelihood's forward pass (whose dense layers split their operands in
+fp16 parts): the two agree within the bound tests/test_specjac_gpu.py holds them to, and a fit's chi^2 is not lnlike's to the bit.
+
+What is fitted: Teff, log(g), [Fe/H], [alpha/Fe] and, for a five-label network, Vmic; Vrad with ``fit_vrad`` (its derivative is a
+central difference of the broadened model at Vrad +- ``vrad_step``).  Vrot and Inst_R are fixed at the values ``start`` gives, and
+Vmic too for a four-label network.  ``fisher`` is the normal matrix J^T W J at the solution and ``err`` its Cramer-Rao bounds
+(``forecast.crlb_from_fisher``): conditional on the fixed parameters, as ``Forecast``'s are.  A continuum network and an LSF vector
+are not supported (``PayneSpecPredict.getgrad`` explains why).
+"""
+import ctypes as C
+
+import numpy as np
+
+from .. import _lib
+from ..engine import THETA_SPEC_COLS
+from ..predict._spec import PayneSpecPredict, smooth_rows
+from .forecast import crlb_from_fisher, weights_from_errors
+
+__all__ = ["OptFit", "check_fit_args", "LM_DEFAULTS", "VRAD_BOUND"]
+
+LM_DEFAULTS = dict(lambda0=1e-3, down=10.0, up=10.0, lambda_min=1e-12, lambda_max=1e8, xtol=1e-3, maxiter=50)
+VRAD_BOUND = 500.0                                   # km/s: the default box of a fitted Vrad
+
+
+def fitted_columns(n_labels, fit_vrad):
+    """The columns of getspec's eight that are fitted: the network's labels, then Vrad."""
+    return [0, 1, 2, 3] + ([6] if n_labels == 5 else []) + ([4] if fit_vrad else [])
+
+
+def check_fit_args(flux, eflux, start, nobs, n_labels, xmin, xmax, fit_vrad=False, bounds=None, vrad_step=0.25, check_every=4, **opts):
+    """What ``OptFit.fit`` checks before anything reaches the device.  Returns (flux [N, nobs] fp32, eflux [N, nobs] fp64, start
+    [N, 8] fp64, lo [K], hi [K], opts dict).  ``bounds``: {column name of THETA_SPEC_COLS: (lo, hi)} for some of the fitted columns,
+    or an array [K, 2] for all of them."""
+    flux = np.atleast_2d(np.asarray(flux, dtype=np.float32))
+    eflux = np.atleast_2d(np.asarray(eflux, dtype=np.float64))
+    start = np.atleast_2d(np.asarray(start, dtype=np.float64))
+    if flux.ndim != 2 or flux.shape[1] != nobs:
+        raise ValueError("flux must be [N, %d], got %s" % (nobs, flux.shape))
+    if eflux.shape != flux.shape:
+        raise ValueError("eflux %s and flux %s differ in shape" % (eflux.shape, flux.shape))
+    if start.ndim != 2 or start.shape != (flux.shape[0], 8):
+        raise ValueError("start must be [%d, 8] (getspec's columns), got %s" % (flux.shape[0], start.shape))
+    cols = fitted_columns(n_labels, fit_vrad)
+    K = len(cols)
+    if not np.all(np.isfinite(start[:, cols])):
+        raise ValueError("start is not finite in a fitted column")
+    if not np.all(np.isfinite(start[:, 5])):
+        raise ValueError("start's Vrot is not finite")
+    if not fit_vrad and not np.all(np.isfinite(start[:, 4])):
+        raise ValueError("start's Vrad is not finite")
+    lo = np.concatenate([np.asarray(xmin, dtype=np.float64)[:n_labels], [-VRAD_BOUND] if fit_vrad else []])
+    hi = np.concatenate([np.asarray(xmax, dtype=np.float64)[:n_labels], [VRAD_BOUND] if fit_vrad else []])
+    if bounds is not None:
+        if isinstance(bounds, dict):
+            names = [THETA_SPEC_COLS[c] for c in cols]
+            for name, (a, b) in bounds.items():
+                if name not in names:
+                    raise ValueError("bounds: %r is not a fitted column (%s)" % (name, ", ".join(names)))
+                lo[names.index(name)], hi[names.index(name)] = float(a), float(b)
+        else:
+            bd = np.asarray(bounds, dtype=np.float64)
+            if bd.shape != (K, 2):
+                raise ValueError("bounds must be [%d, 2] or a dict, got %s" % (K, bd.shape))
+            lo, hi = bd[:, 0].copy(), bd[:, 1].copy()
+    if not (np.all(np.isfinite(lo)) and np.all(np.isfinite(hi)) and np.all(lo < hi)):
+        raise ValueError("bounds: lo < hi, both finite, for every fitted column")
+    if not (np.isfinite(vrad_step) and vrad_step > 0.0):
+        raise ValueError("vrad_step must be positive")
+    if int(check_every) < 1:
+        raise ValueError("check_every must be at least 1")
+    unknown = sorted(set(opts) - set(LM_DEFAULTS))
+    if unknown:
+        raise TypeError("unknown options %s (have %s)" % (unknown, sorted(LM_DEFAULTS)))
+    o = dict(LM_DEFAULTS, **opts)
+    fin = all(np.isfinite(float(o[k])) for k in LM_DEFAULTS)
+    if not fin or o["lambda_min"] < 0 or o["lambda_max"] < o["lambda_min"] or not (o["lambda_min"] <= o["lambda0"] <= o["lambda_max"]) \
+            or o["down"] < 1 or o["up"] < 1 or o["xtol"] < 0 or int(o["maxiter"]) < 1:
+        raise ValueError("options out of range: %s" % (o,))
+    return flux, eflux, start, lo, hi, o
+
+
+class _DeviceArray(object):
+    """A device pointer the library owns, as torch reads it (``torch.as_tensor``)."""
+
+    def __init__(self, ptr, shape, typestr):
+        self.__cuda_array_interface__ = {"shape": tuple(shape), "typestr": typestr, "data": (int(ptr), False), "version": 2, "strides": None}
+
+
+class LMHandle(object):
+    """Owner of one ``payne_lmfit`` handle: K parameters, room for ``max_stars`` stars."""
+
+    def __init__(self, K, max_stars, device, **opts):
+        import torch
+        self.torch, self.lib = torch, _lib.load()
+        self.device, self.K, self.max_stars = device, int(K), int(max_stars)
+        self.opts = _lib.LmfitOpts(**opts)
+        self._h = C.c_void_p()
+        rc = self.lib.payne_lmfit_create(self.device.index, self.K, self.max_stars, C.byref(self.opts), C.byref(self._h))
+        if rc != 0:
+            raise RuntimeError("payne_lmfit_create failed (%d): %s" % (rc, self.lib.payne_last_error(None).decode()))
+        self.B = 0
+        with torch.cuda.device(self.device):
+            self._trial = torch.as_tensor(_DeviceArray(self.lib.payne_lmfit_trial(self._h), (self.max_stars, self.K), "<f8"), device=self.device)
+
+    def _stream(self):
+        return C.c_void_p(self.torch.cuda.current_stream(self.device).cuda_stream)
+
+    def begin(self, x0, lo, hi):
+        """x0 [B, K] (a host array or a device tensor), the box lo, hi [K]."""
+        torch = self.torch
+        x = x0 if isinstance(x0, torch.Tensor) else torch.as_tensor(np.ascontiguousarray(x0, dtype=np.float64))
+        x = x.to(device=self.device, dtype=torch.float64).contiguous()
+        if x.dim() != 2 or x.shape[1] != self.K:
+            raise ValueError("x0 must be [B, %d], got %s" % (self.K, tuple(x.shape)))
+        lo, hi = np.ascontiguousarray(lo, dtype=np.float64), np.ascontiguousarray(hi, dtype=np.float64)
+        if lo.shape != (self.K,) or hi.shape != (self.K,):
+            raise ValueError("lo and hi must be [%d]" % self.K)
+        rc = self.lib.payne_lmfit_begin(self._h, x.data_ptr(), lo.ctypes.data, hi.ctypes.data, x.shape[0], self._stream())
+        if rc != 0:
+            raise RuntimeError("payne_lmfit_begin failed (%d)" % rc)
+        self.B = x.shape[0]
+
+    def trial(self):
+        """x_trial [B, K]: a view of the handle's own memory, valid in stream order."""
+        return self._trial[:self.B]
+
+    def update(self, rows, flux, w):
+        """rows fp32 [B, 1 + K, n] (the model, then its derivatives), flux fp32 [B, n], w fp64 [B, n]: device tensors."""
+        B, n = self.B, rows.shape[-1]
+        if tuple(rows.shape) != (B, 1 + self.K, n) or tuple(flux.shape) != (B, n) or tuple(w.shape) != (B, n):
+            raise ValueError("rows [%d, %d, n], flux and w [%d, n]; got %s, %s, %s" % (B, 1 + self.K, B, tuple(rows.shape), tuple(flux.shape), tuple(w.shape)))
+        torch = self.torch
+        if rows.dtype != torch.float32 or flux.dtype != torch.float32 or w.dtype != torch.float64 or not (rows.is_contiguous() and flux.is_contiguous() and w.is_contiguous()):
+            raise ValueError("rows and flux contiguous fp32, w contiguous fp64")
+        rc = self.lib.payne_lmfit_update(self._h, rows.data_ptr(), n, flux.data_ptr(), w.data_ptr(), n, n, self._stream())
+        if rc != 0:
+            raise RuntimeError("payne_lmfit_update failed (%d)" % rc)
+
+    def status(self):
+        torch = self.torch
+        s = torch.empty(self.B, dtype=torch.int32, device=self.device)
+        rc = self.lib.payne_lmfit_result(self._h, None, None, None, None, None, s.data_ptr(), None, None, self._stream())
+        if rc != 0:
+            raise RuntimeError("payne_lmfit_result failed (%d)" % rc)
+        return s
+
+    def result(self):
+        """dict of device tensors: x_best, chisq, A, g, lambda, status, niter, at_bound."""
+        torch, B, K = self.torch, self.B, self.K
+        f64 = dict(dtype=torch.float64, device=self.device)
+        i32 = dict(dtype=torch.int32, device=self.device)
+        out = dict(x_best=torch.empty((B, K), **f64), chisq=torch.empty(B, **f64), A=torch.empty((B, K, K), **f64), g=torch.empty((B, K), **f64),
+                   **{"lambda": torch.empty(B, **f64)}, status=torch.empty(B, **i32), niter=torch.empty(B, **i32), at_bound=torch.empty(B, **i32))
+        order = ("x_best", "chisq", "A", "g", "lambda", "status", "niter", "at_bound")
+        rc = self.lib.payne_lmfit_result(self._h, *([out[k].data_ptr() if B else None for k in order] + [self._stream()]))
+        if rc != 0:
+            raise RuntimeError("payne_lmfit_result failed (%d)" % rc)
+        return out
+
+    def close(self):
+        if getattr(self, "_h", None) is not None and self._h.value:
+            self._trial = None
+            self.lib.payne_lmfit_destroy(self._h)                   # (waits for the device)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class OptFit(object):
+    """OptFit(specANNpath, NNtype, obs_wave): least-squares fits of the labels on the observed grid ``obs_wave``."""
+
+    def __init__(self, specANNpath, NNtype, obs_wave, device=None, b_max=256, Cnnpath=None):
+        if Cnnpath is not None:
+            raise NotImplementedError("OptFit with a continuum network (Cnnpath): the model is a product of two networks")
+        self.obs_wave = np.ascontiguousarray(obs_wave, dtype=np.float64)
+        if self.obs_wave.ndim != 1 or len(self.obs_wave) < 1:
+            raise ValueError("obs_wave must be a vector")
+        self.predictor = PayneSpecPredict(specANNpath, NNtype=NNtype, device=device, b_max=b_max)
+        self.n_labels = self.predictor.anns.n_labels
+        self.timing = None
+
+    def labels(self, fit_vrad=False):
+        return [THETA_SPEC_COLS[c] for c in fitted_columns(self.n_labels, fit_vrad)]
+
+    def fit(self, flux, eflux, start, fit_vrad=False, bounds=None, vrad_step=0.25, check_every=4, lsf=None, timing=False, **opts):
+        """flux, eflux [N, nobs] on ``obs_wave`` (eflux zero or not finite: the pixel does not count), start [N, 8] = Teff, logg,
+        feh, afe, vrad, vrot, vmic, inst_R (getspec's columns, as ``Forecast.jacobian`` takes them) -> dict: ``pars`` [N, 8],
+        ``chisq``, ``npix`` (pixels with w != 0), ``fisher`` [N, K, K], ``err`` [N, K], ``status`` (``_lib.LMFIT_*``), ``niter``
+        (evaluations of the model), ``at_bound`` (bit k: fitted column k sits on its bound), ``labels`` (the K fitted columns).
+        ``opts``: lambda0, down, up, lambda_min, lambda_max, xtol, maxiter (payne_lmfit_opts).  ``timing``: event pairs around the
+        three steps of every iteration, summed into ``self.timing`` (ms; for tools/optfit_bench.py)."""
+        if lsf is not None:
+            raise NotImplementedError("OptFit with an LSF vector: the rows are not pushed through it (PayneSpecPredict.getgrad)")
+        P = self.predictor
+        anns, eng, D = P.anns, P.anns.engine, self.n_labels
+        flux, eflux, start, lo, hi, o = check_fit_args(flux, eflux, start, len(self.obs_wave), D, anns.xmin, anns.xmax, fit_vrad=fit_vrad,
+                                                       bounds=bounds, vrad_step=vrad_step, check_every=check_every, **opts)
+        torch = eng.torch
+        N, nobs = flux.shape
+        cols = fitted_columns(D, fit_vrad)
+        K = len(cols)
+        w = weights_from_errors(eflux)
+        P._bind(self.obs_wave)
+        step = max(1, eng.b_max // (1 + K + 2 * int(bool(fit_vrad))))
+        handle = LMHandle(K, min(step, N), eng.device, **o)
+        out = dict(pars=start.copy(), chisq=np.empty(N), npix=(w != 0.0).sum(axis=1), fisher=np.empty((N, K, K)), status=np.empty(N, dtype=np.int32),
+                   niter=np.empty(N, dtype=np.int32), at_bound=np.empty(N, dtype=np.uint32), labels=self.labels(fit_vrad))
+        self.timing = dict(network=0.0, broadening=0.0, update=0.0, iterations=0) if timing else None
+        try:
+            for s in range(0, N, step):
+                e = min(N, s + step)
+                res = self._fit_block(handle, flux[s:e], w[s:e], start[s:e], cols, lo, hi, bool(fit_vrad), float(vrad_step), int(check_every),
+                                      int(o["maxiter"]))
+                out["pars"][s:e][:, cols] = res["x_best"].cpu().numpy()
+                out["chisq"][s:e] = res["chisq"].cpu().numpy()
+                out["fisher"][s:e] = res["A"].cpu().numpy()
+                out["status"][s:e] = res["status"].cpu().numpy()
+                out["niter"][s:e] = res["niter"].cpu().numpy()
+                out["at_bound"][s:e] = res["at_bound"].cpu().numpy().astype(np.uint32)
+        finally:
+            handle.close()
+        out["err"] = crlb_from_fisher(out["fisher"])
+        return out
+
+    def _fit_block(self, handle, flux, w, start, cols, lo, hi, fit_vrad, vrad_step, check_every, maxiter):
+        P = self.predictor
+        eng, D, jac_net = P.anns.engine, self.n_labels, P._jacobian()
+        torch = eng.torch
+        nb, nobs, K = flux.shape[0], flux.shape[1], len(cols)
+        dev = eng.device
+        flux_d = torch.as_tensor(np.ascontiguousarray(flux)).to(dev)
+        w_d = torch.as_tensor(np.ascontiguousarray(w)).to(dev)
+        handle.begin(start[:, cols], lo, hi)
+        xt = handle.trial()
+        # the theta blocks, uploaded once: the model's [nb], the derivative rows' [nb * D], and Vrad +- step's [2 nb]
+        th = np.full((nb, eng.ncols), np.nan)
+        th[:, :8] = start
+        th_y = torch.as_tensor(th).to(dev)
+        th_j = th_y.repeat_interleave(D, dim=0)
+        th_pm = th_y.repeat(2, 1) if fit_vrad else None
+        rows = torch.empty((nb, 1 + K, nobs), dtype=torch.float32, device=dev)
+        tm = self.timing
+        marks = []
+
+        def mark():
+            if tm is not None:
+                ev = torch.cuda.Event(enable_timing=True)
+                ev.record(torch.cuda.current_stream(dev))
+                marks.append(ev)
+        it = 0
+        while it < maxiter:
+            it += 1
+            mark()
+            labels = xt[:, :D] if fit_vrad else xt
+            y, jac = jac_net.eval(labels)
+            mark()
+            if fit_vrad:
+                v = xt[:, D]
+                th_y[:, 4] = v
+                th_j[:, 4] = v.repeat_interleave(D)
+                th_pm[:nb, 4] = v + vrad_step
+                th_pm[nb:, 4] = v - vrad_step
+                pm = eng.smooth_batch(y.repeat(2, 1), th_pm, stage=2)
+                rows[:, K] = (pm[:nb] - pm[nb:]) / (2.0 * vrad_step)
+            rows[:, 0] = eng.smooth_batch(y, th_y, stage=2)
+            rows[:, 1:1 + D] = smooth_rows(eng, jac.reshape(nb * D, -1), th_j, 2).reshape(nb, D, nobs)
+            mark()
+            handle.update(rows, flux_d, w_d)
+            mark()
+            if it % check_every == 0 and not bool((handle.status() == _lib.LMFIT_RUNNING).any().item()):
+                break
+        res = handle.result()
+        if tm is not None:
+            torch.cuda.synchronize(dev)
+            for i in range(0, len(marks), 4):
+                tm["network"] += marks[i].elapsed_time(marks[i + 1])
+                tm["broadening"] += marks[i + 1].elapsed_time(marks[i + 2])
+                tm["update"] += marks[i + 2].elapsed_time(marks[i + 3])
+            tm["iterations"] += it
+        return res
