@@ -556,6 +556,44 @@ int payne_lmfit_result(payne_lmfit* h, double* x_best, double* chisq, double* A,
                        unsigned* at_bound, void* stream);
 void payne_lmfit_destroy(payne_lmfit* h);
 
+/* ---- template-bank chi^2 search: every star against every template, the best few per star ----
+ * payne_tmatch_*: chi^2[s][t] = sum_p w[s][p] (flux[s][p] - m[t][p])^2 for N stars and M templates on one pixel grid, expanded into
+ * one N x M matrix product over 2 n terms on the fp64 matrix instruction, and per star the topk smallest (starting points for
+ * payne_lmfit_*).  csrc/tmatch_core.hpp holds the arithmetic and its order; in short:
+ *   value    chi^2 = c0[s] + sum_p (a1 (-2 m) + a2 m^2) with a1 = w f (rounded once), a2 = w, c0 = sum_p a1 f, everything fp64; m is
+ *            widened first, so -2 m and m^2 are exact.  The error against the direct sum is at most (2 n + 4) 2^-53 (sum w f^2 +
+ *            2 sum |w f m| + sum w m^2): the expansion cancels, but in fp64.
+ *   pixels   a pixel with w == 0, or beyond n, contributes nothing whatever the flux or the templates hold there (NaN, 1e30): both
+ *            operands are replaced by zero by a select.  A flux, weight or template value that is not finite at a pixel with w != 0
+ *            makes that chi^2 NaN (for a template value: of that (star, template) pair only).  ld - n padding is never read.
+ *   lists    per star the topk smallest chi^2 ascending, equal values in ascending template index; NaN never enters; a slot that
+ *            cannot be filled (topk > M, or fewer templates that are not NaN) has idx = -1 and chisq = +inf.
+ *   order    the grid is (tiles of 64 stars) x (chunks of payne_tmatch_chunk() templates); a workgroup leaves its chunk's list in the
+ *            handle's workspace and a second small launch merges a star's chunks in chunk order.  No atomics: the same inputs give
+ *            the same bytes, with or without all_dev, and a star's bytes do not depend on the other stars of the call.
+ * payne_tmatch_create: room for max_stars stars and max_templates templates a call; the handle owns only the workspace
+ * (ceil(max_templates / chunk) * max_stars * 8 entries of 12 bytes).
+ *   PAYNE_E_INVALID      null out, max_stars < 1, max_templates < 1
+ * payne_tmatch_match: templates_dev DEVICE fp32 [M][ld_t]; flux_dev DEVICE fp32 [N][ld_f]; w_dev DEVICE fp64 [N][ld_f], each star's
+ * own 1 / sigma^2; n pixels; idx_dev DEVICE int32 [N][topk], chisq_dev DEVICE fp64 [N][topk]; all_dev DEVICE fp64 [N][ld_a], every
+ * chi^2, or NULL.  Checked before anything reaches the device:
+ *   PAYNE_E_INVALID      null handle, topk outside 1 .. PAYNE_TMATCH_MAX_TOPK, N outside 0 .. max_stars, M outside 0 .. max_templates,
+ *                        n < 1, ld_t < n, ld_f < n; with N > 0 and M > 0: a null templates_dev / flux_dev / w_dev / idx_dev /
+ *                        chisq_dev, ld_a < M with all_dev
+ *   PAYNE_E_UNSUPPORTED  more than 65535 chunks of templates (M > 65535 * payne_tmatch_chunk())
+ * N == 0 or M == 0 succeeds and does nothing; the call is enqueued on `stream` and does not wait; payne_last_error(NULL) has the
+ * message of a failure.  Two calls on one handle share its workspace, so they belong on one stream.  payne_tmatch_destroy: NULL is
+ * allowed. */
+#define PAYNE_TMATCH_MAX_TOPK 8
+
+typedef struct payne_tmatch payne_tmatch;
+
+int payne_tmatch_create(int device, int max_stars, int max_templates, payne_tmatch** out);
+int payne_tmatch_match(payne_tmatch* h, const float* templates_dev, int ld_t, int M, const float* flux_dev, const double* w_dev, int ld_f,
+                       int N, int n, int topk, int* idx_dev, double* chisq_dev, double* all_dev, long long ld_a, void* stream);
+int payne_tmatch_chunk(void);
+void payne_tmatch_destroy(payne_tmatch* h);
+
 /* Magnitudes for B parameter vectors: FastPayneSEDPredict.sed
  * (Payne/predict/predictsed.py:75-103).  pars: device fp64 [B][9] =
  * logt, logg, feh, afe, av, rv, logl, dist, logA  (NaN = kwarg absent; the

@@ -41,7 +41,8 @@ SYMBOLS = ["payne_version", "payne_ctx_create", "payne_ctx_set_obs", "payne_ctx_
            "payne_specmlp_train_create", "payne_specmlp_train_step", "payne_specmlp_train_loss", "payne_specmlp_train_predict",
            "payne_specmlp_train_set_lr", "payne_specmlp_train_get", "payne_specmlp_train_steps", "payne_specmlp_train_destroy",
            "payne_specjac_create", "payne_specjac_eval", "payne_specjac_destroy", "payne_fisher_batch",
-           "payne_lmfit_create", "payne_lmfit_begin", "payne_lmfit_trial", "payne_lmfit_update", "payne_lmfit_result", "payne_lmfit_destroy"]
+           "payne_lmfit_create", "payne_lmfit_begin", "payne_lmfit_trial", "payne_lmfit_update", "payne_lmfit_result", "payne_lmfit_destroy",
+           "payne_tmatch_create", "payne_tmatch_match", "payne_tmatch_chunk", "payne_tmatch_destroy"]
 
 PAYNE_MAX_DIM, PAYNE_MAX_FIXED = 24, 16
 PRIOR_UNIFORM, PRIOR_GAUSSIAN, PRIOR_TGAUSSIAN, PRIOR_EXP, PRIOR_TEXP, PRIOR_LOGUNIFORM, PRIOR_TABLE = range(7)
@@ -116,6 +117,7 @@ JAC_ENCODED = 1
 LMFIT_RUNNING, LMFIT_CONVERGED, LMFIT_STALLED, LMFIT_MAXITER, LMFIT_SINGULAR, LMFIT_NAN = range(6)
 LMFIT_STATUS_NAMES = ("RUNNING", "CONVERGED", "STALLED", "MAXITER", "SINGULAR", "NAN")
 LMFIT_MAX_K = 15
+TMATCH_MAX_TOPK = 8
 SPECJAC_MAX_LABELS, FISHER_MAX_ROWS = 8, 16
 
 
@@ -269,6 +271,15 @@ def load(path=None):
     lib.payne_lmfit_result.restype = C.c_int
     lib.payne_lmfit_destroy.argtypes = [ctxp]
     lib.payne_lmfit_destroy.restype = None
+    lib.payne_tmatch_create.argtypes = [C.c_int, C.c_int, C.c_int, C.POINTER(ctxp)]
+    lib.payne_tmatch_create.restype = C.c_int
+    lib.payne_tmatch_match.argtypes = [ctxp, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p,
+                                       C.c_void_p, C.c_void_p, C.c_longlong, C.c_void_p]
+    lib.payne_tmatch_match.restype = C.c_int
+    lib.payne_tmatch_chunk.argtypes = []
+    lib.payne_tmatch_chunk.restype = C.c_int
+    lib.payne_tmatch_destroy.argtypes = [ctxp]
+    lib.payne_tmatch_destroy.restype = None
     lib.payne_ctx_destroy.argtypes = [ctxp]
     lib.payne_ctx_destroy.restype = None
     lib.payne_last_error.argtypes = [ctxp]

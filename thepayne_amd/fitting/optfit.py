@@ -293,3 +293,41 @@ class OptFit(object):
                 tm["update"] += marks[i + 2].elapsed_time(marks[i + 3])
             tm["iterations"] += it
         return res
+
+    def fit_from_bank(self, flux, eflux, bank, topk=1, **fit_kwargs):
+        """``fit`` started from the ``topk`` templates of ``bank`` (a ``tmatch.TemplateBank`` on this fitter's ``obs_wave``) that
+        match each star best: the template's labels, Vrot, Inst_R and Vrad are the start (``fit_vrad`` then refines Vrad).  One
+        ``fit`` call per rank over the stars that have a template of that rank; per star the result of lowest chi^2 among those
+        whose status is not NAN / SINGULAR is kept, the lower rank on a tie (rank 0's if none qualifies).  Returns ``fit``'s dict
+        plus ``start_index`` (the template), ``start_chisq`` (its chi^2 in the search) and ``start_rank``.  A star that no template
+        matches (every chi^2 NaN) keeps status NAN, NaN ``pars`` and ``start_index`` -1.  ``fit_kwargs`` go to ``fit``."""
+        if not hasattr(bank, "match") or not hasattr(bank, "obs_wave"):
+            raise TypeError("bank must be a TemplateBank")
+        if np.shape(bank.obs_wave) != self.obs_wave.shape or not np.array_equal(np.asarray(bank.obs_wave), self.obs_wave):
+            raise ValueError("the bank's obs_wave differs from the fitter's")
+        if "start" in fit_kwargs:
+            raise TypeError("fit_from_bank takes its starts from the bank")
+        flux = np.atleast_2d(np.asarray(flux, dtype=np.float32))
+        eflux = np.atleast_2d(np.asarray(eflux, dtype=np.float64))
+        m = bank.match(flux, eflux, topk=topk)
+        N, k = m["index"].shape
+        K = len(fitted_columns(self.n_labels, bool(fit_kwargs.get("fit_vrad", False))))
+        out = dict(pars=np.full((N, 8), np.nan), chisq=np.full(N, np.nan), npix=m["npix"], fisher=np.full((N, K, K), np.nan),
+                   status=np.full(N, _lib.LMFIT_NAN, dtype=np.int32), niter=np.zeros(N, dtype=np.int32), at_bound=np.zeros(N, dtype=np.uint32),
+                   labels=self.labels(bool(fit_kwargs.get("fit_vrad", False))), err=np.full((N, K), np.nan),
+                   start_index=np.full(N, -1, dtype=np.int32), start_chisq=np.full(N, np.inf), start_rank=np.full(N, -1, dtype=np.int32))
+        per_star = ("pars", "chisq", "fisher", "status", "niter", "at_bound", "err")
+        for r in range(k):
+            sel = np.flatnonzero(m["index"][:, r] >= 0)
+            if len(sel) == 0:
+                continue
+            res = self.fit(flux[sel], eflux[sel], m["pars"][sel, r], **fit_kwargs)
+            valid = (res["status"] != _lib.LMFIT_NAN) & (res["status"] != _lib.LMFIT_SINGULAR)
+            held = out["start_rank"][sel] >= 0
+            held_valid = held & (out["status"][sel] != _lib.LMFIT_NAN) & (out["status"][sel] != _lib.LMFIT_SINGULAR)
+            take = ~held | (valid & (~held_valid | (res["chisq"] < out["chisq"][sel])))
+            dst = sel[take]
+            for name in per_star:
+                out[name][dst] = res[name][take]
+            out["start_index"][dst], out["start_chisq"][dst], out["start_rank"][dst] = m["index"][dst, r], m["chisq"][dst, r], r
+        return out

@@ -1,0 +1,200 @@
+"""Brute-force chi^2 of many spectra against a bank of templates on the GPU: starting points for ``OptFit``.
+
+``TemplateBank`` holds M model spectra on one observed grid (a lattice of labels times a grid of velocities, or any theta the caller
+lists), made by the engine's own forward pass.  ``match`` gives, per star, the ``topk`` templates of lowest
+chi^2 = sum_p w_p (flux_p - template_p)^2 with their chi^2 and parameters.  The N x M chi^2 are one matrix product over 2 n terms on
+the fp64 matrix instruction (payne_tmatch_match; include/payne_hip.h states the rules): the three terms of the expanded square are
+~1e4 times their sum at S/N 100, so the sums are fp64 throughout and the result is within (2 n + 4) 2^-53 of the terms' magnitudes.
+
+No free amplitude or continuum polynomial per template, no interpolation between the lattice's nodes: the best template is a
+start for a fit, not a measurement.  ``OptFit.fit_from_bank`` runs the fit from the best few.
+"""
+import ctypes as C
+import itertools
+
+import numpy as np
+
+from .. import _lib
+from ..engine import THETA_SPEC_COLS
+from ..predict._spec import PayneSpecPredict
+from .forecast import weights_from_errors
+
+__all__ = ["TemplateBank", "TMatchHandle", "lattice_theta", "check_match_args"]
+
+
+def lattice_theta(xmin, xmax, steps, vrad=(0.0,), vrot=(5.0,), inst_R=(np.nan,), inner=(0.0, 1.0)):
+    """theta [M, 8] (getspec's columns): the cell centres of a lattice of ``steps`` cells per label (an int, or one per label) over
+    the part ``inner`` = (a, b) of the box [xmin, xmax] (fractions of its width), times the listed Vrad, Vrot and Inst_R.  The first
+    label varies slowest, Inst_R fastest.  A fifth label is Vmic (column 6); a four-label network's Vmic is NaN (absent), as is an
+    Inst_R of NaN (no instrumental broadening)."""
+    xmin, xmax = np.asarray(xmin, dtype=np.float64), np.asarray(xmax, dtype=np.float64)
+    D = len(xmin)
+    if D not in (4, 5) or xmax.shape != xmin.shape:
+        raise ValueError("xmin and xmax must hold 4 or 5 labels")
+    st = np.full(D, steps, dtype=np.int64) if np.ndim(steps) == 0 else np.asarray(steps, dtype=np.int64)
+    if st.shape != (D,) or np.any(st < 1):
+        raise ValueError("steps must be a positive int or one per label (%d)" % D)
+    a, b = float(inner[0]), float(inner[1])
+    if not (0.0 <= a < b <= 1.0):
+        raise ValueError("inner = (a, b) with 0 <= a < b <= 1")
+    vrad, vrot, inst_R = (np.atleast_1d(np.asarray(v, dtype=np.float64)) for v in (vrad, vrot, inst_R))
+    if min(len(vrad), len(vrot), len(inst_R)) < 1 or not (np.all(np.isfinite(vrad)) and np.all(np.isfinite(vrot))):
+        raise ValueError("vrad, vrot and inst_R must each list at least one value; Vrad and Vrot finite")
+    lo, span = xmin + a * (xmax - xmin), (b - a) * (xmax - xmin)
+    axes = [lo[d] + (np.arange(st[d]) + 0.5) / st[d] * span[d] for d in range(D)] + [vrad, vrot, inst_R]
+    grid = np.array(list(itertools.product(*axes)), dtype=np.float64)
+    theta = np.full((len(grid), 8), np.nan)
+    theta[:, 0:4] = grid[:, 0:4]
+    if D == 5:
+        theta[:, 6] = grid[:, 4]
+    theta[:, 4], theta[:, 5], theta[:, 7] = grid[:, D], grid[:, D + 1], grid[:, D + 2]
+    return theta
+
+
+def check_match_args(flux, eflux, nobs, topk):
+    """What ``TemplateBank.match`` checks of host arrays before anything reaches the device: (flux [N, nobs] fp32, w [N, nobs] fp64).
+    w = 1 / eflux^2 (``weights_from_errors``), and 0 where the flux is not finite."""
+    if not (1 <= int(topk) <= _lib.TMATCH_MAX_TOPK):
+        raise ValueError("topk must be 1 .. %d, got %r" % (_lib.TMATCH_MAX_TOPK, topk))
+    flux = np.atleast_2d(np.asarray(flux, dtype=np.float32))
+    eflux = np.atleast_2d(np.asarray(eflux, dtype=np.float64))
+    if flux.ndim != 2 or flux.shape[1] != nobs:
+        raise ValueError("flux must be [N, %d], got %s" % (nobs, flux.shape))
+    if eflux.shape != flux.shape:
+        raise ValueError("eflux %s and flux %s differ in shape" % (eflux.shape, flux.shape))
+    w = weights_from_errors(eflux)
+    w[~np.isfinite(flux)] = 0.0
+    return flux, w
+
+
+class TMatchHandle(object):
+    """Owner of one ``payne_tmatch`` handle (its workspace of partial lists): at most ``max_stars`` x ``max_templates`` a call."""
+
+    def __init__(self, max_stars, max_templates, device):
+        import torch
+        self.torch, self.lib = torch, _lib.load()
+        self.device, self.max_stars, self.max_templates = device, int(max_stars), int(max_templates)
+        self._h = C.c_void_p()
+        rc = self.lib.payne_tmatch_create(self.device.index, self.max_stars, self.max_templates, C.byref(self._h))
+        if rc != 0:
+            raise RuntimeError("payne_tmatch_create failed (%d): %s" % (rc, self.lib.payne_last_error(None).decode()))
+
+    def match(self, templates, flux, w, topk, n=None, return_all=False):
+        """templates fp32 [M, ld_t], flux fp32 [N, ld_f], w fp64 [N, ld_f]: device tensors whose rows are contiguous; n pixels (the
+        smaller of the two row lengths by default) -> (idx int32 [N, topk], chisq fp64 [N, topk], all fp64 [N, M] or None)."""
+        torch = self.torch
+        if templates.dtype != torch.float32 or flux.dtype != torch.float32 or w.dtype != torch.float64:
+            raise ValueError("templates and flux fp32, w fp64")
+        if templates.dim() != 2 or flux.dim() != 2 or tuple(w.shape) != tuple(flux.shape):
+            raise ValueError("templates [M, ld_t], flux and w [N, ld_f]; got %s, %s, %s" % (tuple(templates.shape), tuple(flux.shape), tuple(w.shape)))
+        if not (templates.is_contiguous() and flux.is_contiguous() and w.is_contiguous()):
+            raise ValueError("templates, flux and w must be contiguous")
+        M, N = templates.shape[0], flux.shape[0]
+        n = min(templates.shape[1], flux.shape[1]) if n is None else int(n)
+        idx = torch.empty((N, topk), dtype=torch.int32, device=self.device)
+        chisq = torch.empty((N, topk), dtype=torch.float64, device=self.device)
+        every = torch.empty((N, M), dtype=torch.float64, device=self.device) if return_all else None
+        stream = C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+        rc = self.lib.payne_tmatch_match(self._h, templates.data_ptr(), templates.shape[1], M, flux.data_ptr(), w.data_ptr(), flux.shape[1], N, n,
+                                         int(topk), idx.data_ptr(), chisq.data_ptr(), every.data_ptr() if return_all else None, M, stream)
+        if rc != 0:
+            raise RuntimeError("payne_tmatch_match failed (%d): %s" % (rc, self.lib.payne_last_error(None).decode()))
+        return idx, chisq, every
+
+    def close(self):
+        if getattr(self, "_h", None) is not None and self._h.value:
+            self.lib.payne_tmatch_destroy(self._h)                  # (waits for the device)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class TemplateBank(object):
+    """TemplateBank(specANNpath, NNtype, obs_wave): templates on the observed grid ``obs_wave`` and the chi^2 search against them.
+    ``max_stars``: stars per call of the device search (``match`` walks more in blocks)."""
+
+    def __init__(self, specANNpath, NNtype, obs_wave, device=None, b_max=256, max_stars=4096):
+        self.obs_wave = np.ascontiguousarray(obs_wave, dtype=np.float64)
+        if self.obs_wave.ndim != 1 or len(self.obs_wave) < 1:
+            raise ValueError("obs_wave must be a vector")
+        if int(max_stars) < 1:
+            raise ValueError("max_stars must be at least 1")
+        self.predictor = PayneSpecPredict(specANNpath, NNtype=NNtype, device=device, b_max=b_max)
+        self.n_labels = self.predictor.anns.n_labels
+        self.max_stars = int(max_stars)
+        self.theta, self.templates, self._handle = None, None, None
+
+    def lattice(self, steps, vrad=(0.0,), vrot=(5.0,), inst_R=(np.nan,), inner=(0.0, 1.0)):
+        """``build`` on ``lattice_theta`` of the network's box; returns self."""
+        anns = self.predictor.anns
+        return self.build(lattice_theta(anns.xmin[:self.n_labels], anns.xmax[:self.n_labels], steps, vrad=vrad, vrot=vrot, inst_R=inst_R, inner=inner))
+
+    def build(self, theta):
+        """theta [M, 8] (getspec's columns, any Vrad / Vrot / Inst_R per template) -> the templates, ``predict_batch(theta, stage=2)``
+        in the engine's blocks, as one fp32 device tensor [M, nobs]; returns self."""
+        theta = np.atleast_2d(np.asarray(theta, dtype=np.float64))
+        if theta.ndim != 2 or theta.shape[1] != 8 or theta.shape[0] < 1:
+            raise ValueError("theta must be [M, 8] (%s), got %s" % (", ".join(THETA_SPEC_COLS), theta.shape))
+        P = self.predictor
+        eng = P.anns.engine
+        P._bind(self.obs_wave)
+        M, step = theta.shape[0], eng.b_max
+        out = eng.torch.empty((M, len(self.obs_wave)), dtype=eng.torch.float32, device=eng.device)
+        for s in range(0, M, step):
+            th = np.full((min(step, M - s), eng.ncols), np.nan)
+            th[:, :8] = theta[s:s + step]
+            out[s:s + step] = eng.predict_batch(th, stage=2)
+        self.close()
+        self.theta, self.templates = theta.copy(), out
+        return self
+
+    def __len__(self):
+        return 0 if self.theta is None else len(self.theta)
+
+    def match(self, flux, eflux, topk=1, return_all=False):
+        """flux, eflux [N, nobs] on ``obs_wave`` (host arrays or device tensors; eflux zero or not finite, or a flux that is not
+        finite: the pixel does not count) -> dict: ``index`` int32 [N, topk] (-1: no such template), ``chisq`` [N, topk] ascending
+        (+inf there), ``pars`` [N, topk, 8] the bank's theta rows (NaN there), ``npix`` (pixels with w != 0) and, with
+        ``return_all``, ``all`` [N, M].  Equal chi^2 are listed in ascending template index; a NaN chi^2 is never listed."""
+        if self.templates is None:
+            raise RuntimeError("the bank is empty: call build(theta) or lattice(steps, ...) first")
+        eng = self.predictor.anns.engine
+        torch, dev, nobs = eng.torch, eng.device, len(self.obs_wave)
+        if isinstance(flux, torch.Tensor) or isinstance(eflux, torch.Tensor):
+            if not (1 <= int(topk) <= _lib.TMATCH_MAX_TOPK):
+                raise ValueError("topk must be 1 .. %d, got %r" % (_lib.TMATCH_MAX_TOPK, topk))
+            f = torch.as_tensor(flux).to(device=dev, dtype=torch.float32).reshape(-1, nobs).contiguous()
+            e = torch.as_tensor(eflux).to(device=dev, dtype=torch.float64)
+            if tuple(e.shape) != tuple(f.shape):
+                raise ValueError("eflux %s and flux %s differ in shape" % (tuple(e.shape), tuple(f.shape)))
+            ok = torch.isfinite(e) & (e != 0.0) & torch.isfinite(f)
+            w = torch.where(ok, 1.0 / (e * e), torch.zeros_like(e)).contiguous()
+        else:
+            fh, wh = check_match_args(flux, eflux, nobs, topk)
+            f, w = torch.as_tensor(fh).to(dev), torch.as_tensor(wh).to(dev)
+        N, M, k = f.shape[0], len(self), int(topk)
+        if self._handle is None:
+            self._handle = TMatchHandle(self.max_stars, M, dev)
+        index = np.empty((N, k), dtype=np.int32)
+        chisq = np.empty((N, k))
+        every = np.empty((N, M)) if return_all else None
+        for s in range(0, N, self.max_stars):
+            e_ = min(N, s + self.max_stars)
+            i_d, c_d, a_d = self._handle.match(self.templates, f[s:e_], w[s:e_], k, n=nobs, return_all=return_all)
+            index[s:e_], chisq[s:e_] = i_d.cpu().numpy(), c_d.cpu().numpy()
+            if return_all:
+                every[s:e_] = a_d.cpu().numpy()
+        pars = np.where((index >= 0)[:, :, None], self.theta[np.maximum(index, 0)], np.nan)
+        out = dict(index=index, chisq=chisq, pars=pars, npix=(w != 0.0).sum(dim=1).cpu().numpy())
+        if return_all:
+            out["all"] = every
+        return out
+
+    def close(self):
+        if getattr(self, "_handle", None) is not None:
+            self._handle.close()
+            self._handle = None

@@ -1,0 +1,130 @@
+"""Template-bank chi^2 search on one GPU: thepayne_amd.fitting.tmatch (payne_tmatch_match) against torch's own fp64 matrix form on
+the same card and numpy's direct sum on one CPU core.
+
+    python tools/tmatch_bench.py [--stars 4096] [--nobs 3600] [--templates 4096,65536] [--topk 4] [--repeats 5] [--warmup 1] [--numpy-stars 8]
+
+The workload: tools/optfit_bench.py's SMLP 4-256-256-256-4096, 3600 observed pixels, stars drawn in the inner half of the label box,
+spectra from the model itself plus seeded noise at S/N 100.  The bank: a lattice of the four labels (4 per label for 4096 templates,
+8 per label for 65 536) times 16 radial velocities, one Vrot and Inst_R.  A timed unit is one payne_tmatch_match call (both
+launches) on device tensors between two events on the stream, warm; the figure is the median of `repeats` calls.  The share of the
+fp64 matrix rate counts 4 N M n flop (two multiply-adds a pixel and pair) against the card's 78.6 TFLOP/s.  `build` is the wall
+time of TemplateBank.lattice (the forward pass of every template), synchronised.
+torch's form on the same tensors: (w f) @ (-2 m).T + w @ (m m).T + c0 in fp64, then torch.topk, in template blocks as large as
+half of the free memory allows (its fp64 operand copies and N x block buffers are counted and reported), block lists merged by a
+second topk.  numpy: sum w (f - m)^2 for `numpy-stars` stars against at most 4096 templates, one thread.  Prints one JSON line."""
+import argparse
+import json
+import os
+import sys
+import time
+
+import numpy as np
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+FP64_MATRIX_PEAK = 78.6e12
+
+
+def timed(torch, fn, repeats, warmup):
+    ms = []
+    for r in range(repeats + warmup):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        out = fn()
+        e1.record()
+        e1.synchronize()
+        if r >= warmup:
+            ms.append(e0.elapsed_time(e1))
+    return float(np.median(ms)), float(np.min(ms)), out
+
+
+def torch_form(torch, templates, f, w, topk, budget):
+    """(idx, chisq, bytes of its buffers): the expanded form on torch's fp64 matmul, templates in blocks."""
+    N, n = f.shape
+    M = templates.shape[0]
+    per_template = 2 * n * 8 + 3 * N * 8                            # -2 m and m^2 in fp64; two products and their sum
+    block = int(max(1, min(M, budget // per_template)))
+    a1 = w * f.double()
+    c0 = (a1 * f.double()).sum(dim=1, keepdim=True)
+    best_c, best_i = None, None
+    for s in range(0, M, block):
+        m = templates[s:s + block].double()
+        chi = a1 @ (-2.0 * m).T + w @ (m * m).T + c0
+        c, i = torch.topk(chi, min(topk, chi.shape[1]), dim=1, largest=False)
+        i = i + s
+        if best_c is None:
+            best_c, best_i = c, i
+        else:
+            cc, ii = torch.cat([best_c, c], dim=1), torch.cat([best_i, i], dim=1)
+            best_c, pick = torch.topk(cc, topk, dim=1, largest=False)
+            best_i = torch.gather(ii, 1, pick)
+    return best_i, best_c, block * per_template + 2 * N * n * 8, block
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--stars", type=int, default=4096)
+    ap.add_argument("--nobs", type=int, default=3600)
+    ap.add_argument("--templates", default="4096,65536")
+    ap.add_argument("--topk", type=int, default=4)
+    ap.add_argument("--repeats", type=int, default=5)
+    ap.add_argument("--warmup", type=int, default=1)
+    ap.add_argument("--numpy-stars", type=int, default=8)
+    ap.add_argument("--b-max", type=int, default=512)
+    args = ap.parse_args()
+    import torch
+    from optfit_bench import workload
+    from thepayne_amd.fitting.optfit import OptFit
+    from thepayne_amd.fitting.tmatch import TemplateBank, TMatchHandle
+    net, obs_wave, truth, start, rng = workload(args.stars, args.nobs)
+    fit = OptFit(net, "SMLP", obs_wave, b_max=args.b_max)
+    P, eng = fit.predictor, fit.predictor.anns.engine
+    P._bind(obs_wave)
+    th = np.full((args.stars, eng.ncols), np.nan)
+    th[:, :8] = truth
+    clean = torch.cat([eng.smooth_batch(P._jacobian().eval(truth[s:s + 512, :4])[0], th[s:s + 512], stage=2) for s in range(0, args.stars, 512)])
+    flux = (clean.cpu().numpy().astype(np.float64) + rng.normal(0, 0.01, (args.stars, args.nobs))).astype(np.float32)
+    dev = eng.device
+    f_d = torch.as_tensor(flux).to(dev)
+    w_d = torch.full(flux.shape, 1e4, dtype=torch.float64, device=dev)
+    N, n = flux.shape
+    out = {"stars": N, "nobs": n, "topk": args.topk, "repeats": args.repeats, "warmup": args.warmup, "fp64_matrix_peak": FP64_MATRIX_PEAK, "runs": []}
+    for M in [int(v) for v in args.templates.split(",")]:
+        steps = int(round((M / 16.0) ** 0.25))
+        bank = TemplateBank(net, "SMLP", obs_wave, b_max=args.b_max, max_stars=N)
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        bank.lattice(steps, vrad=np.linspace(-30.0, 30.0, 16), vrot=(10.0,), inst_R=(20000.0,))
+        torch.cuda.synchronize()
+        build_s = time.perf_counter() - t0
+        M = len(bank)
+        h = TMatchHandle(N, M, dev)
+        ms, ms_min, (idx, chisq, _) = timed(torch, lambda: h.match(bank.templates, f_d, w_d, args.topk, n=n), args.repeats, args.warmup)
+        flop = 4.0 * N * M * n
+        run = {"templates": M, "lattice_steps": steps, "build_s": build_s, "template_values_not_finite": int((~torch.isfinite(bank.templates)).sum().item()), "match_ms_median": ms, "match_ms_min": ms_min,
+               "star_templates_per_s": N * M / (ms * 1e-3), "flop_per_s": flop / (ms * 1e-3), "fraction_of_fp64_matrix_peak": flop / (ms * 1e-3) / FP64_MATRIX_PEAK}
+        free, _total = torch.cuda.mem_get_info(dev)
+        t_ms, t_min, (t_idx, t_c, t_bytes, t_block) = timed(torch, lambda: torch_form(torch, bank.templates, f_d, w_d, args.topk, free // 2), args.repeats, args.warmup)
+        run.update(torch_ms_median=t_ms, torch_ms_min=t_min, torch_buffer_bytes=int(t_bytes), torch_template_block=int(t_block),
+                   torch_star_templates_per_s=N * M / (t_ms * 1e-3), torch_over_kernel_time=t_ms / ms,
+                   top1_agree_with_torch=float((t_idx[:, 0] == idx[:, 0].long()).double().mean().item()),
+                   max_abs_dchisq_top1=float((t_c[:, 0] - chisq[:, 0]).abs().max().item()))
+        if args.numpy_stars > 0:
+            tm = bank.templates[:4096].cpu().numpy().astype(np.float64)
+            ww = np.full(n, 1e4)
+            t0 = time.perf_counter()
+            for s in range(args.numpy_stars):
+                d = flux[s].astype(np.float64)[None, :] - tm
+                (ww[None, :] * d * d).sum(axis=1)
+            sec = time.perf_counter() - t0
+            run.update(numpy_star_templates_per_s=args.numpy_stars * len(tm) / sec, kernel_over_numpy=(N * M / (ms * 1e-3)) / (args.numpy_stars * len(tm) / sec))
+        out["runs"].append(run)
+        h.close()
+        bank.close()
+        del bank, h
+        torch.cuda.empty_cache()
+    print(json.dumps(out), flush=True)
+
+
+if __name__ == "__main__":
+    main()
