@@ -96,6 +96,66 @@ def test_modpoly_matches_reference_golden(emul, golden):
     assert np.all(np.abs(-0.5 * chi2 - g["lnlike"]) <= lnl_tol(g["lnlike"]))
 
 
+BLAZE_FLUX_TOL = 2e-6          # where the blaze multiplies (tests/test_api_gpu.py, tests/test_fuzz_gpu.py)
+_blaze_cache = {}
+
+
+def _blaze_problem(npoly):
+    """The `small` problem with deep lines, six candidates (one that does not rotate, one without an instrumental stage) and `npoly`
+    Chebyshev coefficients that differ from row to row (pc_0 ~ U(0.9, 1.1), the others N(0, 0.05): a blaze within about 0.7 .. 1.3),
+    and the oracle's genspec(modpoly=True) / lnlikefn for them: computed once per order, read by every case."""
+    if npoly not in _blaze_cache:
+        from helpers import yst_problem, SPEC_PARS
+        net, obs, flux, eflux = yst_problem("small", H=64, line_depth=0.3)
+        th7 = synth.draw_candidates(6, seed=41)
+        th7[1, 5] = 0.0
+        th7[2, 6] = np.nan
+        rng = np.random.default_rng(100 + npoly)
+        pcs = np.column_stack([rng.uniform(0.9, 1.1, 6), rng.normal(0.0, 0.05, (6, npoly - 1))])
+        th8 = _th8(th7)
+        with np.errstate(all="ignore"):
+            spec = np.array([O.genspec(net, list(t) + list(p), outwave=obs, modpoly=True)[1] for t, p in zip(th8, pcs)])
+            L = O.OracleLikelihood(net, obs, flux, eflux, SPEC_PARS + ["pc_%d" % i for i in range(npoly)], modpoly=True)
+            lnl = np.array([L.lnlikefn(list(t) + list(p)) for t, p in zip(th7, pcs)])
+        for a in (th8, pcs, spec, lnl):
+            a.setflags(write=False)
+        _blaze_cache[npoly] = (net, obs, flux, eflux, th8, pcs, spec, lnl)
+    return _blaze_cache[npoly]
+
+
+def _check_blaze(emul, npoly, **kw):
+    net, obs, flux, eflux, th8, pcs, spec, lnl = _blaze_problem(npoly)
+    assert np.isfinite(spec).all() and np.isfinite(lnl).all()              # (no row of these is NaN: every one compares)
+    out, _, _ = emul(net, obs, flux, eflux, th8, 3, npoly=npoly, pcs=pcs, **kw)
+    assert np.isfinite(out).all()
+    assert np.abs(out - spec).max() <= BLAZE_FLUX_TOL, np.abs(out - spec).max()
+    _, chi2, _ = emul(net, obs, flux, eflux, th8, -1, npoly=npoly, pcs=pcs, **kw)
+    assert np.all(np.abs(-0.5 * chi2 - lnl) <= lnl_tol(lnl)), (np.abs(-0.5 * chi2 - lnl) / lnl_tol(lnl)).max()
+    # the blaze is in the numbers compared: without it the same rows are far outside the bound
+    flat, _, _ = emul(net, obs, flux, eflux, th8, 2, npoly=npoly, pcs=pcs, **kw)
+    assert np.abs(flat - spec).max() > 1e3 * BLAZE_FLUX_TOL
+
+
+@pytest.mark.parametrize("prep", [1, 0], ids=["records", "in_kernel"])
+@pytest.mark.parametrize("general", [0, 1])
+@pytest.mark.parametrize("npoly", [1, 2, 3, 4, 7, 12])
+def test_blaze_of_every_order_vs_oracle(emul, npoly, general, prep):
+    """The Chebyshev blaze at every length Clenshaw's recurrence takes a branch of its own for (one coefficient, two, the loop from
+    three up to PAYNE_MAX_POLY = 12), through the compile-time and the runtime geometry, the coefficients loaded by the record made
+    ahead (prep_candidate: twelve loads with a clamped column) and inside the kernel (phase_setup): genspec(modpoly=True) and the
+    chi^2 of a modpoly fit against the oracle."""
+    _check_blaze(emul, npoly, general=general, prep=prep)
+
+
+@pytest.mark.parametrize("prep", [1, 0], ids=["records", "in_kernel"])
+@pytest.mark.parametrize("npoly", [1, 12])
+def test_blaze_coefficients_reach_a_single_wave(emul, npoly, prep):
+    """phase_setup spreads its chains over the first threads of four waves (`lanes` = 64) in a workgroup of 256 or more, the
+    coefficients on thread 3 * lanes; a smaller group has lanes = 0 and thread 0 does everything.  The thread that loads the
+    coefficients therefore exists at every group size: 64 threads give the oracle's spectrum and chi^2 as 512 do."""
+    _check_blaze(emul, npoly, general=1, prep=prep, nthreads=64)
+
+
 @pytest.mark.parametrize("npix,nobs,nthreads", [(300, 250, 64), (777, 600, 256), (2048, 1800, 128), (5000, 4000, 256), (40000, 30000, 512)])
 def test_ragged_sizes_vs_oracle(emul, npix, nobs, nthreads):
     """npix not a power of two (the vsini grid is then a genuine resampling), few threads."""
@@ -131,7 +191,7 @@ def test_emulator_under_address_and_ub_sanitizers(tmp_path):
 #include <cstdio>
 #include <vector>
 extern "C" int payne_emul_post(const double*, int, double, const double*, const double*, const double*, int, int,
-    const double*, int, int, double, const float*, int, float*, int, double*, int*, int, int);
+    const double*, int, int, double, const float*, int, float*, int, double*, int*, int, int, int);
 int main() {
   const int npix = 700, nobs = 500, B = 3;
   std::vector<double> w(npix), ow(nobs), fl(nobs, 1.0), ef(nobs, 0.01), th(B * 8);
@@ -142,9 +202,31 @@ int main() {
   for (int b = 0; b < B; ++b) { double* t = &th[b * 8]; t[0]=5770; t[1]=4.4; t[2]=0; t[3]=0; t[4]=10.0*b; t[5]=b; t[6]=NAN; t[7]=25000+2000*b; }
   std::vector<float> out(B * nobs); std::vector<double> chi(B); std::vector<int> info(3 * B);
   int rc = payne_emul_post(w.data(), npix, 32000 * 2.3548, ow.data(), fl.data(), ef.data(), nobs, 0, th.data(), 8, B, 2.355,
-                           raw.data(), 2, out.data(), nobs, chi.data(), info.data(), 256, 0);
+                           raw.data(), 2, out.data(), nobs, chi.data(), info.data(), 256, 0, 1);
   std::printf("rc=%d chi=%g\n", rc, chi[1]);
-  return rc;
+  if (rc) return rc;
+  // the blaze polynomial at the lengths that index pc[12] / S.poly[12] at their ends (S.poly[nc - r]): one, two and twelve
+  // coefficients in rows of exactly 8 + npoly values (nothing behind the last coefficient belongs to the row), genspec's
+  // spectrum (stage 3) and the chi^2 (stage -1), the coefficients loaded by the record made ahead and inside the kernel
+  const int orders[3] = {1, 2, 12};
+  for (int o = 0; o < 3; ++o) {
+    const int np = orders[o], nc = 8 + np;
+    std::vector<double> tp(B * nc);
+    for (int b = 0; b < B; ++b) {
+      for (int k = 0; k < 8; ++k) tp[b * nc + k] = th[b * 8 + k];
+      tp[b * nc + 8] = 1.0 + 0.03 * b;
+      for (int k = 1; k < np; ++k) tp[b * nc + 8 + k] = 0.04 * std::sin(1.0 + k + 3 * b);
+    }
+    for (int prep = 0; prep < 2; ++prep)
+      for (int s = 0; s < 2; ++s) {
+        const int stage = s ? -1 : 3;
+        rc = payne_emul_post(w.data(), npix, 32000 * 2.3548, ow.data(), fl.data(), ef.data(), nobs, np, tp.data(), nc, B, 2.355,
+                             raw.data(), stage, out.data(), nobs, chi.data(), info.data(), 256, 0, prep);
+        std::printf("npoly=%d prep=%d stage=%d rc=%d chi=%g out=%g\n", np, prep, stage, rc, chi[1], out[nobs + 7]);
+        if (rc || !(chi[1] == chi[1]) || !(out[nobs + 7] == out[nobs + 7])) return 1;
+      }
+  }
+  return 0;
 }''')
     cmd = ["g++", "-O1", "-g", "-std=c++17", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
            str(main), os.path.join(ROOT, "tests", "emul", "cpu_emul.cpp"), "-o", str(exe)]
@@ -152,6 +234,10 @@ int main() {
     res = subprocess.run([str(exe)], capture_output=True, text=True)
     assert res.returncode == 0, res.stderr[-2000:]
     assert "rc=0" in res.stdout
+    for npoly in (1, 2, 12):
+        for prep in (0, 1):
+            for stage in (3, -1):
+                assert "npoly=%d prep=%d stage=%d rc=0" % (npoly, prep, stage) in res.stdout, res.stdout
 
 
 @pytest.mark.parametrize("general", [0, 1])
