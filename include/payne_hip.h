@@ -594,6 +594,64 @@ int payne_tmatch_match(payne_tmatch* h, const float* templates_dev, int ld_t, in
 int payne_tmatch_chunk(void);
 void payne_tmatch_destroy(payne_tmatch* h);
 
+/* ---- continuum polynomials: the blaze's Chebyshev coefficients for many stars against a given model row each ----
+ * payne_contfit_batch: per star the c [P] that minimise chi^2 = sum_p w_p (f_p - m_p sum_j c_j T_j(x_p))^2, the likelihood's own
+ * objective in its pc_* parameters (modpoly: model x polycalc) for a fixed model, which is linear least squares; optional
+ * kappa-sigma clipping; and the spectrum divided by the polynomial with its weights carried along, sum w (f - m p)^2 =
+ * sum (w p^2) (f / p - m)^2.  One stateless call, one 256-thread workgroup a star, enqueued on `stream`; nothing waits.
+ * csrc/contfit_core.hpp holds the arithmetic and its order; in short, per star:
+ *   pixels   a pixel counts if w != 0.  One with w == 0 is ignored whatever flux and model hold there (NaN, 1e30), by a select, as
+ *            in payne_lmfit_update and payne_tmatch_match.  A counting pixel whose flux, model or weight is not finite: status NAN.
+ *            A model_index outside [0, n_models): BAD_MODEL, and nothing is read through it.
+ *   sums     R [P + 1][n]: R_j = m T_j(x) (T by the three-term recurrence in fp64), R_P = f.  G = R diag(w_kept) R^T on the fp64
+ *            matrix instruction with payne_lmfit_update's operand map and pixel order; four partial tiles added in wave order, no
+ *            atomics.  G holds the normal matrix, the right-hand side G[j][P] and sum w f^2 = G[P][P].
+ *   solve    one thread: the matrix scaled to a unit diagonal, Cholesky, c; chi^2 = e^T G e with e = (c, -1), that is
+ *            G[P][P] - 2 c.b + c^T A c (no second pass over the residuals: without clipping every pixel is read once for the fit).
+ *            A diagonal entry or pivot that is not positive, or a c or chi^2 that is not finite: SINGULAR.  Fewer kept pixels than
+ *            P: TOO_FEW.
+ *   clipping nclip > 0: z_p = sqrt(w_p) (f_p - m_p p(x_p)) over every counting pixel (a pixel may come back); s = 1 or, with
+ *            `rescale`, sqrt(max(chi^2, 0) / max(1, kept - P)); kept iff -kappa_lo s <= z_p <= kappa_hi s.  The fit is repeated on
+ *            the kept pixels until the mask does not change, at most nclip times.  rounds = the solves that succeeded; npix = the
+ *            kept pixels of the last solve (of the attempt that failed, for TOO_FEW / SINGULAR / NAN; 0 for BAD_MODEL), chisq is
+ *            over them.
+ *   outputs  flux_out = f / p rounded to fp32 (for every pixel: NaN where the flux is NaN), w_out = (w p) p; w_out = 0 for a pixel
+ *            that does not count and, with drop_clipped, for a pixel the last solve did not keep.  Where p <= 0 or is not finite
+ *            w_out = 0 and flux_out = 0; on a counting pixel that makes the status NONPOSITIVE (whether or not output rows were
+ *            asked for), and the coefficients are still reported.  NAN, SINGULAR, TOO_FEW, BAD_MODEL: coefficients and chi^2 are
+ *            NaN, w_out = 0 and flux_out = the input flux.  Nothing is written beyond column n of a row or beyond [N][P].
+ * The same inputs give the same bytes, and a star's bytes do not depend on the batch it is in.  Rows are read (and written) 16
+ * bytes a lane where ld_f, ld_m, ld_o are multiples of four and every pointer is 16-byte aligned, element by element otherwise
+ * (the same bytes).
+ * flux_dev DEVICE fp32 [N][ld_f], w_dev DEVICE fp64 [N][ld_f]; model_dev DEVICE fp32 [n_models][ld_m]; model_index_dev DEVICE int
+ * [N], or NULL: star s uses row s; x_dev DEVICE fp64 [n], polycalc's abscissa in [-1, 1]; coef_dev fp64 [N][P], chisq_dev fp64 [N],
+ * npix_dev, status_dev, rounds_dev int [N]; flux_out_dev fp32 [N][ld_o] and w_out_dev fp64 [N][ld_o], each may be NULL.
+ *   PAYNE_E_INVALID      null opts, P outside 1 .. PAYNE_CONTFIT_MAX_P, nclip outside 0 .. PAYNE_CONTFIT_MAX_NCLIP, a kappa that is
+ *                        not positive, N < 0, n < 1, ld_f < n, ld_m < n, n_models < 1, n_models < N without model_index_dev, ld_o < n
+ *                        with an output row; with N > 0 a null flux_dev / w_dev / model_dev / x_dev / coef_dev / chisq_dev /
+ *                        npix_dev / status_dev / rounds_dev
+ *   PAYNE_E_UNSUPPORTED  n > PAYNE_CONTFIT_MAX_N (the clipping mask is a bit set in LDS)
+ * N == 0 succeeds and does nothing; payne_last_error(NULL) has the message of a failure. */
+#define PAYNE_CONTFIT_OK 0
+#define PAYNE_CONTFIT_NONPOSITIVE 1
+#define PAYNE_CONTFIT_TOO_FEW 2
+#define PAYNE_CONTFIT_SINGULAR 3
+#define PAYNE_CONTFIT_NAN 4
+#define PAYNE_CONTFIT_BAD_MODEL 5
+#define PAYNE_CONTFIT_MAX_P 15
+#define PAYNE_CONTFIT_MAX_NCLIP 16
+#define PAYNE_CONTFIT_MAX_N 262144
+
+typedef struct payne_contfit_opts {
+  int P, nclip, rescale, drop_clipped;
+  double kappa_lo, kappa_hi;
+} payne_contfit_opts;
+
+int payne_contfit_batch(int device, const float* flux_dev, const double* w_dev, long long ld_f, const float* model_dev, long long ld_m,
+                        int n_models, const int* model_index_dev, const double* x_dev, int N, int n, const payne_contfit_opts* opts,
+                        double* coef_dev, double* chisq_dev, int* npix_dev, int* status_dev, int* rounds_dev, float* flux_out_dev,
+                        double* w_out_dev, long long ld_o, void* stream);
+
 /* Magnitudes for B parameter vectors: FastPayneSEDPredict.sed
  * (Payne/predict/predictsed.py:75-103).  pars: device fp64 [B][9] =
  * logt, logg, feh, afe, av, rv, logl, dist, logA  (NaN = kwarg absent; the

@@ -42,7 +42,8 @@ SYMBOLS = ["payne_version", "payne_ctx_create", "payne_ctx_set_obs", "payne_ctx_
            "payne_specmlp_train_set_lr", "payne_specmlp_train_get", "payne_specmlp_train_steps", "payne_specmlp_train_destroy",
            "payne_specjac_create", "payne_specjac_eval", "payne_specjac_destroy", "payne_fisher_batch",
            "payne_lmfit_create", "payne_lmfit_begin", "payne_lmfit_trial", "payne_lmfit_update", "payne_lmfit_result", "payne_lmfit_destroy",
-           "payne_tmatch_create", "payne_tmatch_match", "payne_tmatch_chunk", "payne_tmatch_destroy"]
+           "payne_tmatch_create", "payne_tmatch_match", "payne_tmatch_chunk", "payne_tmatch_destroy",
+           "payne_contfit_batch"]
 
 PAYNE_MAX_DIM, PAYNE_MAX_FIXED = 24, 16
 PRIOR_UNIFORM, PRIOR_GAUSSIAN, PRIOR_TGAUSSIAN, PRIOR_EXP, PRIOR_TEXP, PRIOR_LOGUNIFORM, PRIOR_TABLE = range(7)
@@ -113,11 +114,22 @@ class LmfitOpts(C.Structure):
         super(LmfitOpts, self).__init__(float(lambda0), float(down), float(up), float(lambda_min), float(lambda_max), float(xtol), int(maxiter))
 
 
+class ContfitOpts(C.Structure):
+    """payne_contfit_opts."""
+    _fields_ = [("P", C.c_int), ("nclip", C.c_int), ("rescale", C.c_int), ("drop_clipped", C.c_int), ("kappa_lo", C.c_double), ("kappa_hi", C.c_double)]
+
+    def __init__(self, P=4, nclip=0, rescale=False, drop_clipped=True, kappa_lo=3.0, kappa_hi=3.0):
+        super(ContfitOpts, self).__init__(int(P), int(nclip), int(bool(rescale)), int(bool(drop_clipped)), float(kappa_lo), float(kappa_hi))
+
+
 JAC_ENCODED = 1
 LMFIT_RUNNING, LMFIT_CONVERGED, LMFIT_STALLED, LMFIT_MAXITER, LMFIT_SINGULAR, LMFIT_NAN = range(6)
 LMFIT_STATUS_NAMES = ("RUNNING", "CONVERGED", "STALLED", "MAXITER", "SINGULAR", "NAN")
 LMFIT_MAX_K = 15
 TMATCH_MAX_TOPK = 8
+CONTFIT_OK, CONTFIT_NONPOSITIVE, CONTFIT_TOO_FEW, CONTFIT_SINGULAR, CONTFIT_NAN, CONTFIT_BAD_MODEL = range(6)
+CONTFIT_STATUS_NAMES = ("OK", "NONPOSITIVE", "TOO_FEW", "SINGULAR", "NAN", "BAD_MODEL")
+CONTFIT_MAX_P, CONTFIT_MAX_NCLIP, CONTFIT_MAX_N = 15, 16, 262144
 SPECJAC_MAX_LABELS, FISHER_MAX_ROWS = 8, 16
 
 
@@ -280,6 +292,10 @@ def load(path=None):
     lib.payne_tmatch_chunk.restype = C.c_int
     lib.payne_tmatch_destroy.argtypes = [ctxp]
     lib.payne_tmatch_destroy.restype = None
+    lib.payne_contfit_batch.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_longlong, C.c_void_p, C.c_longlong, C.c_int, C.c_void_p, C.c_void_p,
+                                        C.c_int, C.c_int, C.POINTER(ContfitOpts), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                        C.c_void_p, C.c_void_p, C.c_longlong, C.c_void_p]
+    lib.payne_contfit_batch.restype = C.c_int
     lib.payne_ctx_destroy.argtypes = [ctxp]
     lib.payne_ctx_destroy.restype = None
     lib.payne_last_error.argtypes = [ctxp]

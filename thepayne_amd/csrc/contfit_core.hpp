@@ -1,0 +1,284 @@
+// contfit_core.hpp -- arithmetic of payne_contfit_batch (k_contfit.hip): per star the Chebyshev coefficients c that minimise
+// sum_p w_p (f_p - m_p sum_j c_j T_j(x_p))^2 for a given model row m, with optional kappa-sigma clipping, and the spectrum divided by
+// that polynomial.  Plain C++, host / device: the same source runs in the kernel and on the host (tests/emul/contfit_emul.cpp, also
+// under ASan / UBSan).  Every array is the caller's (LDS or global memory in the kernel); the emulator fills its workspace with NaN
+// before every star, as LDS holds whatever the workgroup before left there.
+//   counting a pixel counts if it is inside n and w != 0; any other pixel is replaced by zeros by a select, whatever it holds.
+//   rows     R [P + 1][n] in fp64: R_j = m T_j(x) (one rounded product) for j < P, R_P = f.  T_j is `cheb`: T_0 = 1, T_1 = x,
+//            T_k = fma(2 x, T_k-1, -T_k-2).  G = R diag(w_kept) R^T is one 16 x 16 tile in lmfit_core.hpp's pixel groups, wave
+//            stripes and operand pair (value, value * w); the four partial tiles are added in wave order.
+//   solve    solve_star: S = diag(G_kk^-1/2), Cholesky of S A S (unit diagonal), c = S u, and
+//            chi^2 = e^T G e with e = (c, -1), i.e. G[P][P] - 2 c.b + c^T A c, summed row by row in fp64.  (Not a second pass over
+//            the residuals: without clipping the kernel reads every pixel once.  The form is second-order in c's error; what it
+//            loses is the sums' rounding, n 2^-52 sum_ij |e_i e_j| sum_p |R_i R_j| w.)
+//   clipping keeps: z = sqrt(w) fma(-m, p(x), f) over every counting pixel, kept iff -kappa_lo s <= z <= kappa_hi s, s = clip_scale.
+//   outputs  out_pixel: f / p rounded to fp32 and (w p) p; zero where p <= 0 or is not finite.
+//   order    fit_star_host below is the kernel's sequence of passes, statement by statement.
+#pragma once
+#include <math.h>
+#include <stddef.h>
+
+#include <vector>
+
+#include "../../include/payne_hip.h"
+#include "lmfit_core.hpp"
+
+namespace payne {
+namespace contfit {
+
+namespace lm = payne::lmfit;
+
+constexpr int kMaxP = PAYNE_CONTFIT_MAX_P;
+constexpr int kMaxClip = PAYNE_CONTFIT_MAX_NCLIP;
+constexpr int kMaxN = PAYNE_CONTFIT_MAX_N;            // the clipping mask is a bit set in LDS
+constexpr int kWorkDoubles = kMaxP * kMaxP + 2 * kMaxP;   // solve_star's workspace: the scaled matrix, S, u
+constexpr int kChunk = 4;                             // pixels a thread takes at a time in the residual and output passes
+
+PAYNE_LMFIT_HD bool opts_ok(const payne_contfit_opts& o) {
+  return o.P >= 1 && o.P <= kMaxP && o.nclip >= 0 && o.nclip <= kMaxClip && o.kappa_lo > 0.0 && o.kappa_hi > 0.0;
+}
+PAYNE_LMFIT_HD int mask_words(int n) { return (n + 31) / 32; }
+PAYNE_LMFIT_HD bool finite_f(float v) { return lm::finite((double)v); }
+PAYNE_LMFIT_HD bool failed(int status) { return status != PAYNE_CONTFIT_OK && status != PAYNE_CONTFIT_NONPOSITIVE; }
+
+// The three-term recurrence, written once: T_k = 2 x T_k-1 - T_k-2.
+PAYNE_LMFIT_HD double cheb_next(double x, double t1, double t0) { return fma(2.0 * x, t1, -t0); }
+
+// T_i(x).
+PAYNE_LMFIT_HD double cheb(int i, double x) {
+  if (i == 0) return 1.0;
+  double t0 = 1.0, t1 = x;
+  for (int k = 2; k <= i; ++k) {
+    const double t2 = cheb_next(x, t1, t0);
+    t0 = t1;
+    t1 = t2;
+  }
+  return t1;
+}
+
+// T_i at four abscissae, the same values: one loop for the four, and a trip count (P) that every lane of a wave shares -- the lanes
+// differ only in the step they keep.  (Four calls of cheb are four loops whose length differs from lane to lane; measured, NOTES.md.)
+PAYNE_LMFIT_HD void cheb4(int i, int P, const double* x, double* T) {
+  double t0[4], t1[4];
+  for (int t = 0; t < 4; ++t) {
+    t0[t] = 1.0;
+    t1[t] = x[t];
+    T[t] = i == 0 ? 1.0 : x[t];
+  }
+  for (int k = 2; k < P; ++k)
+    for (int t = 0; t < 4; ++t) {
+      const double t2 = cheb_next(x[t], t1[t], t0[t]);
+      t0[t] = t1[t];
+      t1[t] = t2;
+      T[t] = k == i ? t2 : T[t];
+    }
+}
+
+// p(x) = sum_j c_j T_j(x), j ascending, on the same recurrence.
+PAYNE_LMFIT_HD double poly_value(const double* c, int P, double x) {
+  double s = c[0];
+  if (P > 1) s = fma(c[1], x, s);
+  double t0 = 1.0, t1 = x;
+  for (int k = 2; k < P; ++k) {
+    const double t2 = cheb_next(x, t1, t0);
+    s = fma(c[k], t2, s);
+    t0 = t1;
+    t1 = t2;
+  }
+  return s;
+}
+
+// poly_value at four abscissae, the same values: each coefficient is read once for the four.
+PAYNE_LMFIT_HD void poly4(const double* c, int P, const double* x, double* pv) {
+  double t0[4], t1[4];
+  const double c0 = c[0], c1 = P > 1 ? c[1] : 0.0;
+  for (int t = 0; t < 4; ++t) {
+    t0[t] = 1.0;
+    t1[t] = x[t];
+    pv[t] = P > 1 ? fma(c1, x[t], c0) : c0;
+  }
+  for (int k = 2; k < P; ++k) {
+    const double ck = c[k];
+    for (int t = 0; t < 4; ++t) {
+      const double t2 = cheb_next(x[t], t1[t], t0[t]);
+      pv[t] = fma(ck, t2, pv[t]);
+      t0[t] = t1[t];
+      t1[t] = t2;
+    }
+  }
+}
+
+// Row i of R at one pixel.
+PAYNE_LMFIT_HD double row_value(int i, int P, float m, float f, double x) { return i < P ? (double)m * cheb(i, x) : (double)f; }
+// The same from T = T_i(x) (cheb4).
+PAYNE_LMFIT_HD double row_from(int i, int P, float m, float f, double T) { return i < P ? (double)m * T : (double)f; }
+
+// What the first sums pass checks of a counting pixel.
+PAYNE_LMFIT_HD bool pixel_finite(float f, float m, double w) { return finite_f(f) && finite_f(m) && lm::finite(w); }
+
+// The tile of one star on the host in the kernel's pixel order (lmfit_core.hpp: tile_sums_host); mask == NULL: every counting
+// pixel is kept.  *count = the counting pixels, *bad = one of them is not finite.
+inline void tile_sums_host(const float* flux, const double* w, const float* model, const double* x, int n, int P, const unsigned* mask,
+                           double* G, int* count, bool* bad) {
+  for (int e = 0; e < lm::kTileSize; ++e) G[e] = 0.0;
+  const int gpw = lm::groups_per_wave(n), groups = lm::groups_of(n);
+  std::vector<double> acc((size_t)lm::kTileSize);
+  int cnt = 0;
+  bool nan = false;
+  for (int v = 0; v < lm::kWaves; ++v) {
+    for (double& e : acc) e = 0.0;
+    for (int grp = v * gpw; grp < (v + 1) * gpw && grp < groups; ++grp)
+      for (int t = 0; t < 4; ++t)
+        for (int q = 0; q < 4; ++q) {
+          const int p = lm::pixel_of(grp, q, t);
+          const bool counts = p < n && w[p < n ? p : 0] != 0.0;
+          if (!counts) continue;                                    // (both operands zero: the sums do not change)
+          ++cnt;
+          nan = nan || !pixel_finite(flux[p], model[p], w[p]);
+          if (mask && !((mask[p >> 5] >> (p & 31)) & 1u)) continue;
+          double a[lm::kTile], b[lm::kTile];
+          for (int i = 0; i <= P; ++i) lm::operand_pair(row_value(i, P, model[p], flux[p], x[p]), w[p], true, &a[i], &b[i]);
+          for (int i = 0; i <= P; ++i)
+            for (int j = 0; j <= P; ++j) acc[(size_t)(i * lm::kTile + j)] += a[i] * b[j];
+        }
+    for (int i = 0; i <= P; ++i)
+      for (int j = 0; j <= P; ++j) {
+        const int e = i * lm::kTile + j;
+        G[e] = v == 0 ? acc[(size_t)e] : G[e] + acc[(size_t)e];
+      }
+  }
+  *count = cnt;
+  *bad = nan;
+}
+
+// The coefficients behind the tile G [16][16] of `kept` pixels: c [P], *chisq.  work holds kWorkDoubles.  Returns the status:
+// NAN (the first pass met a value that is not finite), TOO_FEW, SINGULAR or OK; c and *chisq are written only with OK.
+PAYNE_LMFIT_HD int solve_star(const double* G, int P, int kept, bool bad, double* work, double* c, double* chisq) {
+  if (bad) return PAYNE_CONTFIT_NAN;
+  if (kept < P) return PAYNE_CONTFIT_TOO_FEW;
+  double* M = work;
+  double* S = work + P * P;
+  double* u = S + P;
+  for (int k = 0; k < P; ++k) {
+    const double d = G[k * lm::kTile + k];
+    if (!(d > 0.0) || !lm::finite(d)) return PAYNE_CONTFIT_SINGULAR;
+    S[k] = 1.0 / sqrt(d);
+  }
+  for (int i = 0; i < P; ++i) {
+    for (int j = 0; j < i; ++j) M[i * P + j] = G[i * lm::kTile + j] * S[i] * S[j];
+    M[i * P + i] = 1.0;
+    u[i] = G[i * lm::kTile + P] * S[i];
+  }
+  if (!lm::cholesky_solve(M, u, P)) return PAYNE_CONTFIT_SINGULAR;
+  for (int k = 0; k < P; ++k) {
+    u[k] *= S[k];
+    if (!lm::finite(u[k])) return PAYNE_CONTFIT_SINGULAR;
+  }
+  double total = 0.0;                                               // e^T G e, e = (c, -1); the upper triangle, mirrored
+  for (int i = 0; i <= P; ++i) {
+    const double ei = i < P ? u[i] : -1.0;
+    double row = 0.5 * ei * G[i * lm::kTile + i];
+    for (int j = i + 1; j <= P; ++j) row += (j < P ? u[j] : -1.0) * G[i * lm::kTile + j];
+    total += 2.0 * ei * row;
+  }
+  if (!lm::finite(total)) return PAYNE_CONTFIT_SINGULAR;
+  for (int k = 0; k < P; ++k) c[k] = u[k];
+  *chisq = total;
+  return PAYNE_CONTFIT_OK;
+}
+
+// The clipping scale s.
+PAYNE_LMFIT_HD double clip_scale(double chisq, int kept, int P, int rescale) {
+  if (!rescale) return 1.0;
+  const int dof = kept - P > 1 ? kept - P : 1;
+  return sqrt((chisq > 0.0 ? chisq : 0.0) / (double)dof);
+}
+
+// Is a counting pixel kept?  pv = p(x) there; lo = kappa_lo s, hi = kappa_hi s.
+PAYNE_LMFIT_HD bool keeps(float f, float m, double w, double pv, double lo, double hi) {
+  const double z = sqrt(w) * fma(-(double)m, pv, (double)f);
+  return z >= -lo && z <= hi;
+}
+
+// One pixel of the output rows.  True: a counting pixel whose polynomial is not positive (or not finite).
+PAYNE_LMFIT_HD bool out_pixel(float f, double w, double pv, bool counts, bool dropped, float* fo, double* wo) {
+  const bool ok = pv > 0.0 && lm::finite(pv);
+  *fo = ok ? (float)((double)f / pv) : 0.0f;
+  *wo = ok && counts && !dropped ? (w * pv) * pv : 0.0;
+  return counts && !ok;
+}
+
+// What the host walk leaves for the tests: per solve the tile [16][16] and the kept pixels [n].
+struct HostTrace {
+  std::vector<double> G;
+  std::vector<unsigned char> kept;
+};
+
+// One star on the host, pass by pass as payne_contfit_kernel takes them.  model == NULL: the star's model index is out of range.
+// G [256], work [kWorkDoubles], coef_lds [kMaxP] and mask [mask_words(n)] are the workspace (LDS in the kernel).  coef [P], chisq,
+// npix, status, rounds: the star's results; flux_out / w_out [n] or NULL.
+inline void fit_star_host(const float* flux, const double* w, const float* model, const double* x, int n, const payne_contfit_opts& o,
+                          double* G, double* work, double* coef_lds, unsigned* mask, double* coef, double* chisq, int* npix, int* status,
+                          int* rounds, float* flux_out, double* w_out, HostTrace* trace) {
+  const int P = o.P;
+  int st = model ? PAYNE_CONTFIT_OK : PAYNE_CONTFIT_BAD_MODEL, solves = 0, kept = 0;
+  double chi = 0.0;
+  bool masked = false;
+  const int chunks = (n + kChunk - 1) / kChunk;
+  if (model) {
+    for (int round = 0;; ++round) {
+      int cnt = 0;
+      bool bad = false;
+      tile_sums_host(flux, w, model, x, n, P, round > 0 ? mask : nullptr, G, &cnt, &bad);
+      if (round == 0) kept = cnt;
+      st = solve_star(G, P, kept, round == 0 && bad, work, coef_lds, &chi);
+      if (st != PAYNE_CONTFIT_OK) break;
+      ++solves;
+      if (trace) {
+        trace->G.insert(trace->G.end(), G, G + lm::kTileSize);
+        for (int p = 0; p < n; ++p) trace->kept.push_back(w[p] != 0.0 && (!masked || ((mask[p >> 5] >> (p & 31)) & 1u)) ? 1 : 0);
+      }
+      if (round == o.nclip) break;
+      const double s = clip_scale(chi, kept, P, o.rescale), lo = o.kappa_lo * s, hi = o.kappa_hi * s;
+      int now = 0, changed = 0;
+      for (int c = 0; c < chunks; c += 8) {                          // eight threads' chunks are one word
+        unsigned word = 0u, old = 0u;
+        for (int p = kChunk * c; p < kChunk * c + 32 && p < n; ++p) {
+          const bool counts = w[p] != 0.0;
+          const bool keep = counts && keeps(flux[p], model[p], w[p], poly_value(coef_lds, P, x[p]), lo, hi);
+          word |= (keep ? 1u : 0u) << (p & 31);
+          old |= (counts ? 1u : 0u) << (p & 31);
+          now += keep ? 1 : 0;
+        }
+        if (masked) old = mask[c >> 3];
+        for (int k = 0; k < 8; ++k) changed += ((old >> (4 * k)) & 15u) != ((word >> (4 * k)) & 15u) ? 1 : 0;
+        mask[c >> 3] = word;
+      }
+      masked = true;
+      if (!changed) break;
+      kept = now;
+    }
+  }
+  const bool fail = failed(st);
+  bool nonpos = false;
+  for (int p = 0; p < n; ++p) {
+    float fo = flux[p];
+    double wo = 0.0;
+    if (!fail) {
+      const bool counts = w[p] != 0.0;
+      const bool dropped = o.drop_clipped && masked && !((mask[p >> 5] >> (p & 31)) & 1u);
+      nonpos = out_pixel(flux[p], w[p], poly_value(coef_lds, P, x[p]), counts, dropped, &fo, &wo) || nonpos;
+    }
+    if (flux_out) flux_out[p] = fo;
+    if (w_out) w_out[p] = wo;
+  }
+  if (!fail && nonpos) st = PAYNE_CONTFIT_NONPOSITIVE;
+  for (int k = 0; k < P; ++k) coef[k] = fail ? (double)NAN : coef_lds[k];
+  *chisq = fail ? (double)NAN : chi;
+  *npix = kept;
+  *status = st;
+  *rounds = solves;
+}
+
+}  // namespace contfit
+}  // namespace payne

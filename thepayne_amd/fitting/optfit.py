@@ -294,6 +294,70 @@ class OptFit(object):
             tm["iterations"] += it
         return res
 
+    def model_spectra(self, pars):
+        """The model ``fit`` minimises at pars [N, 8] (getspec's columns): payne_specjac_eval's y through payne_smooth_batch, fp32
+        [N, nobs] on the device."""
+        P = self.predictor
+        eng = P.anns.engine
+        pars = np.atleast_2d(np.asarray(pars, dtype=np.float64))
+        P._bind(self.obs_wave)
+        out = eng.torch.empty((len(pars), len(self.obs_wave)), dtype=eng.torch.float32, device=eng.device)
+        cols = fitted_columns(self.n_labels, False)
+        for s in range(0, len(pars), eng.b_max):
+            blk = pars[s:s + eng.b_max]
+            y, _ = P._jacobian().eval(blk[:, cols])
+            th = np.full((len(blk), eng.ncols), np.nan)
+            th[:, :8] = blk
+            out[s:s + eng.b_max] = eng.smooth_batch(y, th, stage=2)
+        return out
+
+    def fit_with_continuum(self, flux, eflux, start, npoly=4, rounds=3, clip=None, **fit_kwargs):
+        """Labels and a continuum polynomial of ``npoly`` Chebyshev coefficients per star, by block-coordinate descent on
+        chi^2 = sum w (flux - model(x) p)^2.  Each of ``rounds`` rounds fits the polynomial against the model at the current
+        parameters (``contfit.ContinuumFit.fit`` on ``model_spectra``: the linear block, solved exactly) and then runs ``fit`` on the
+        normalised flux and errors, started from the round before: sum w (f - m p)^2 = sum (w p^2) (f / p - m)^2, so both blocks
+        descend the same chi^2.  ``clip``: dict(nclip, kappa, rescale, drop_clipped) for the polynomial's kappa-sigma clipping.
+        Returns ``fit``'s dict of the last round plus ``coef`` [N, npoly] (``polycalc``'s), ``cont_status`` (``_lib.CONTFIT_*``) and
+        ``chisq_rounds`` [N, rounds] (the label fit's chi^2 of every round).  A star whose continuum status is not OK / NONPOSITIVE
+        in some round keeps its last valid result from there on, and that status in ``cont_status``; one that never had a valid
+        continuum has status NAN and NaN ``pars`` in the fitted columns.  ``fit_kwargs`` go to ``fit``."""
+        from .contfit import ContinuumFit
+        if int(rounds) < 1:
+            raise ValueError("rounds must be at least 1")
+        flux, eflux, start = check_fit_args(flux, eflux, start, len(self.obs_wave), self.n_labels, self.predictor.anns.xmin, self.predictor.anns.xmax,
+                                            **{k: v for k, v in fit_kwargs.items() if k not in ("lsf", "timing")})[:3]
+        fit_vrad = bool(fit_kwargs.get("fit_vrad", False))
+        cols = fitted_columns(self.n_labels, fit_vrad)
+        N, K = flux.shape[0], len(cols)
+        cont = ContinuumFit(self.obs_wave, npoly=npoly, device=self.predictor.anns.engine.device, **(clip or {}))
+        pars = start.copy()
+        out = dict(pars=start.copy(), chisq=np.full(N, np.nan), npix=np.zeros(N, dtype=np.int64), fisher=np.full((N, K, K), np.nan),
+                   status=np.full(N, _lib.LMFIT_NAN, dtype=np.int32), niter=np.zeros(N, dtype=np.int32), at_bound=np.zeros(N, dtype=np.uint32),
+                   labels=self.labels(fit_vrad), err=np.full((N, K), np.nan), coef=np.full((N, int(npoly)), np.nan),
+                   cont_status=np.full(N, _lib.CONTFIT_OK, dtype=np.int32), chisq_rounds=np.full((N, int(rounds)), np.nan))
+        out["pars"][:, cols] = np.nan
+        alive = np.ones(N, dtype=bool)
+        for r in range(int(rounds)):
+            sel = np.flatnonzero(alive)
+            if len(sel) == 0:
+                break
+            c = cont.fit(flux[sel], eflux[sel], self.model_spectra(pars[sel]))
+            c = {k: v.cpu().numpy() for k, v in c.items()}
+            good = (c["status"] == _lib.CONTFIT_OK) | (c["status"] == _lib.CONTFIT_NONPOSITIVE)
+            out["cont_status"][sel] = c["status"]
+            alive[sel[~good]] = False
+            if not good.any():
+                continue
+            dst = sel[good]
+            res = self.fit(c["flux"][good], c["eflux"][good], pars[dst], **fit_kwargs)
+            for name in ("pars", "chisq", "npix", "fisher", "status", "niter", "at_bound", "err"):
+                out[name][dst] = res[name]
+            out["coef"][dst] = c["coef"][good]
+            out["chisq_rounds"][dst, r] = res["chisq"]
+            ok = (res["status"] != _lib.LMFIT_NAN) & (res["status"] != _lib.LMFIT_SINGULAR)
+            pars[dst[ok]] = res["pars"][ok]
+        return out
+
     def fit_from_bank(self, flux, eflux, bank, topk=1, **fit_kwargs):
         """``fit`` started from the ``topk`` templates of ``bank`` (a ``tmatch.TemplateBank`` on this fitter's ``obs_wave``) that
         match each star best: the template's labels, Vrot, Inst_R and Vrad are the start (``fit_vrad`` then refines Vrad).  One
