@@ -528,6 +528,15 @@ int payne_fisher_batch(int device, const float* rows_dev, int ld, int K, int n, 
  * Rows and flux are read 16 bytes a lane where ld and ld_f are multiples of four and the pointers 16-byte aligned, element by
  * element otherwise (the same bits).
  *   PAYNE_E_INVALID      null handle, n < 1, ld < n, ld_f < n, null rows_dev / flux_dev / w_dev with B > 0
+ * payne_lmfit_update_poly: the update for a model multiplied by a continuum polynomial that is fitted with it.  The handle's K
+ * parameters are Km = K - P of the caller's model m (Km >= 0) and then P Chebyshev coefficients c of p(x) = sum_j c_j T_j(x), in
+ * polycalc's basis on payne_contfit_batch's abscissa x_dev, DEVICE fp64 [n], shared by all stars.  rows_dev is [B][1 + Km][ld], the
+ * un-normalised model and its Km derivatives as payne_lmfit_update takes them; the coefficients are read from the star's x_trial.
+ * The K + 1 rows of R are formed in registers and never stored: p dm/dtheta_i (i < Km), m T_j(x) (i = Km + j) and flux - m p
+ * (i = K), p and T_j in fp64 by the recurrence T_k = fma(2 x, T_k-1, -T_k-2), p = fma(c_k, T_k, p) with k ascending.  Pixel order,
+ * operand map, the handling of w == 0, NaN and pixels beyond n, both load forms (x_dev 16-byte aligned too for the first) and the
+ * step that follows are payne_lmfit_update's, over all K parameters; a star's bits do not depend on its batch.  |x| <= 1 is assumed.
+ *   PAYNE_E_INVALID      as payne_lmfit_update, and P < 1, P > K, null x_dev with B > 0
  * payne_lmfit_result: DEVICE pointers, any may be NULL: x_best fp64 [B][K], chisq fp64 [B] (of x_best), A fp64 [B][K][K] and g fp64
  * [B][K] (at x_best), lambda fp64 [B], status int [B], niter int [B] (evaluations), at_bound unsigned [B].  Copies on `stream`.
  *   PAYNE_E_INVALID      null handle
@@ -552,6 +561,8 @@ int payne_lmfit_begin(payne_lmfit* h, const double* x0_dev, const double* lo, co
 double* payne_lmfit_trial(payne_lmfit* h);
 int payne_lmfit_update(payne_lmfit* h, const float* rows_dev, int ld, const float* flux_dev, const double* w_dev, int ld_f, int n,
                        void* stream);
+int payne_lmfit_update_poly(payne_lmfit* h, int P, const float* rows_dev, int ld, const float* flux_dev, const double* w_dev, int ld_f,
+                            const double* x_dev, int n, void* stream);
 int payne_lmfit_result(payne_lmfit* h, double* x_best, double* chisq, double* A, double* g, double* lambda, int* status, int* niter,
                        unsigned* at_bound, void* stream);
 void payne_lmfit_destroy(payne_lmfit* h);

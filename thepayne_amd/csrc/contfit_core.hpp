@@ -41,72 +41,12 @@ PAYNE_LMFIT_HD int mask_words(int n) { return (n + 31) / 32; }
 PAYNE_LMFIT_HD bool finite_f(float v) { return lm::finite((double)v); }
 PAYNE_LMFIT_HD bool failed(int status) { return status != PAYNE_CONTFIT_OK && status != PAYNE_CONTFIT_NONPOSITIVE; }
 
-// The three-term recurrence, written once: T_k = 2 x T_k-1 - T_k-2.
-PAYNE_LMFIT_HD double cheb_next(double x, double t1, double t0) { return fma(2.0 * x, t1, -t0); }
-
-// T_i(x).
-PAYNE_LMFIT_HD double cheb(int i, double x) {
-  if (i == 0) return 1.0;
-  double t0 = 1.0, t1 = x;
-  for (int k = 2; k <= i; ++k) {
-    const double t2 = cheb_next(x, t1, t0);
-    t0 = t1;
-    t1 = t2;
-  }
-  return t1;
-}
-
-// T_i at four abscissae, the same values: one loop for the four, and a trip count (P) that every lane of a wave shares -- the lanes
-// differ only in the step they keep.  (Four calls of cheb are four loops whose length differs from lane to lane; measured, NOTES.md.)
-PAYNE_LMFIT_HD void cheb4(int i, int P, const double* x, double* T) {
-  double t0[4], t1[4];
-  for (int t = 0; t < 4; ++t) {
-    t0[t] = 1.0;
-    t1[t] = x[t];
-    T[t] = i == 0 ? 1.0 : x[t];
-  }
-  for (int k = 2; k < P; ++k)
-    for (int t = 0; t < 4; ++t) {
-      const double t2 = cheb_next(x[t], t1[t], t0[t]);
-      t0[t] = t1[t];
-      t1[t] = t2;
-      T[t] = k == i ? t2 : T[t];
-    }
-}
-
-// p(x) = sum_j c_j T_j(x), j ascending, on the same recurrence.
-PAYNE_LMFIT_HD double poly_value(const double* c, int P, double x) {
-  double s = c[0];
-  if (P > 1) s = fma(c[1], x, s);
-  double t0 = 1.0, t1 = x;
-  for (int k = 2; k < P; ++k) {
-    const double t2 = cheb_next(x, t1, t0);
-    s = fma(c[k], t2, s);
-    t0 = t1;
-    t1 = t2;
-  }
-  return s;
-}
-
-// poly_value at four abscissae, the same values: each coefficient is read once for the four.
-PAYNE_LMFIT_HD void poly4(const double* c, int P, const double* x, double* pv) {
-  double t0[4], t1[4];
-  const double c0 = c[0], c1 = P > 1 ? c[1] : 0.0;
-  for (int t = 0; t < 4; ++t) {
-    t0[t] = 1.0;
-    t1[t] = x[t];
-    pv[t] = P > 1 ? fma(c1, x[t], c0) : c0;
-  }
-  for (int k = 2; k < P; ++k) {
-    const double ck = c[k];
-    for (int t = 0; t < 4; ++t) {
-      const double t2 = cheb_next(x[t], t1[t], t0[t]);
-      pv[t] = fma(ck, t2, pv[t]);
-      t0[t] = t1[t];
-      t1[t] = t2;
-    }
-  }
-}
+// The Chebyshev series (lmfit_core.hpp: the recurrence, written once, is also payne_lmfit_update_poly's).
+using lm::cheb_next;
+using lm::cheb;
+using lm::cheb4;
+using lm::poly_value;
+using lm::poly4;
 
 // Row i of R at one pixel.
 PAYNE_LMFIT_HD double row_value(int i, int P, float m, float f, double x) { return i < P ? (double)m * cheb(i, x) : (double)f; }

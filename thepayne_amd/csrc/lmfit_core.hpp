@@ -9,6 +9,9 @@
 //            fp32) and feeds them to four consecutive matrix instructions: instruction t sums pixels p0 + 4 k + t, k = 0..3
 //            (A[i][k] = R[i][p], B[k][j] = R[j][p] w[p], the same lane's value times w).  Wave v of the workgroup's four owns the
 //            groups [v * gpw, (v + 1) * gpw), gpw = ceil(groups / 4); the four partial tiles are added in wave order.
+//   poly     payne_lmfit_update_poly: the same tile for a model times a Chebyshev series whose coefficients are the last P parameters,
+//            R = [p dm/dtheta ; m T_j ; flux - m p] formed from the caller's 1 + Km rows (below: series4, operand_poly,
+//            tile_sums_poly_host; tests/emul/lmfit_poly_emul.cpp).  The series' recurrence is the one contfit_core.hpp uses.
 //   zero w   a pixel with w == 0 (or beyond n) has both operands replaced by zero by a select: the rows may hold NaN there.
 //   step     update_star below: decide, solve, next trial, stop (include/payne_hip.h states the rules).
 #pragma once
@@ -85,6 +88,154 @@ inline void tile_sums_host(const float* rows, long long ld, const float* flux, c
       }
       G[i * kTile + j] = total;
     }
+}
+
+// ---- Chebyshev series (contfit_core.hpp uses these under its own names) -----------------------------------------------------
+// The three-term recurrence, written once: T_k = 2 x T_k-1 - T_k-2.
+PAYNE_LMFIT_HD double cheb_next(double x, double t1, double t0) { return fma(2.0 * x, t1, -t0); }
+
+// T_i(x).
+PAYNE_LMFIT_HD double cheb(int i, double x) {
+  if (i == 0) return 1.0;
+  double t0 = 1.0, t1 = x;
+  for (int k = 2; k <= i; ++k) {
+    const double t2 = cheb_next(x, t1, t0);
+    t0 = t1;
+    t1 = t2;
+  }
+  return t1;
+}
+
+// T_i at four abscissae, the same values: one loop for the four, and a trip count (P) that every lane of a wave shares -- the lanes
+// differ only in the step they keep.  (Four calls of cheb are four loops whose length differs from lane to lane; measured, NOTES.md.)
+PAYNE_LMFIT_HD void cheb4(int i, int P, const double* x, double* T) {
+  double t0[4], t1[4];
+  for (int t = 0; t < 4; ++t) {
+    t0[t] = 1.0;
+    t1[t] = x[t];
+    T[t] = i == 0 ? 1.0 : x[t];
+  }
+  for (int k = 2; k < P; ++k)
+    for (int t = 0; t < 4; ++t) {
+      const double t2 = cheb_next(x[t], t1[t], t0[t]);
+      t0[t] = t1[t];
+      t1[t] = t2;
+      T[t] = k == i ? t2 : T[t];
+    }
+}
+
+// p(x) = sum_j c_j T_j(x), j ascending, on the same recurrence.
+PAYNE_LMFIT_HD double poly_value(const double* c, int P, double x) {
+  double s = c[0];
+  if (P > 1) s = fma(c[1], x, s);
+  double t0 = 1.0, t1 = x;
+  for (int k = 2; k < P; ++k) {
+    const double t2 = cheb_next(x, t1, t0);
+    s = fma(c[k], t2, s);
+    t0 = t1;
+    t1 = t2;
+  }
+  return s;
+}
+
+// poly_value at four abscissae, the same values: each coefficient is read once for the four.
+PAYNE_LMFIT_HD void poly4(const double* c, int P, const double* x, double* pv) {
+  double t0[4], t1[4];
+  const double c0 = c[0], c1 = P > 1 ? c[1] : 0.0;
+  for (int t = 0; t < 4; ++t) {
+    t0[t] = 1.0;
+    t1[t] = x[t];
+    pv[t] = P > 1 ? fma(c1, x[t], c0) : c0;
+  }
+  for (int k = 2; k < P; ++k) {
+    const double ck = c[k];
+    for (int t = 0; t < 4; ++t) {
+      const double t2 = cheb_next(x[t], t1[t], t0[t]);
+      pv[t] = fma(ck, t2, pv[t]);
+      t0[t] = t1[t];
+      t1[t] = t2;
+    }
+  }
+}
+
+// ---- the sums with a continuum polynomial (payne_lmfit_update_poly) -----------------------------------------------------------
+// K = Km + P parameters: Km of the caller's model m, then the P Chebyshev coefficients c of p(x) = sum_j c_j T_j(x) that multiplies
+// it.  The rows of R at one pixel, from the fp32 values of the caller's 1 + Km rows, the flux f and x, in fp64:
+//   i < Km        p dm/dtheta_i       one rounded product
+//   Km <= i < K   m T_{i-Km}(x)       one rounded product
+//   i == K        f - m p             one fma
+// A lane of row i therefore needs one series in x: p (row i < Km or i == K), or T_j, which is the series of the unit vector e_j --
+// fma(1, T_j, 0) = T_j and fma(0, T_k, s) = s are exact while every T_k is finite, which |x| <= 1 ensures.  So every lane runs
+// poly_value's loop on its own coefficients, P - 2 steps whatever its row, and the values are poly_value's and cheb's.
+// j: the lane's T_j, or -1 where it wants p.
+PAYNE_LMFIT_HD int series_index(int i, int Km, int K) { return i >= Km && i < K ? i - Km : -1; }
+PAYNE_LMFIT_HD double series_coef(const double* c, int j, int k) { return j < 0 ? c[k] : (k == j ? 1.0 : 0.0); }
+
+// The lane's series at one abscissa.
+PAYNE_LMFIT_HD double series_value(const double* c, int j, int P, double x) {
+  double s = series_coef(c, j, 0);
+  if (P > 1) s = fma(series_coef(c, j, 1), x, s);
+  double t0 = 1.0, t1 = x;
+  for (int k = 2; k < P; ++k) {
+    const double t2 = cheb_next(x, t1, t0);
+    s = fma(series_coef(c, j, k), t2, s);
+    t0 = t1;
+    t1 = t2;
+  }
+  return s;
+}
+
+// series_value at four abscissae, the same values (poly4's loop).
+PAYNE_LMFIT_HD void series4(const double* c, int j, int P, const double* x, double* sv) {
+  double t0[4], t1[4];
+  const double c0 = series_coef(c, j, 0), c1 = P > 1 ? series_coef(c, j, 1) : 0.0;
+  for (int t = 0; t < 4; ++t) {
+    t0[t] = 1.0;
+    t1[t] = x[t];
+    sv[t] = P > 1 ? fma(c1, x[t], c0) : c0;
+  }
+  for (int k = 2; k < P; ++k) {
+    const double ck = series_coef(c, j, k);
+    for (int t = 0; t < 4; ++t) {
+      const double t2 = cheb_next(x[t], t1[t], t0[t]);
+      sv[t] = fma(ck, t2, sv[t]);
+      t0[t] = t1[t];
+      t1[t] = t2;
+    }
+  }
+}
+
+// Row i of R at one pixel: `a` of rows[1 + i] for i < Km, of row 0 (the model) otherwise; s the lane's series there.
+PAYNE_LMFIT_HD double operand_poly(int i, int K, float a, float f, double s) { return i < K ? (double)a * s : fma(-(double)a, s, (double)f); }
+
+// The tile on the host in the kernel's pixel order (tile_sums_host): G [16][16] of one star.  rows [1 + Km][ld], c [P], x [n].
+inline void tile_sums_poly_host(const float* rows, long long ld, const float* flux, const double* w, const double* x, int n, int Km, int P,
+                                const double* c, double* G) {
+  const int K = Km + P;
+  for (int e = 0; e < kTileSize; ++e) G[e] = 0.0;
+  const int gpw = groups_per_wave(n), groups = groups_of(n);
+  double acc[kTileSize];
+  for (int v = 0; v < kWaves; ++v) {
+    for (int e = 0; e < kTileSize; ++e) acc[e] = 0.0;
+    for (int grp = v * gpw; grp < (v + 1) * gpw && grp < groups; ++grp)
+      for (int t = 0; t < 4; ++t)
+        for (int q = 0; q < 4; ++q) {
+          const int p = pixel_of(grp, q, t);
+          if (!(p < n && w[p < n ? p : 0] != 0.0)) continue;         // (both operands zero: the sums do not change)
+          double a[kTile], b[kTile];
+          for (int i = 0; i <= K; ++i) {
+            const float ai = rows[(size_t)(i < Km ? 1 + i : 0) * (size_t)ld + (size_t)p];
+            operand_pair(operand_poly(i, K, ai, flux[p], series_value(c, series_index(i, Km, K), P, x[p])), w[p], true, &a[i], &b[i]);
+          }
+          for (int i = 0; i <= K; ++i)
+            for (int j = 0; j <= K; ++j) acc[i * kTile + j] += a[i] * b[j];
+        }
+    for (int i = 0; i <= K; ++i)
+      for (int j = 0; j <= K; ++j) {
+        const int e = i * kTile + j;
+        G[e] = v == 0 ? acc[e] : G[e] + acc[e];
+      }
+  }
 }
 
 // ---- one star's state -------------------------------------------------------------------------------------------------------

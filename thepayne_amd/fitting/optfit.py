@@ -17,6 +17,9 @@ central difference of the broadened model at Vrad +- ``vrad_step``).  Vrot and I
 Vmic too for a four-label network.  ``fisher`` is the normal matrix J^T W J at the solution and ``err`` its Cramer-Rao bounds
 (``forecast.crlb_from_fisher``): conditional on the fixed parameters, as ``Forecast``'s are.  A continuum network and an LSF vector
 are not supported (``PayneSpecPredict.getgrad`` explains why).
+
+``OptFit.fit_joint`` fits a continuum polynomial (``polycalc``'s Chebyshev coefficients) along with these parameters, in the same
+loop: its update, payne_lmfit_update_poly, forms the rows of model x polynomial in registers.
 """
 import ctypes as C
 
@@ -27,7 +30,7 @@ from ..engine import THETA_SPEC_COLS
 from ..predict._spec import PayneSpecPredict, smooth_rows
 from .forecast import crlb_from_fisher, weights_from_errors
 
-__all__ = ["OptFit", "check_fit_args", "LM_DEFAULTS", "VRAD_BOUND"]
+__all__ = ["OptFit", "check_fit_args", "check_joint_args", "LM_DEFAULTS", "VRAD_BOUND", "COEF_BOUND"]
 
 LM_DEFAULTS = dict(lambda0=1e-3, down=10.0, up=10.0, lambda_min=1e-12, lambda_max=1e8, xtol=1e-3, maxiter=50)
 VRAD_BOUND = 500.0                                   # km/s: the default box of a fitted Vrad
@@ -90,6 +93,43 @@ def check_fit_args(flux, eflux, start, nobs, n_labels, xmin, xmax, fit_vrad=Fals
     return flux, eflux, start, lo, hi, o
 
 
+COEF_BOUND = 1e30                                    # the default box of a fitted Chebyshev coefficient: finite, as payne_lmfit_begin requires
+
+
+def check_joint_args(flux, eflux, start, nobs, n_labels, xmin, xmax, npoly=4, coef=None, clip=None, coef_bounds=None, **fit_args):
+    """What ``OptFit.fit_joint`` checks before anything reaches the device: ``check_fit_args`` on ``fit``'s arguments, then the
+    polynomial's.  Returns (flux, eflux, start, lo [K], hi [K], opts dict, coef fp64 [N, npoly] or None, clip dict) with
+    K = K_m + npoly, the coefficients' box behind the fitted columns'."""
+    flux, eflux, start, lo, hi, o = check_fit_args(flux, eflux, start, nobs, n_labels, xmin, xmax, **fit_args)
+    if isinstance(npoly, bool) or int(npoly) != npoly or int(npoly) < 1:
+        raise ValueError("npoly must be an integer >= 1, got %r" % (npoly,))
+    P, Km = int(npoly), len(lo)
+    if Km + P > _lib.LMFIT_MAX_K:
+        raise ValueError("%d fitted columns and npoly = %d are %d parameters; at most %d (one 16 x 16 tile holds a star's normal equations)"
+                         % (Km, P, Km + P, _lib.LMFIT_MAX_K))
+    if coef is not None:
+        coef = np.atleast_2d(np.asarray(coef.cpu() if hasattr(coef, "cpu") else coef, dtype=np.float64))     # (ContinuumFit's may be a device tensor)
+        if coef.shape != (flux.shape[0], P):
+            raise ValueError("coef must be [%d, %d], got %s" % (flux.shape[0], P, coef.shape))
+        if not np.all(np.isfinite(coef)):
+            raise ValueError("coef is not finite")
+    clip = dict(clip or {})
+    unknown = sorted(set(clip) - {"nclip", "kappa", "rescale"})
+    if unknown:
+        raise ValueError("clip: unknown keys %s (have nclip, kappa, rescale)" % unknown)
+    if coef is not None and clip:
+        raise ValueError("clip belongs to the starting continuum fit, which coef replaces")
+    if coef_bounds is None:
+        cb = np.tile([-COEF_BOUND, COEF_BOUND], (P, 1))
+    else:
+        cb = np.asarray(coef_bounds, dtype=np.float64)
+        if cb.shape != (P, 2):
+            raise ValueError("coef_bounds must be [%d, 2], got %s" % (P, cb.shape))
+        if not (np.all(np.isfinite(cb)) and np.all(cb[:, 0] < cb[:, 1])):
+            raise ValueError("coef_bounds: lo < hi, both finite, for every coefficient")
+    return flux, eflux, start, np.concatenate([lo, cb[:, 0]]), np.concatenate([hi, cb[:, 1]]), o, coef, clip
+
+
 class _DeviceArray(object):
     """A device pointer the library owns, as torch reads it (``torch.as_tensor``)."""
 
@@ -146,6 +186,24 @@ class LMHandle(object):
         rc = self.lib.payne_lmfit_update(self._h, rows.data_ptr(), n, flux.data_ptr(), w.data_ptr(), n, n, self._stream())
         if rc != 0:
             raise RuntimeError("payne_lmfit_update failed (%d)" % rc)
+
+    def update_poly(self, rows, flux, w, x, P):
+        """The update for model x polynomial, the handle's last P parameters the Chebyshev coefficients (payne_lmfit_update_poly):
+        rows fp32 [B, 1 + K - P, n] (the un-normalised model, then its derivatives), flux fp32 [B, n], w fp64 [B, n], x fp64 [n]
+        (``contfit.abscissa``): device tensors."""
+        B, n, P = self.B, rows.shape[-1], int(P)
+        if not 1 <= P <= self.K:
+            raise ValueError("P must be 1 .. %d, got %d" % (self.K, P))
+        if tuple(rows.shape) != (B, 1 + self.K - P, n) or tuple(flux.shape) != (B, n) or tuple(w.shape) != (B, n) or tuple(x.shape) != (n,):
+            raise ValueError("rows [%d, %d, n], flux and w [%d, n], x [n]; got %s, %s, %s, %s"
+                             % (B, 1 + self.K - P, B, tuple(rows.shape), tuple(flux.shape), tuple(w.shape), tuple(x.shape)))
+        torch = self.torch
+        if rows.dtype != torch.float32 or flux.dtype != torch.float32 or w.dtype != torch.float64 or x.dtype != torch.float64 \
+                or not (rows.is_contiguous() and flux.is_contiguous() and w.is_contiguous() and x.is_contiguous()):
+            raise ValueError("rows and flux contiguous fp32, w and x contiguous fp64")
+        rc = self.lib.payne_lmfit_update_poly(self._h, P, rows.data_ptr(), n, flux.data_ptr(), w.data_ptr(), n, x.data_ptr(), n, self._stream())
+        if rc != 0:
+            raise RuntimeError("payne_lmfit_update_poly failed (%d)" % rc)
 
     def status(self):
         torch = self.torch
@@ -237,7 +295,9 @@ class OptFit(object):
         out["err"] = crlb_from_fisher(out["fisher"])
         return out
 
-    def _fit_block(self, handle, flux, w, start, cols, lo, hi, fit_vrad, vrad_step, check_every, maxiter):
+    def _fit_block(self, handle, flux, w, start, cols, lo, hi, fit_vrad, vrad_step, check_every, maxiter, coef=None, x=None):
+        """One block of stars through the handle.  ``coef`` [nb, P] and ``x``: the handle's parameters are the fitted columns and then
+        the coefficients, and the update is ``update_poly`` on the abscissa ``x`` (``fit_joint``)."""
         P = self.predictor
         eng, D, jac_net = P.anns.engine, self.n_labels, P._jacobian()
         torch = eng.torch
@@ -245,7 +305,7 @@ class OptFit(object):
         dev = eng.device
         flux_d = torch.as_tensor(np.ascontiguousarray(flux)).to(dev)
         w_d = torch.as_tensor(np.ascontiguousarray(w)).to(dev)
-        handle.begin(start[:, cols], lo, hi)
+        handle.begin(start[:, cols] if coef is None else np.concatenate([start[:, cols], coef], axis=1), lo, hi)
         xt = handle.trial()
         # the theta blocks, uploaded once: the model's [nb], the derivative rows' [nb * D], and Vrad +- step's [2 nb]
         th = np.full((nb, eng.ncols), np.nan)
@@ -266,7 +326,7 @@ class OptFit(object):
         while it < maxiter:
             it += 1
             mark()
-            labels = xt[:, :D] if fit_vrad else xt
+            labels = xt[:, :D] if handle.K > D else xt
             y, jac = jac_net.eval(labels)
             mark()
             if fit_vrad:
@@ -280,7 +340,10 @@ class OptFit(object):
             rows[:, 0] = eng.smooth_batch(y, th_y, stage=2)
             rows[:, 1:1 + D] = smooth_rows(eng, jac.reshape(nb * D, -1), th_j, 2).reshape(nb, D, nobs)
             mark()
-            handle.update(rows, flux_d, w_d)
+            if coef is None:
+                handle.update(rows, flux_d, w_d)
+            else:
+                handle.update_poly(rows, flux_d, w_d, x, coef.shape[1])
             mark()
             if it % check_every == 0 and not bool((handle.status() == _lib.LMFIT_RUNNING).any().item()):
                 break
@@ -320,7 +383,11 @@ class OptFit(object):
         Returns ``fit``'s dict of the last round plus ``coef`` [N, npoly] (``polycalc``'s), ``cont_status`` (``_lib.CONTFIT_*``) and
         ``chisq_rounds`` [N, rounds] (the label fit's chi^2 of every round).  A star whose continuum status is not OK / NONPOSITIVE
         in some round keeps its last valid result from there on, and that status in ``cont_status``; one that never had a valid
-        continuum has status NAN and NaN ``pars`` in the fitted columns.  ``fit_kwargs`` go to ``fit``."""
+        continuum has status NAN and NaN ``pars`` in the fitted columns.  ``fit_kwargs`` go to ``fit``.
+
+        The alternation converges linearly and slowly (NOTES.md: about 40 rounds to come within 0.01 sigma of its fixed point);
+        ``fit_joint`` minimises the same chi^2 over labels and coefficients in one Levenberg-Marquardt fit and is the method to
+        prefer for up to 15 parameters."""
         from .contfit import ContinuumFit
         if int(rounds) < 1:
             raise ValueError("rounds must be at least 1")
@@ -356,6 +423,75 @@ class OptFit(object):
             out["chisq_rounds"][dst, r] = res["chisq"]
             ok = (res["status"] != _lib.LMFIT_NAN) & (res["status"] != _lib.LMFIT_SINGULAR)
             pars[dst[ok]] = res["pars"][ok]
+        return out
+
+    def fit_joint(self, flux, eflux, start, npoly=4, coef=None, clip=None, fit_vrad=False, bounds=None, coef_bounds=None, vrad_step=0.25,
+                  check_every=4, lsf=None, timing=False, **opts):
+        """Labels (Vrad with ``fit_vrad``) and a continuum polynomial of ``npoly`` Chebyshev coefficients per star in ONE
+        Levenberg-Marquardt fit of chi^2 = sum w (flux - model(x) p)^2 over all K = K_m + npoly <= 15 parameters: what
+        ``fit_with_continuum`` approaches by alternation, at the cost of one ``fit``.  An iteration is ``fit``'s three enqueued
+        steps with the update replaced by payne_lmfit_update_poly, which forms the rows p dm/dtheta, m T_j and flux - m p in
+        registers; nothing is normalised and no row is stored.
+
+        ``coef`` [N, npoly]: the starting coefficients (``polycalc``'s); by default one ``ContinuumFit.fit`` against
+        ``model_spectra(start)``, with ``clip`` (dict(nclip, kappa, rescale)) its kappa-sigma clipping, and the pixels its last solve
+        dropped do not count in the joint fit.  A star whose continuum status is not OK / NONPOSITIVE gets status NAN and NaN
+        results.  ``coef_bounds`` [npoly, 2]: the coefficients' box, finite; +-1e30 by default.  The other arguments are ``fit``'s.
+
+        Returns ``fit``'s dict with ``labels`` (the fitted columns, then pc_0 ..), ``fisher`` [N, K, K], ``err`` [N, K] and
+        ``at_bound`` over all K parameters -- ``err`` is sqrt(diag(inv(fisher))), so the labels' entries are marginalised over the
+        polynomial -- plus ``coef`` [N, npoly] and ``cont_status`` (``_lib.CONTFIT_*``; OK where ``coef`` was given)."""
+        if lsf is not None:
+            raise NotImplementedError("OptFit with an LSF vector: the rows are not pushed through it (PayneSpecPredict.getgrad)")
+        Pr = self.predictor
+        anns, eng, D = Pr.anns, Pr.anns.engine, self.n_labels
+        flux, eflux, start, lo, hi, o, coef, clip = check_joint_args(flux, eflux, start, len(self.obs_wave), D, anns.xmin, anns.xmax, npoly=npoly, coef=coef,
+                                                                     clip=clip, fit_vrad=fit_vrad, bounds=bounds, coef_bounds=coef_bounds,
+                                                                     vrad_step=vrad_step, check_every=check_every, **opts)
+        from .contfit import ContinuumFit, abscissa
+        torch = eng.torch
+        N, nobs = flux.shape
+        cols = fitted_columns(D, fit_vrad)
+        Km, P = len(cols), int(npoly)
+        K = Km + P
+        w = weights_from_errors(eflux)
+        cont_status = np.full(N, _lib.CONTFIT_OK, dtype=np.int32)
+        x = abscissa(self.obs_wave)
+        if coef is None:
+            cont = ContinuumFit(self.obs_wave, npoly=P, device=eng.device, drop_clipped=True, **clip)
+            c = cont.fit(flux, eflux, self.model_spectra(start), normalise=bool(clip))
+            c = {k: v.cpu().numpy() for k, v in c.items()}            # (a device model gives device tensors)
+            coef, cont_status = c["coef"], c["status"].astype(np.int32)
+            if clip:                                                  # a counting pixel whose weight came back 0 under a positive polynomial was clipped
+                w = np.where((c["weights"] == 0.0) & (np.polynomial.chebyshev.chebval(x, np.nan_to_num(coef).T) > 0.0), 0.0, w)
+        good = (cont_status == _lib.CONTFIT_OK) | (cont_status == _lib.CONTFIT_NONPOSITIVE)
+        out = dict(pars=start.copy(), chisq=np.full(N, np.nan), npix=(w != 0.0).sum(axis=1), fisher=np.full((N, K, K), np.nan),
+                   status=np.full(N, _lib.LMFIT_NAN, dtype=np.int32), niter=np.zeros(N, dtype=np.int32), at_bound=np.zeros(N, dtype=np.uint32),
+                   labels=self.labels(fit_vrad) + ["pc_%d" % j for j in range(P)], coef=np.full((N, P), np.nan), cont_status=cont_status)
+        out["pars"][:, cols] = np.nan
+        Pr._bind(self.obs_wave)
+        step = max(1, eng.b_max // (1 + Km + 2 * int(bool(fit_vrad))))
+        sel = np.flatnonzero(good)
+        self.timing = dict(network=0.0, broadening=0.0, update=0.0, iterations=0) if timing else None
+        if len(sel):
+            handle = LMHandle(K, min(step, len(sel)), eng.device, **o)
+            x_d = torch.as_tensor(x).to(eng.device)
+            try:
+                for s in range(0, len(sel), step):
+                    idx = sel[s:s + step]
+                    res = self._fit_block(handle, flux[idx], w[idx], start[idx], cols, lo, hi, bool(fit_vrad), float(vrad_step), int(check_every),
+                                          int(o["maxiter"]), coef=np.ascontiguousarray(coef[idx], dtype=np.float64), x=x_d)
+                    xb = res["x_best"].cpu().numpy()
+                    out["pars"][idx[:, None], np.asarray(cols)[None, :]] = xb[:, :Km]
+                    out["coef"][idx] = xb[:, Km:]
+                    out["chisq"][idx] = res["chisq"].cpu().numpy()
+                    out["fisher"][idx] = res["A"].cpu().numpy()
+                    out["status"][idx] = res["status"].cpu().numpy()
+                    out["niter"][idx] = res["niter"].cpu().numpy()
+                    out["at_bound"][idx] = res["at_bound"].cpu().numpy().astype(np.uint32)
+            finally:
+                handle.close()
+        out["err"] = crlb_from_fisher(out["fisher"])
         return out
 
     def fit_from_bank(self, flux, eflux, bank, topk=1, **fit_kwargs):

@@ -2,6 +2,7 @@
 payne_lmfit_update an iteration) against scipy.optimize.least_squares around the numpy oracle's getspec on one CPU core.
 
     python tools/optfit_bench.py [--stars 4096] [--nobs 3600] [--b-max 2560] [--repeats 5] [--warmup 1] [--scipy-stars 8]
+    python tools/optfit_bench.py --npoly 4 [--ref-stars 6] [--alt-rounds 3,10,20,40]     (OptFit.fit_joint: joint_mode below)
 
 The workload: SMLP 4-256-256-256-4096 (synth.make_torch_net), 3600 observed pixels, stars drawn in the inner half of the label box
 with their own Vrad / Vrot / inst_R, spectra from the model itself plus seeded noise at S/N 100, starts 10 % of the box off the
@@ -55,6 +56,140 @@ def scipy_side(net, obs_wave, flux, eflux, start, n):
     return float(np.median(secs)), nfev
 
 
+def event_ms(torch, before, timed, repeats, warmup):
+    """Median ms of `timed()` between an event pair on the stream, `before()` run outside the pair, after `warmup` untimed calls."""
+    ms = []
+    for r in range(repeats + warmup):
+        before()
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        timed()
+        e1.record()
+        e1.synchronize()
+        if r >= warmup:
+            ms.append(e0.elapsed_time(e1))
+    return float(np.median(ms))
+
+
+def joint_reference(net, obs_wave, flux, eflux, start, x, P, n):
+    """The fp64 joint Levenberg-Marquardt loop of tests/test_lmfit_poly.py (numpy, the oracle's getspec chain) on the first n stars:
+    [(x*, A*) or None where it does not end CONVERGED inside the box within 25 evaluations]."""
+    sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests"))
+    from numpy.polynomial.chebyshev import chebvander
+    from test_lmfit import OracleModel, lm_reference, CONVERGED
+    from test_contfit import oracle_star
+    V = chebvander(x, P - 1)
+    out = []
+    for i in range(n):
+        om = OracleModel(net, "SMLP", obs_wave, start[i])
+        f, w = flux[i].astype(np.float64), 1.0 / eflux[i] ** 2
+        o = oracle_star(flux[i], w, om(start[i, :4])[0].astype(np.float32), x, P)
+
+        def fun(z):
+            m, J = om(z[:4])
+            p = V @ z[4:]
+            return m * p, np.concatenate([J * p[None, :], m[None, :] * V.T], axis=0)
+        r = lm_reference(fun, np.concatenate([start[i, :4], o["coef"]]), np.concatenate([net["xmin"], np.full(P, -1e30)]),
+                         np.concatenate([net["xmax"], np.full(P, 1e30)]), f, w)
+        out.append((r["x"], r["A"]) if r["status"] == CONVERGED and r["at_bound"] == 0 and r["niter"] <= 25 else None)
+    return out
+
+
+def distances(refs, pars, coef):
+    """Per compared star: (max over all K parameters of |x - x*| sqrt(A*_kk), max over the labels of |x - x*| in marginal sigma)."""
+    cond, marg = [], []
+    for i, ref in enumerate(refs):
+        if ref is None:
+            continue
+        xs, A = ref
+        dz = np.abs(np.concatenate([pars[i, :4], coef[i]]) - xs)
+        cond.append(float(np.max(dz * np.sqrt(np.diag(A)))))
+        marg.append(float(np.max(dz[:4] / np.sqrt(np.diag(np.linalg.inv(A)))[:4])))
+    return cond, marg
+
+
+def joint_mode(args):
+    """--npoly P: the workload multiplied by a Chebyshev series of P coefficients per star (c_0 in [0.5, 2], |c_j| <= 0.1, the errors
+    scaled with it).  (a) ``fit_joint`` stars/s and its distance from the fp64 joint reference loop on the first --ref-stars stars,
+    against ``fit_with_continuum`` at each of --alt-rounds; (b) the update alone for one block of stars, event pairs on the stream:
+    payne_lmfit_update at K = 4 (what the added rows cost), payne_lmfit_update_poly at K = 4 + P, and the route without it -- the
+    4 + P + 1 rows built by torch in fp32 and handed to payne_lmfit_update at K = 4 + P; (c) payne_lmfit_update_poly's compulsory
+    bytes, (1 + 4) n 4 + n 4 + n 8 a star and x once, against the HBM peak."""
+    import torch
+    from numpy.polynomial.chebyshev import chebvander
+    from thepayne_amd.fitting.optfit import OptFit, LMHandle
+    from thepayne_amd.fitting.contfit import abscissa
+    P, N, n = args.npoly, args.stars, args.nobs
+    net, obs_wave, truth, start, rng = workload(N, n)
+    fit = OptFit(net, "SMLP", obs_wave, b_max=args.b_max)
+    eng = fit.predictor.anns.engine
+    clean = fit.model_spectra(truth).cpu().numpy().astype(np.float64)
+    x = abscissa(obs_wave)
+    ctrue = np.concatenate([rng.uniform(0.5, 2.0, (N, 1)), rng.uniform(-0.1, 0.1, (N, P - 1))], axis=1)
+    poly = np.ascontiguousarray((chebvander(x, P - 1) @ ctrue.T).T)
+    flux = ((clean + rng.normal(0, 0.01, (N, n))) * poly).astype(np.float32)
+    eflux = 0.01 * poly
+
+    def clock(call):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        res = call()
+        torch.cuda.synchronize()
+        return time.perf_counter() - t0, res
+    for _ in range(args.warmup):
+        clock(lambda: fit.fit_joint(flux, eflux, start, npoly=P))
+    secs = []
+    for _ in range(args.repeats):
+        s, res = clock(lambda: fit.fit_joint(flux, eflux, start, npoly=P))
+        secs.append(s)
+    clock(lambda: fit.fit_joint(flux, eflux, start, npoly=P, timing=True))
+    tm = fit.timing
+    refs = joint_reference(net, obs_wave, flux, eflux, start, x, P, args.ref_stars) if args.ref_stars > 0 else []
+    cond, marg = distances(refs, res["pars"], res["coef"])
+    out = {"mode": "npoly", "npoly": P, "stars": N, "nobs": n, "b_max": args.b_max, "fit_joint_s_median": float(np.median(secs)), "fit_joint_s_min": float(np.min(secs)),
+           "fit_joint_stars_per_s": N / float(np.median(secs)), "status_counts": np.bincount(res["status"], minlength=6).tolist(),
+           "evaluations_median": float(np.median(res["niter"])), "evaluations_max": int(res["niter"].max()), "block_iterations": tm["iterations"],
+           "ms_per_iteration": {k: tm[k] / tm["iterations"] for k in ("network", "broadening", "update")},
+           "reference_stars_compared": len(cond), "fit_joint_sigma_all_parameters": cond, "fit_joint_marginal_sigma_labels": marg, "alternation": []}
+    clock(lambda: fit.fit_with_continuum(flux[:args.b_max], eflux[:args.b_max], start[:args.b_max], npoly=P, rounds=1))
+    for rounds in args.alt_rounds:
+        s, alt = clock(lambda: fit.fit_with_continuum(flux, eflux, start, npoly=P, rounds=rounds))
+        _, m = distances(refs, alt["pars"], alt["coef"])
+        out["alternation"].append({"rounds": rounds, "s": s, "stars_per_s": N / s, "marginal_sigma_labels": m,
+                                   "status_counts": np.bincount(alt["status"], minlength=6).tolist()})
+    # (b) the update alone, every star RUNNING (a fresh begin before each launch, outside the event pair)
+    Km, B, dev = 4, min(N, max(1, args.b_max // 5)), eng.device
+    K = Km + P
+    rows = torch.randn((B, 1 + Km, n), dtype=torch.float32, device=dev)
+    rows[:, 0] = 1.0 + 0.1 * rows[:, 0]
+    flux_d, w_d = torch.as_tensor(flux[:B]).to(dev), torch.as_tensor(1.0 / eflux[:B] ** 2).to(dev)
+    x_d = torch.as_tensor(x).to(dev)
+    T32 = torch.as_tensor(chebvander(x, P - 1).T.copy()).to(dev).to(torch.float32)               # [P, n]
+    lo, hi = np.concatenate([net["xmin"], np.full(P, -1e30)]), np.concatenate([net["xmax"], np.full(P, 1e30)])
+    x0 = np.concatenate([start[:B, :4], ctrue[:B]], axis=1)
+    h4, hK = LMHandle(Km, B, dev), LMHandle(K, B, dev)
+    big = torch.empty((B, 1 + K, n), dtype=torch.float32, device=dev)
+
+    def torch_route():
+        c32 = hK.trial()[:, Km:].to(torch.float32)
+        p = c32 @ T32                                                                             # [B, n]
+        big[:, 0] = rows[:, 0] * p
+        big[:, 1:1 + Km] = rows[:, 1:] * p[:, None, :]
+        big[:, 1 + Km:] = rows[:, :1] * T32[None, :, :]
+        hK.update(big, flux_d, w_d)
+    ms_plain = event_ms(torch, lambda: h4.begin(x0[:, :Km], lo[:Km], hi[:Km]), lambda: h4.update(rows, flux_d, w_d), args.repeats * 4, args.warmup + 2)
+    ms_poly = event_ms(torch, lambda: hK.begin(x0, lo, hi), lambda: hK.update_poly(rows, flux_d, w_d, x_d, P), args.repeats * 4, args.warmup + 2)
+    ms_torch = event_ms(torch, lambda: hK.begin(x0, lo, hi), torch_route, args.repeats * 4, args.warmup + 2)
+    h4.close()
+    hK.close()
+    nbytes = B * ((1 + Km) * n * 4 + n * 4 + n * 8) + n * 8
+    out.update({"stars_per_block": B, "update_ms_K4": ms_plain, "update_poly_ms": ms_poly, "torch_rows_plus_update_ms": ms_torch,
+                "update_poly_over_update_K4": ms_poly / ms_plain, "torch_route_over_update_poly": ms_torch / ms_poly,
+                "update_poly_bytes": nbytes, "update_poly_bytes_per_s": nbytes / (ms_poly * 1e-3), "update_poly_fraction_of_hbm_peak": nbytes / (ms_poly * 1e-3) / HBM_PEAK,
+                "repeats": args.repeats, "warmup": args.warmup})
+    print(json.dumps(out), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--stars", type=int, default=4096)
@@ -63,7 +198,12 @@ def main():
     ap.add_argument("--repeats", type=int, default=5)
     ap.add_argument("--warmup", type=int, default=1)
     ap.add_argument("--scipy-stars", type=int, default=8)
+    ap.add_argument("--npoly", type=int, default=0, help="fit a continuum polynomial of this many coefficients along (fit_joint)")
+    ap.add_argument("--ref-stars", type=int, default=6, help="--npoly: stars compared with the fp64 joint reference loop")
+    ap.add_argument("--alt-rounds", type=lambda s: [int(v) for v in s.split(",")], default=[3, 10, 20, 40], help="--npoly: fit_with_continuum's rounds")
     args = ap.parse_args()
+    if args.npoly:
+        return joint_mode(args)
     import torch
     from thepayne_amd.fitting.optfit import OptFit, LMHandle
     net, obs_wave, truth, start, rng = workload(args.stars, args.nobs)
