@@ -7,6 +7,33 @@
 //     no launch of its own (C3: 9.1 us as a launch between the dense kernels and the post kernel).
 // Arithmetic: fp64 on fp32 weights, as numpy promotes them (photANN.py:125-131).
 #pragma once
+#include <stddef.h>
+
+#ifdef __HIPCC__
+#define PAYNE_SED_HD __host__ __device__ inline
+#else
+#define PAYNE_SED_HD inline
+#endif
+
+// ---- tile form: sizes, and how many candidates a tile takes (plain C++: tests/test_phot_shapes.py builds this part with g++)
+constexpr int kSedCandsMax = 48;
+constexpr int kSedMaxH = 64;
+constexpr int kSedPitchA = kSedMaxH + 2;      // doubles: row stride 132 dwords = 4 banks (mod 64): the 16 rows of an A fragment hit 16 bank quads
+constexpr int kSedPitchW = kSedMaxH + 16;     // floats: k rows 80 dwords apart = 16 banks (mod 32): the k = 0..3 rows of a B fragment do not collide
+PAYNE_SED_HD constexpr size_t sed_tile_lds_bytes() {
+  return (size_t)kSedCandsMax * kSedPitchA * 8 + (size_t)(kSedMaxH + 8) * kSedPitchW * 4 + 3 * kSedMaxH * 4 + (size_t)6 * kSedCandsMax * 8;
+}
+PAYNE_SED_HD bool sed_tile_ok(int H) { return H >= 16 && H <= kSedMaxH && (H & 15) == 0; }
+// Candidates per photometric tile for a batch of B and F filters: as few as keeps F x blocks within `slots`, the workgroup slots the
+// hidden-layer launch's other workgroups leave free (none or fewer: one block over the whole batch) -- a multiple of 16 in
+// 16 .. kSedCandsMax; the launch then has F * ceil(B / cb) tiles.
+PAYNE_SED_HD int sed_tile_cands(int B, int F, int slots) {
+  const int nblk = slots >= F ? slots / F : 1;
+  const int cb = ((B + nblk - 1) / nblk + 15) & ~15;
+  return cb < 16 ? 16 : (cb > kSedCandsMax ? kSedCandsMax : cb);
+}
+
+#ifdef __HIPCC__
 #include <type_traits>
 
 struct PhotTables {
@@ -83,14 +110,7 @@ __device__ __forceinline__ double sed_mag(const PhotTables& P, const SedRow& s, 
 // instruction every ~5 cycles whatever it is, so sixteen fp64 fma per lane cost what ONE matrix instruction costs.
 //   LDS: X [48][kSedPitchA] f64 (encoded labels, then layer-1 outputs, then layer-2 outputs) | W2 [H][kSedPitchW] f32 ([k][h])
 //        | W1 [8][kSedPitchW] f32 ([d][h], rows 6, 7 zero) | b1, b2, w3 [H] f32
-constexpr int kSedCandsMax = 48;
-constexpr int kSedMaxH = 64;
-constexpr int kSedPitchA = kSedMaxH + 2;      // doubles: row stride 132 dwords = 4 banks (mod 64): the 16 rows of an A fragment hit 16 bank quads
-constexpr int kSedPitchW = kSedMaxH + 16;     // floats: k rows 80 dwords apart = 16 banks (mod 32): the k = 0..3 rows of a B fragment do not collide
-__host__ __device__ constexpr size_t sed_tile_lds_bytes() {
-  return (size_t)kSedCandsMax * kSedPitchA * 8 + (size_t)(kSedMaxH + 8) * kSedPitchW * 4 + 3 * kSedMaxH * 4 + (size_t)6 * kSedCandsMax * 8;
-}
-__host__ __device__ inline bool sed_tile_ok(int H) { return H >= 16 && H <= kSedMaxH && (H & 15) == 0; }
+//   (kSedCandsMax, kSedMaxH, the pitches, sed_tile_lds_bytes and sed_tile_ok: at the head of this file)
 
 // 1 / (1 + exp(-z)) in fp64 (photANN.py:125-131 through numpy) for N values at once: exp by 2^n * 2^f (|f| <= 1/2, degree-13
 // Taylor polynomial of exp(f ln 2): truncation < 5e-18, n ln 2 subtracted from -z in two parts), the quotient by v_rcp_f64 +
@@ -294,3 +314,4 @@ __device__ inline void sed_tile(const PhotTables& P, const double* __restrict__ 
   SED_STAMP(5);
 #undef SED_STAMP
 }
+#endif  // __HIPCC__
