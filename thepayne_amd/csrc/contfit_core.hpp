@@ -4,10 +4,9 @@
 // under ASan / UBSan).  Every array is the caller's (LDS or global memory in the kernel); the emulator fills its workspace with NaN
 // before every star, as LDS holds whatever the workgroup before left there.
 //   counting a pixel counts if it is inside n and w != 0; any other pixel is replaced by zeros by a select, whatever it holds.
-//   rows     R [P + 1][n] in fp64: R_j = m T_j(x) (one rounded product) for j < P, R_P = f.  T_j is `cheb`: T_0 = 1, T_1 = x,
-//            T_k = fma(2 x, T_k-1, -T_k-2).  G = R diag(w_kept) R^T is one 16 x 16 tile in lmfit_core.hpp's pixel groups, wave
-//            stripes and operand pair (value, value * w); the four partial tiles are added in wave order.
-//   solve    solve_star: S = diag(G_kk^-1/2), Cholesky of S A S (unit diagonal), c = S u, and
+//   rows     R [P + 1][n] in fp64: R_j = m T_j(x) (one rounded product) for j < P, R_P = f, T_j from cheb_series.hpp.
+//            G = R diag(w_kept) R^T is normal_tile.hpp's tile: its pixel groups, wave stripes, operand pair and wave-order sum.
+//   solve    solve_star: normal_tile.hpp's scaled_solve on G (unit diagonal), and
 //            chi^2 = e^T G e with e = (c, -1), i.e. G[P][P] - 2 c.b + c^T A c, summed row by row in fp64.  (Not a second pass over
 //            the residuals: without clipping the kernel reads every pixel once.  The form is second-order in c's error; what it
 //            loses is the sums' rounding, n 2^-52 sum_ij |e_i e_j| sum_p |R_i R_j| w.)
@@ -21,12 +20,13 @@
 #include <vector>
 
 #include "../../include/payne_hip.h"
-#include "lmfit_core.hpp"
+#include "cheb_series.hpp"
+#include "normal_tile.hpp"
 
 namespace payne {
 namespace contfit {
 
-namespace lm = payne::lmfit;
+namespace nt = payne::ntile;
 
 constexpr int kMaxP = PAYNE_CONTFIT_MAX_P;
 constexpr int kMaxClip = PAYNE_CONTFIT_MAX_NCLIP;
@@ -34,115 +34,80 @@ constexpr int kMaxN = PAYNE_CONTFIT_MAX_N;            // the clipping mask is a 
 constexpr int kWorkDoubles = kMaxP * kMaxP + 2 * kMaxP;   // solve_star's workspace: the scaled matrix, S, u
 constexpr int kChunk = 4;                             // pixels a thread takes at a time in the residual and output passes
 
-PAYNE_LMFIT_HD bool opts_ok(const payne_contfit_opts& o) {
+PAYNE_HD bool opts_ok(const payne_contfit_opts& o) {
   return o.P >= 1 && o.P <= kMaxP && o.nclip >= 0 && o.nclip <= kMaxClip && o.kappa_lo > 0.0 && o.kappa_hi > 0.0;
 }
-PAYNE_LMFIT_HD int mask_words(int n) { return (n + 31) / 32; }
-PAYNE_LMFIT_HD bool finite_f(float v) { return lm::finite((double)v); }
-PAYNE_LMFIT_HD bool failed(int status) { return status != PAYNE_CONTFIT_OK && status != PAYNE_CONTFIT_NONPOSITIVE; }
+PAYNE_HD int mask_words(int n) { return (n + 31) / 32; }
+PAYNE_HD bool finite_f(float v) { return nt::finite((double)v); }
+PAYNE_HD bool failed(int status) { return status != PAYNE_CONTFIT_OK && status != PAYNE_CONTFIT_NONPOSITIVE; }
 
-// The Chebyshev series (lmfit_core.hpp: the recurrence, written once, is also payne_lmfit_update_poly's).
-using lm::cheb_next;
-using lm::cheb;
-using lm::cheb4;
-using lm::poly_value;
-using lm::poly4;
+// The Chebyshev series (cheb_series.hpp) under this namespace, as the kernel and the emulator name it.
+using chebs::cheb;
+using chebs::cheb4;
+using chebs::poly_value;
+using chebs::poly4;
 
 // Row i of R at one pixel.
-PAYNE_LMFIT_HD double row_value(int i, int P, float m, float f, double x) { return i < P ? (double)m * cheb(i, x) : (double)f; }
+PAYNE_HD double row_value(int i, int P, float m, float f, double x) { return i < P ? (double)m * cheb(i, x) : (double)f; }
 // The same from T = T_i(x) (cheb4).
-PAYNE_LMFIT_HD double row_from(int i, int P, float m, float f, double T) { return i < P ? (double)m * T : (double)f; }
+PAYNE_HD double row_from(int i, int P, float m, float f, double T) { return i < P ? (double)m * T : (double)f; }
 
 // What the first sums pass checks of a counting pixel.
-PAYNE_LMFIT_HD bool pixel_finite(float f, float m, double w) { return finite_f(f) && finite_f(m) && lm::finite(w); }
+PAYNE_HD bool pixel_finite(float f, float m, double w) { return finite_f(f) && finite_f(m) && nt::finite(w); }
 
-// The tile of one star on the host in the kernel's pixel order (lmfit_core.hpp: tile_sums_host); mask == NULL: every counting
-// pixel is kept.  *count = the counting pixels, *bad = one of them is not finite.
+// The tile of one star on the host in the kernel's pixel order; mask == NULL: every counting pixel is kept.  *count = the counting
+// pixels, *bad = one of them is not finite.
 inline void tile_sums_host(const float* flux, const double* w, const float* model, const double* x, int n, int P, const unsigned* mask,
                            double* G, int* count, bool* bad) {
-  for (int e = 0; e < lm::kTileSize; ++e) G[e] = 0.0;
-  const int gpw = lm::groups_per_wave(n), groups = lm::groups_of(n);
-  std::vector<double> acc((size_t)lm::kTileSize);
   int cnt = 0;
   bool nan = false;
-  for (int v = 0; v < lm::kWaves; ++v) {
-    for (double& e : acc) e = 0.0;
-    for (int grp = v * gpw; grp < (v + 1) * gpw && grp < groups; ++grp)
-      for (int t = 0; t < 4; ++t)
-        for (int q = 0; q < 4; ++q) {
-          const int p = lm::pixel_of(grp, q, t);
-          const bool counts = p < n && w[p < n ? p : 0] != 0.0;
-          if (!counts) continue;                                    // (both operands zero: the sums do not change)
-          ++cnt;
-          nan = nan || !pixel_finite(flux[p], model[p], w[p]);
-          if (mask && !((mask[p >> 5] >> (p & 31)) & 1u)) continue;
-          double a[lm::kTile], b[lm::kTile];
-          for (int i = 0; i <= P; ++i) lm::operand_pair(row_value(i, P, model[p], flux[p], x[p]), w[p], true, &a[i], &b[i]);
-          for (int i = 0; i <= P; ++i)
-            for (int j = 0; j <= P; ++j) acc[(size_t)(i * lm::kTile + j)] += a[i] * b[j];
-        }
-    for (int i = 0; i <= P; ++i)
-      for (int j = 0; j <= P; ++j) {
-        const int e = i * lm::kTile + j;
-        G[e] = v == 0 ? acc[(size_t)e] : G[e] + acc[(size_t)e];
-      }
-  }
+  nt::tile_sums_host(w, n, P + 1, [&](int p, double* r) {
+    ++cnt;
+    nan = nan || !pixel_finite(flux[p], model[p], w[p]);
+    if (mask && !((mask[p >> 5] >> (p & 31)) & 1u)) return false;
+    for (int i = 0; i <= P; ++i) r[i] = row_value(i, P, model[p], flux[p], x[p]);
+    return true;
+  }, G);
   *count = cnt;
   *bad = nan;
 }
 
 // The coefficients behind the tile G [16][16] of `kept` pixels: c [P], *chisq.  work holds kWorkDoubles.  Returns the status:
 // NAN (the first pass met a value that is not finite), TOO_FEW, SINGULAR or OK; c and *chisq are written only with OK.
-PAYNE_LMFIT_HD int solve_star(const double* G, int P, int kept, bool bad, double* work, double* c, double* chisq) {
+PAYNE_HD int solve_star(const double* G, int P, int kept, bool bad, double* work, double* c, double* chisq) {
   if (bad) return PAYNE_CONTFIT_NAN;
   if (kept < P) return PAYNE_CONTFIT_TOO_FEW;
-  double* M = work;
-  double* S = work + P * P;
-  double* u = S + P;
-  for (int k = 0; k < P; ++k) {
-    const double d = G[k * lm::kTile + k];
-    if (!(d > 0.0) || !lm::finite(d)) return PAYNE_CONTFIT_SINGULAR;
-    S[k] = 1.0 / sqrt(d);
-  }
-  for (int i = 0; i < P; ++i) {
-    for (int j = 0; j < i; ++j) M[i * P + j] = G[i * lm::kTile + j] * S[i] * S[j];
-    M[i * P + i] = 1.0;
-    u[i] = G[i * lm::kTile + P] * S[i];
-  }
-  if (!lm::cholesky_solve(M, u, P)) return PAYNE_CONTFIT_SINGULAR;
-  for (int k = 0; k < P; ++k) {
-    u[k] *= S[k];
-    if (!lm::finite(u[k])) return PAYNE_CONTFIT_SINGULAR;
-  }
+  if (!nt::scaled_solve(G, nt::kTile, G + P, nt::kTile, 1.0, P, work)) return PAYNE_CONTFIT_SINGULAR;
+  const double* u = work + P * P + P;
   double total = 0.0;                                               // e^T G e, e = (c, -1); the upper triangle, mirrored
   for (int i = 0; i <= P; ++i) {
     const double ei = i < P ? u[i] : -1.0;
-    double row = 0.5 * ei * G[i * lm::kTile + i];
-    for (int j = i + 1; j <= P; ++j) row += (j < P ? u[j] : -1.0) * G[i * lm::kTile + j];
+    double row = 0.5 * ei * G[i * nt::kTile + i];
+    for (int j = i + 1; j <= P; ++j) row += (j < P ? u[j] : -1.0) * G[i * nt::kTile + j];
     total += 2.0 * ei * row;
   }
-  if (!lm::finite(total)) return PAYNE_CONTFIT_SINGULAR;
+  if (!nt::finite(total)) return PAYNE_CONTFIT_SINGULAR;
   for (int k = 0; k < P; ++k) c[k] = u[k];
   *chisq = total;
   return PAYNE_CONTFIT_OK;
 }
 
 // The clipping scale s.
-PAYNE_LMFIT_HD double clip_scale(double chisq, int kept, int P, int rescale) {
+PAYNE_HD double clip_scale(double chisq, int kept, int P, int rescale) {
   if (!rescale) return 1.0;
   const int dof = kept - P > 1 ? kept - P : 1;
   return sqrt((chisq > 0.0 ? chisq : 0.0) / (double)dof);
 }
 
 // Is a counting pixel kept?  pv = p(x) there; lo = kappa_lo s, hi = kappa_hi s.
-PAYNE_LMFIT_HD bool keeps(float f, float m, double w, double pv, double lo, double hi) {
+PAYNE_HD bool keeps(float f, float m, double w, double pv, double lo, double hi) {
   const double z = sqrt(w) * fma(-(double)m, pv, (double)f);
   return z >= -lo && z <= hi;
 }
 
 // One pixel of the output rows.  True: a counting pixel whose polynomial is not positive (or not finite).
-PAYNE_LMFIT_HD bool out_pixel(float f, double w, double pv, bool counts, bool dropped, float* fo, double* wo) {
-  const bool ok = pv > 0.0 && lm::finite(pv);
+PAYNE_HD bool out_pixel(float f, double w, double pv, bool counts, bool dropped, float* fo, double* wo) {
+  const bool ok = pv > 0.0 && nt::finite(pv);
   *fo = ok ? (float)((double)f / pv) : 0.0f;
   *wo = ok && counts && !dropped ? (w * pv) * pv : 0.0;
   return counts && !ok;
@@ -175,7 +140,7 @@ inline void fit_star_host(const float* flux, const double* w, const float* model
       if (st != PAYNE_CONTFIT_OK) break;
       ++solves;
       if (trace) {
-        trace->G.insert(trace->G.end(), G, G + lm::kTileSize);
+        trace->G.insert(trace->G.end(), G, G + nt::kTileSize);
         for (int p = 0; p < n; ++p) trace->kept.push_back(w[p] != 0.0 && (!masked || ((mask[p >> 5] >> (p & 31)) & 1u)) ? 1 : 0);
       }
       if (round == o.nclip) break;

@@ -3,11 +3,9 @@
 //
 //   payne_contfit_kernel  one 256-thread workgroup a star.  Passes over the star's flux (4 B), w (8 B) and model (4 B) per pixel;
 //     x is shared by every star and stays in cache.
-//       sums      k_lmfit.hip's loop: lane (i = lane & 15, q = lane >> 4) of every wave takes four consecutive pixels, forms row i of
-//                 R = [m T_0(x) .. m T_P-1(x) ; f] there and hands (value, value * w) to four v_mfma_f64_16x16x4_f64:
-//                 A[i][k = q] = R[i][p], B[k = q][j = i] = R[i][p] w[p], so nothing is transposed.  D[(lane >> 4) + 4 v][lane & 15]
-//                 is G.  Each wave owns a contiguous stripe of pixel groups; the four partial tiles meet in LDS and are added in
-//                 wave order.  The sixteen lanes of one q read the same four pixels; lane i = 0 counts and checks them.
+//       sums      normal_tile.hpp's loop (wave_sums, sum_waves): lane (i = lane & 15, q = lane >> 4) of every wave takes four
+//                 consecutive pixels and forms row i of R = [m T_0(x) .. m T_P-1(x) ; f] there.  The sixteen lanes of one q read
+//                 the same four pixels; lane i = 0 counts and checks them.
 //       solve     thread 0, solve_star on LDS.
 //       residual  (nclip > 0) a thread takes four consecutive pixels, eight neighbouring lanes OR their keep bits into one word
 //                 of the mask in LDS (dynamic, ceil(n / 32) words) and one of them stores it: no atomics.
@@ -18,19 +16,19 @@
 //     same operands: measured at 13 - 19 % of the matrix instructions' floor, not waiting for memory (NOTES.md, 2026-10-20).
 #include <hip/hip_runtime.h>
 
-#include <cstdint>
-#include <string>
-
 #include "../../include/payne_hip.h"
 #include "contfit_core.hpp"
-#include "ctx_api.hpp"
+#include "host_prologue.hpp"
 
 namespace cf = payne::contfit;
-namespace lm = payne::lmfit;
+namespace nt = payne::ntile;
 
 namespace {
 
-typedef double cf_d4 __attribute__((ext_vector_type(4)));
+using nt::load4;
+using payne::host::OnDevice;
+using payne::host::aligned16;
+using payne::host::fail;
 
 struct Args {
   const float* flux;
@@ -53,71 +51,44 @@ struct Args {
   long long ld_o;
 };
 
-// Four consecutive values from p (a multiple of four, p < n); `whole`: all four may be read.  Beyond n: zero.
-template <bool VEC>
-__device__ inline void load4(const float* __restrict__ base, int p, int n, bool whole, float* v) {
-  if (VEC && whole) {
-    const float4 a = *reinterpret_cast<const float4*>(base + p);
-    v[0] = p + 0 < n ? a.x : 0.0f; v[1] = p + 1 < n ? a.y : 0.0f; v[2] = p + 2 < n ? a.z : 0.0f; v[3] = p + 3 < n ? a.w : 0.0f;
-  } else {
-#pragma unroll
-    for (int t = 0; t < 4; ++t) v[t] = p + t < n ? base[p + t] : 0.0f;
-  }
-}
-template <bool VEC>
-__device__ inline void load4(const double* __restrict__ base, int p, int n, bool whole, double* v) {
-  if (VEC && whole) {
-    const double2 a = *reinterpret_cast<const double2*>(base + p), b = *reinterpret_cast<const double2*>(base + p + 2);
-    v[0] = p + 0 < n ? a.x : 0.0; v[1] = p + 1 < n ? a.y : 0.0; v[2] = p + 2 < n ? b.x : 0.0; v[3] = p + 3 < n ? b.y : 0.0;
-  } else {
-#pragma unroll
-    for (int t = 0; t < 4; ++t) v[t] = p + t < n ? base[p + t] : 0.0;
-  }
-}
-
 // The sum of v over the workgroup (integers: any order gives the same value).
 __device__ inline long long block_sum(long long v, long long* red) {
 #pragma unroll
   for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
   __syncthreads();                                                  // (the readers of the call before are done with red)
-  if ((threadIdx.x & (lm::kWave - 1)) == 0) red[threadIdx.x / lm::kWave] = v;
+  if ((threadIdx.x & (nt::kWave - 1)) == 0) red[threadIdx.x / nt::kWave] = v;
   __syncthreads();
   return (red[0] + red[1]) + (red[2] + red[3]);
 }
 
 template <bool VEC>
-__global__ void __launch_bounds__(lm::kThreads) payne_contfit_kernel(const Args a) {
+__global__ void __launch_bounds__(nt::kThreads) payne_contfit_kernel(const Args a) {
   extern __shared__ unsigned mask[];                                // cf::mask_words(n) words where nclip > 0
-  __shared__ double part[lm::kWaves][lm::kTileSize];
-  __shared__ double tile[lm::kTileSize];
+  __shared__ double part[nt::kWaves][nt::kTileSize];
+  __shared__ double tile[nt::kTileSize];
   __shared__ double work[cf::kWorkDoubles];
   __shared__ double coef[cf::kMaxP + 1];
   __shared__ double chisq_s;
-  __shared__ long long red[lm::kWaves];
+  __shared__ long long red[nt::kWaves];
   __shared__ int status_s;
   const size_t s = blockIdx.x;
-  const int tid = threadIdx.x, lane = tid & (lm::kWave - 1), wave = tid / lm::kWave;
-  const int i = lane & 15, q = lane >> 4;
+  const int tid = threadIdx.x, i = tid & 15;
   const int n = a.n, P = a.o.P;
   const int mi = a.model_index ? a.model_index[s] : (int)s;
   const bool bad_model = mi < 0 || mi >= a.n_models;
   const float* fb = a.flux + s * (size_t)a.ld_f;
   const double* wb = a.w + s * (size_t)a.ld_f;
   const float* mb = a.model + (size_t)(bad_model ? 0 : mi) * (size_t)a.ld_m;   // (not read when bad_model)
-  const int chunks = (n + cf::kChunk - 1) / cf::kChunk, sweeps = (chunks + lm::kThreads - 1) / lm::kThreads;
+  const int chunks = (n + cf::kChunk - 1) / cf::kChunk, sweeps = (chunks + nt::kThreads - 1) / nt::kThreads;
   int st = bad_model ? PAYNE_CONTFIT_BAD_MODEL : PAYNE_CONTFIT_OK, solves = 0, kept = 0;
   double chi = 0.0;
   bool masked = false;
   if (!bad_model) {
     const bool live = i <= P;
-    const int gpw = lm::groups_per_wave(n), groups = lm::groups_of(n);
-    const int g0 = wave * gpw, g1 = g0 + gpw < groups ? g0 + gpw : groups;
     for (int round = 0;; ++round) {
       // ---- sums
-      cf_d4 acc = {0.0, 0.0, 0.0, 0.0};
       long long seen = 0;                                           // counting pixels; bit 32 up: those that are not finite
-      for (int grp = g0; grp < g1; ++grp) {
-        const int p = lm::pixel_of(grp, q, 0);
+      const nt::d4 acc = nt::wave_sums(n, [&](int p) PAYNE_TILE_CALLABLE {
         float f[4] = {0.0f, 0.0f, 0.0f, 0.0f}, m[4] = {0.0f, 0.0f, 0.0f, 0.0f};
         double wv[4] = {0.0, 0.0, 0.0, 0.0}, xv[4] = {0.0, 0.0, 0.0, 0.0};
         unsigned bits = 0u;
@@ -132,27 +103,24 @@ __global__ void __launch_bounds__(lm::kThreads) payne_contfit_kernel(const Args 
         }
         double T[4];
         cf::cheb4(live ? i : 0, P, xv, T);
-#pragma unroll
-        for (int t = 0; t < 4; ++t) {
+        return [=, &seen](int t, double* r, double* wt) PAYNE_TILE_CALLABLE {
           const bool counts = p + t < n && wv[t] != 0.0;
           if (round == 0 && i == 0 && counts) seen += 1ll + (cf::pixel_finite(f[t], m[t], wv[t]) ? 0ll : 1ll << 32);
-          double av, bv;
-          lm::operand_pair(cf::row_from(live ? i : 0, P, m[t], f[t], T[t]), wv[t], live && counts && ((bits >> t) & 1u), &av, &bv);
-          acc = __builtin_amdgcn_mfma_f64_16x16x4f64(av, bv, acc, 0, 0, 0);
-        }
-      }
-#pragma unroll
-      for (int v = 0; v < 4; ++v) part[wave][(q + 4 * v) * lm::kTile + i] = acc[v];
+          *r = cf::row_from(live ? i : 0, P, m[t], f[t], T[t]);
+          *wt = wv[t];
+          return live && counts && ((bits >> t) & 1u);
+        };
+      });
       bool bad = false;
-      if (round == 0) {
-        const long long total = block_sum(seen, red);               // (its barriers publish part too)
-        kept = (int)(total & 0xffffffffll);
-        bad = (total >> 32) != 0;
-      } else {
-        __syncthreads();
-      }
-      tile[tid] = ((part[0][tid] + part[1][tid]) + part[2][tid]) + part[3][tid];
-      __syncthreads();
+      nt::sum_waves(acc, part, tile, [&]() PAYNE_TILE_CALLABLE {
+        if (round == 0) {
+          const long long total = block_sum(seen, red);             // (its barriers publish part too)
+          kept = (int)(total & 0xffffffffll);
+          bad = (total >> 32) != 0;
+        } else {
+          __syncthreads();
+        }
+      });
       // ---- solve
       if (tid == 0) status_s = cf::solve_star(tile, P, kept, bad, work, coef, &chisq_s);
       __syncthreads();
@@ -165,7 +133,7 @@ __global__ void __launch_bounds__(lm::kThreads) payne_contfit_kernel(const Args 
       const double sc = cf::clip_scale(chi, kept, P, a.o.rescale), lo = a.o.kappa_lo * sc, hi = a.o.kappa_hi * sc;
       long long tally = 0;                                          // kept pixels; bit 32 up: threads whose four bits changed
       for (int k = 0; k < sweeps; ++k) {
-        const int c = k * lm::kThreads + tid, p = cf::kChunk * c;
+        const int c = k * nt::kThreads + tid, p = cf::kChunk * c;
         unsigned nib = 0u, old = 0u;
         if (p < n) {
           float f[4], m[4];
@@ -206,7 +174,7 @@ __global__ void __launch_bounds__(lm::kThreads) payne_contfit_kernel(const Args 
   long long nonpos = 0;
   if (!fail || rows) {
     for (int k = 0; k < sweeps; ++k) {
-      const int c = k * lm::kThreads + tid, p = cf::kChunk * c;
+      const int c = k * nt::kThreads + tid, p = cf::kChunk * c;
       if (p >= n) continue;
       float f[4] = {0.0f, 0.0f, 0.0f, 0.0f}, fo[4];
       double wv[4] = {0.0, 0.0, 0.0, 0.0}, xv[4] = {0.0, 0.0, 0.0, 0.0}, wo[4];
@@ -251,13 +219,6 @@ __global__ void __launch_bounds__(lm::kThreads) payne_contfit_kernel(const Args 
   }
 }
 
-int fail(int code, const std::string& msg) {
-  payne::set_create_error(msg);
-  return code;
-}
-
-bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
-
 }  // namespace
 
 extern "C" int payne_contfit_batch(int device, const float* flux_dev, const double* w_dev, long long ld_f, const float* model_dev,
@@ -272,9 +233,8 @@ extern "C" int payne_contfit_batch(int device, const float* flux_dev, const doub
     return fail(PAYNE_E_INVALID, "payne_contfit_batch: a null device pointer");
   if (n > cf::kMaxN) return fail(PAYNE_E_UNSUPPORTED, "payne_contfit_batch: n > 262144 (the clipping mask is a bit set in LDS)");
   if (N == 0) return PAYNE_OK;
-  int prev = 0;
-  (void)hipGetDevice(&prev);
-  if (hipSetDevice(device) != hipSuccess) return fail(PAYNE_E_HIP, "payne_contfit_batch: hipSetDevice");
+  OnDevice on(device);
+  if (!on.ok()) return fail(PAYNE_E_HIP, "payne_contfit_batch: hipSetDevice");
   const Args a{flux_dev, w_dev, ld_f, model_dev, ld_m, n_models, model_index_dev, x_dev, n, *opts, coef_dev, chisq_dev, npix_dev, status_dev,
                rounds_dev, flux_out_dev, w_out_dev, ld_o};
   const bool rows = flux_out_dev || w_out_dev;
@@ -283,10 +243,8 @@ extern "C" int payne_contfit_batch(int device, const float* flux_dev, const doub
   const size_t lds = opts->nclip > 0 ? (size_t)cf::mask_words(n) * sizeof(unsigned) : 0;
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   if (vec)
-    hipLaunchKernelGGL(payne_contfit_kernel<true>, dim3((unsigned)N), dim3(lm::kThreads), lds, st, a);
+    hipLaunchKernelGGL(payne_contfit_kernel<true>, dim3((unsigned)N), dim3(nt::kThreads), lds, st, a);
   else
-    hipLaunchKernelGGL(payne_contfit_kernel<false>, dim3((unsigned)N), dim3(lm::kThreads), lds, st, a);
-  const bool ok = hipGetLastError() == hipSuccess;
-  (void)hipSetDevice(prev);
-  return ok ? PAYNE_OK : fail(PAYNE_E_HIP, "payne_contfit_batch: the launch failed");
+    hipLaunchKernelGGL(payne_contfit_kernel<false>, dim3((unsigned)N), dim3(nt::kThreads), lds, st, a);
+  return hipGetLastError() == hipSuccess ? PAYNE_OK : fail(PAYNE_E_HIP, "payne_contfit_batch: the launch failed");
 }

@@ -1,33 +1,31 @@
 // k_lmfit.hip -- payne_lmfit_*: batched Levenberg-Marquardt (include/payne_hip.h).  The arithmetic is lmfit_core.hpp, which runs on
-// the host too (tests/emul/lmfit_emul.cpp).
+// the host too (tests/emul/lmfit_emul.cpp, lmfit_poly_emul.cpp); the tile, its loop and the 16-byte loads are normal_tile.hpp.
 //
 //   payne_lmfit_update_kernel  one 256-thread workgroup a star, skipped when the star is no longer RUNNING.  Lane (i = lane & 15,
-//     q = lane >> 4) of every wave reads four consecutive fp32 pixels of row i of R = [rows 1..K ; flux - row 0] and the four fp64
-//     weights, and hands them to four v_mfma_f64_16x16x4_f64: A[i][k = q] = R[i][p], B[k = q][j = i] = R[i][p] w[p], the same
-//     lane's value times w, so nothing is transposed.  D[i = (lane >> 4) + 4 v][j = lane & 15], v = 0..3, is G = R diag(w) R^T.
-//     Each wave owns a contiguous stripe of pixel groups; the four partial tiles meet in LDS and are added in wave order.  Thread 0
-//     then takes the star's step (lmfit_core.hpp: update_star) on LDS and the handle's arrays.  <VEC>: 16-byte loads (ld, ld_f
-//     multiples of four, aligned pointers); otherwise element by element, the same values in the same places.
-//     The kernel streams (1 + K) n fp32 + n fp32 + n fp64 per star once and is bound by HBM; the matrix instruction takes the
-//     (K + 1)^2 / 2 products a pixel off the vector pipeline, which would otherwise bind it for K >= 4.
-//   payne_lmfit_update_poly_kernel  the same launch for a model times a Chebyshev series whose P coefficients are the last P of the K
-//     parameters: R = [p dm/dtheta ; m T_j(x) ; flux - m p] is formed in registers from the caller's 1 + Km rows, the star's
-//     coefficients (x_trial, copied to LDS) and x, and never stored.  Every lane evaluates one series at its four pixels in one
-//     loop of P - 2 steps (lmfit_core.hpp: series4): p, or T_j as the series of a unit vector.  Loads, pixel order, operand map,
-//     the select for w == 0 and the wave-order sum are the kernel's above; update_star is the same call.
+//     q = lane >> 4) of every wave reads four consecutive fp32 pixels of row i of R and the four fp64 weights and hands them to
+//     normal_tile.hpp's loop (wave_sums); the four partial tiles meet in LDS (sum_waves).  Thread 0 then takes the star's step
+//     (lmfit_core.hpp: update_star) on LDS and the handle's arrays.  <VEC>: 16-byte loads (ld, ld_f multiples of four, aligned
+//     pointers); otherwise element by element, the same values in the same places.
+//       <POLY = false>  payne_lmfit_update: R = [rows 1..K ; flux - row 0].  The kernel streams (1 + K) n fp32 + n fp32 + n fp64 per
+//         star once and is bound by HBM; the matrix instruction takes the (K + 1)^2 / 2 products a pixel off the vector pipeline,
+//         which would otherwise bind it for K >= 4.
+//       <POLY = true>   payne_lmfit_update_poly: a model times a Chebyshev series whose P coefficients are the last P of the K
+//         parameters.  R = [p dm/dtheta ; m T_j(x) ; flux - m p] is formed in registers from the caller's 1 + Km rows, the star's
+//         coefficients (x_trial, copied to LDS) and x, and never stored.  Every lane evaluates one series at its four pixels in one
+//         loop of P - 2 steps (cheb_series.hpp: series4): p, or T_j as the series of a unit vector.
 //   payne_lmfit_begin_kernel   one thread a star: x_trial = clip(x0), the state reset.
 //   No atomics; every sum has a fixed order.
 #include <hip/hip_runtime.h>
 
-#include <cstdint>
-#include <string>
 #include <vector>
 
 #include "../../include/payne_hip.h"
-#include "ctx_api.hpp"
+#include "host_prologue.hpp"
 #include "lmfit_core.hpp"
 
 namespace lm = payne::lmfit;
+namespace nt = payne::ntile;
+namespace chebs = payne::chebs;
 
 struct payne_lmfit {
   int device = 0, K = 0, max_stars = 0, B = 0;
@@ -39,171 +37,59 @@ struct payne_lmfit {
 
 namespace {
 
-typedef double lm_d4 __attribute__((ext_vector_type(4)));
+using payne::host::OnDevice;
+using payne::host::aligned16;
+using payne::host::fail;
 
-__global__ void __launch_bounds__(lm::kThreads) payne_lmfit_begin_kernel(const double* __restrict__ x0, int B, int K, const lm::State st,
+__global__ void __launch_bounds__(nt::kThreads) payne_lmfit_begin_kernel(const double* __restrict__ x0, int B, int K, const lm::State st,
                                                                          const lm::Box box, double lambda0) {
   const int b = blockIdx.x * blockDim.x + threadIdx.x;
   if (b < B) lm::begin_star(st, (size_t)b, K, x0 + (size_t)b * (size_t)K, box, lambda0);
 }
 
-template <bool VEC>
-__global__ void __launch_bounds__(lm::kThreads) payne_lmfit_update_kernel(const float* __restrict__ rows, long long ld,
+// rows holds 1 + K rows a star, or with POLY 1 + Km, Km = K - P; x and P are read with POLY only.
+template <bool VEC, bool POLY>
+__global__ void __launch_bounds__(nt::kThreads) payne_lmfit_update_kernel(const float* __restrict__ rows, long long ld,
                                                                           const float* __restrict__ flux, const double* __restrict__ w,
-                                                                          long long ld_f, int n, int K, const lm::State st, const lm::Box box,
-                                                                          const payne_lmfit_opts opts) {
-  __shared__ double part[lm::kWaves][lm::kTileSize];
-  __shared__ double tile[lm::kTileSize];
+                                                                          long long ld_f, const double* __restrict__ x, int n, int K, int P,
+                                                                          const lm::State st, const lm::Box box, const payne_lmfit_opts opts) {
+  __shared__ double part[nt::kWaves][nt::kTileSize];
+  __shared__ double tile[nt::kTileSize];
   __shared__ double work[lm::kWorkDoubles];
+  __shared__ double coef[lm::kMaxK];                                // (POLY only: the plain form never names it)
   const size_t b = blockIdx.x;
   if (st.status[b] != PAYNE_LMFIT_RUNNING) return;                  // (the whole workgroup)
-  const int tid = threadIdx.x, lane = tid & (lm::kWave - 1), wave = tid / lm::kWave;
-  const int i = lane & 15, q = lane >> 4;
-  const bool live = i <= K, residual = i == K;
-  const float* ra = rows + (b * (size_t)(1 + K) + (size_t)(i < K ? 1 + i : 0)) * (size_t)ld;   // the lane's row (row 0 where it has none)
-  const float* fb = flux + b * (size_t)ld_f;
-  const double* wb = w + b * (size_t)ld_f;
-  const int gpw = lm::groups_per_wave(n), groups = lm::groups_of(n);
-  const int g0 = wave * gpw, g1 = g0 + gpw < groups ? g0 + gpw : groups;
-  lm_d4 acc = {0.0, 0.0, 0.0, 0.0};
-  for (int grp = g0; grp < g1; ++grp) {
-    const int p = lm::pixel_of(grp, q, 0);
-    float a[4] = {0.0f, 0.0f, 0.0f, 0.0f}, f[4] = {0.0f, 0.0f, 0.0f, 0.0f};
-    double wv[4] = {0.0, 0.0, 0.0, 0.0};
-    if (VEC) {
-      if (p < n) {                                                  // p + 3 < ld and ld_f: both are multiples of four
-        const double2 w01 = *reinterpret_cast<const double2*>(wb + p), w23 = *reinterpret_cast<const double2*>(wb + p + 2);
-        wv[0] = w01.x; wv[1] = w01.y; wv[2] = w23.x; wv[3] = w23.y;
-        if (live) {
-          const float4 a4 = *reinterpret_cast<const float4*>(ra + p);
-          a[0] = a4.x; a[1] = a4.y; a[2] = a4.z; a[3] = a4.w;
-        }
-        if (residual) {
-          const float4 f4 = *reinterpret_cast<const float4*>(fb + p);
-          f[0] = f4.x; f[1] = f4.y; f[2] = f4.z; f[3] = f4.w;
-        }
-      }
-    } else {
-#pragma unroll
-      for (int t = 0; t < 4; ++t)
-        if (p + t < n) {
-          wv[t] = wb[p + t];
-          if (live) a[t] = ra[p + t];
-          if (residual) f[t] = fb[p + t];
-        }
-    }
-#pragma unroll
-    for (int t = 0; t < 4; ++t) {
-      double av, bv;
-      lm::operand_pair(lm::operand(i, K, a[t], f[t]), wv[t], live && p + t < n && wv[t] != 0.0, &av, &bv);
-      acc = __builtin_amdgcn_mfma_f64_16x16x4f64(av, bv, acc, 0, 0, 0);
-    }
+  const int tid = threadIdx.x, i = tid & 15;
+  const int Km = POLY ? K - P : K;
+  if constexpr (POLY) {
+    if (tid < P) coef[tid] = st.x_trial[b * (size_t)K + (size_t)(Km + tid)];
+    __syncthreads();
   }
-#pragma unroll
-  for (int v = 0; v < 4; ++v) part[wave][(q + 4 * v) * lm::kTile + i] = acc[v];
-  __syncthreads();
-  tile[tid] = ((part[0][tid] + part[1][tid]) + part[2][tid]) + part[3][tid];
-  __syncthreads();
-  if (tid == 0) lm::update_star(st, b, K, tile, opts, box, work);
-}
-
-// The same with a continuum polynomial: K = Km + P, rows holds 1 + Km rows a star.
-template <bool VEC>
-__global__ void __launch_bounds__(lm::kThreads) payne_lmfit_update_poly_kernel(const float* __restrict__ rows, long long ld,
-                                                                               const float* __restrict__ flux, const double* __restrict__ w,
-                                                                               long long ld_f, const double* __restrict__ x, int n, int K, int P,
-                                                                               const lm::State st, const lm::Box box, const payne_lmfit_opts opts) {
-  __shared__ double part[lm::kWaves][lm::kTileSize];
-  __shared__ double tile[lm::kTileSize];
-  __shared__ double work[lm::kWorkDoubles];
-  __shared__ double coef[lm::kMaxK];
-  const size_t b = blockIdx.x;
-  if (st.status[b] != PAYNE_LMFIT_RUNNING) return;                  // (the whole workgroup)
-  const int tid = threadIdx.x, lane = tid & (lm::kWave - 1), wave = tid / lm::kWave;
-  const int i = lane & 15, q = lane >> 4;
-  const int Km = K - P;
-  if (tid < P) coef[tid] = st.x_trial[b * (size_t)K + (size_t)(Km + tid)];
-  __syncthreads();
   const bool live = i <= K, residual = i == K;
   const int j = lm::series_index(i, Km, K);
   const float* ra = rows + (b * (size_t)(1 + Km) + (size_t)(i < Km ? 1 + i : 0)) * (size_t)ld;   // the lane's row (row 0, the model, where it has none)
   const float* fb = flux + b * (size_t)ld_f;
   const double* wb = w + b * (size_t)ld_f;
-  const int gpw = lm::groups_per_wave(n), groups = lm::groups_of(n);
-  const int g0 = wave * gpw, g1 = g0 + gpw < groups ? g0 + gpw : groups;
-  lm_d4 acc = {0.0, 0.0, 0.0, 0.0};
-  for (int grp = g0; grp < g1; ++grp) {
-    const int p = lm::pixel_of(grp, q, 0);
+  const nt::d4 acc = nt::wave_sums(n, [&](int p) PAYNE_TILE_CALLABLE {
     float a[4] = {0.0f, 0.0f, 0.0f, 0.0f}, f[4] = {0.0f, 0.0f, 0.0f, 0.0f};
-    double wv[4] = {0.0, 0.0, 0.0, 0.0}, xv[4] = {0.0, 0.0, 0.0, 0.0};
-    if (VEC && p + 3 < n) {                                         // (x holds n values and no more)
-      const double2 x01 = *reinterpret_cast<const double2*>(x + p), x23 = *reinterpret_cast<const double2*>(x + p + 2);
-      xv[0] = x01.x; xv[1] = x01.y; xv[2] = x23.x; xv[3] = x23.y;
-    } else {
-#pragma unroll
-      for (int t = 0; t < 4; ++t)
-        if (p + t < n) xv[t] = x[p + t];
+    double wv[4] = {0.0, 0.0, 0.0, 0.0}, xv[4] = {0.0, 0.0, 0.0, 0.0}, sv[4];                       // (sv: POLY only)
+    if constexpr (POLY) nt::load4<VEC>(x, p, n, p + 3 < n, xv);     // (x holds n values and no more)
+    if (p < n) {                                                    // p + 3 < ld and ld_f where VEC: both are multiples of four
+      nt::load4<VEC>(wb, p, n, true, wv);
+      if (live) nt::load4<VEC>(ra, p, n, true, a);
+      if (residual) nt::load4<VEC>(fb, p, n, true, f);
     }
-    if (VEC) {
-      if (p < n) {                                                  // p + 3 < ld and ld_f: both are multiples of four
-        const double2 w01 = *reinterpret_cast<const double2*>(wb + p), w23 = *reinterpret_cast<const double2*>(wb + p + 2);
-        wv[0] = w01.x; wv[1] = w01.y; wv[2] = w23.x; wv[3] = w23.y;
-        if (live) {
-          const float4 a4 = *reinterpret_cast<const float4*>(ra + p);
-          a[0] = a4.x; a[1] = a4.y; a[2] = a4.z; a[3] = a4.w;
-        }
-        if (residual) {
-          const float4 f4 = *reinterpret_cast<const float4*>(fb + p);
-          f[0] = f4.x; f[1] = f4.y; f[2] = f4.z; f[3] = f4.w;
-        }
-      }
-    } else {
-#pragma unroll
-      for (int t = 0; t < 4; ++t)
-        if (p + t < n) {
-          wv[t] = wb[p + t];
-          if (live) a[t] = ra[p + t];
-          if (residual) f[t] = fb[p + t];
-        }
-    }
-    double sv[4];
-    lm::series4(coef, j, P, xv, sv);
-#pragma unroll
-    for (int t = 0; t < 4; ++t) {
-      double av, bv;
-      lm::operand_pair(lm::operand_poly(i, K, a[t], f[t], sv[t]), wv[t], live && p + t < n && wv[t] != 0.0, &av, &bv);
-      acc = __builtin_amdgcn_mfma_f64_16x16x4f64(av, bv, acc, 0, 0, 0);
-    }
-  }
-#pragma unroll
-  for (int v = 0; v < 4; ++v) part[wave][(q + 4 * v) * lm::kTile + i] = acc[v];
-  __syncthreads();
-  tile[tid] = ((part[0][tid] + part[1][tid]) + part[2][tid]) + part[3][tid];
-  __syncthreads();
+    if constexpr (POLY) chebs::series4(coef, j, P, xv, sv);
+    return [=](int t, double* r, double* wt) PAYNE_TILE_CALLABLE {
+      if constexpr (POLY) *r = lm::operand_poly(i, K, a[t], f[t], sv[t]);
+      else *r = lm::operand(i, K, a[t], f[t]);
+      *wt = wv[t];
+      return live && p + t < n && wv[t] != 0.0;
+    };
+  });
+  nt::sum_waves(acc, part, tile, []() PAYNE_TILE_CALLABLE { __syncthreads(); });
   if (tid == 0) lm::update_star(st, b, K, tile, opts, box, work);
 }
-
-int fail(int code, const std::string& msg) {
-  payne::set_create_error(msg);
-  return code;
-}
-
-// Selects `device` for its scope and puts the caller's device back on the way out.
-class OnDevice {
- public:
-  explicit OnDevice(int device) {
-    (void)hipGetDevice(&prev_);
-    ok_ = hipSetDevice(device) == hipSuccess;
-  }
-  ~OnDevice() { (void)hipSetDevice(prev_); }
-  OnDevice(const OnDevice&) = delete;
-  OnDevice& operator=(const OnDevice&) = delete;
-  bool ok() const { return ok_; }
-
- private:
-  int prev_ = 0;
-  bool ok_ = false;
-};
 
 template <class T>
 bool alloc(payne_lmfit* h, T** p, size_t count) {
@@ -214,7 +100,18 @@ bool alloc(payne_lmfit* h, T** p, size_t count) {
   return true;
 }
 
-bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
+// One update of the handle's B stars; P == 0 and x == NULL (which aligned16 passes): the plain form.
+int launch_update(payne_lmfit* h, int P, const float* rows, int ld, const float* flux, const double* w, int ld_f, const double* x, int n,
+                  void* stream) {
+  OnDevice on(h->device);
+  if (!on.ok()) return PAYNE_E_HIP;
+  const bool vec = ld % 4 == 0 && ld_f % 4 == 0 && aligned16(rows) && aligned16(flux) && aligned16(w) && aligned16(x);
+  const auto kernel = P ? (vec ? payne_lmfit_update_kernel<true, true> : payne_lmfit_update_kernel<false, true>)
+                        : (vec ? payne_lmfit_update_kernel<true, false> : payne_lmfit_update_kernel<false, false>);
+  hipLaunchKernelGGL(kernel, dim3((unsigned)h->B), dim3(nt::kThreads), 0, reinterpret_cast<hipStream_t>(stream), rows, (long long)ld, flux, w,
+                     (long long)ld_f, x, n, h->K, P, h->st, h->box, h->opts);
+  return hipGetLastError() == hipSuccess ? PAYNE_OK : PAYNE_E_HIP;
+}
 
 }  // namespace
 
@@ -262,7 +159,7 @@ extern "C" int payne_lmfit_begin(payne_lmfit* h, const double* x0_dev, const dou
   if (B == 0) return PAYNE_OK;
   OnDevice on(h->device);
   if (!on.ok()) return PAYNE_E_HIP;
-  hipLaunchKernelGGL(payne_lmfit_begin_kernel, dim3((unsigned)((B + lm::kThreads - 1) / lm::kThreads)), dim3(lm::kThreads), 0,
+  hipLaunchKernelGGL(payne_lmfit_begin_kernel, dim3((unsigned)((B + nt::kThreads - 1) / nt::kThreads)), dim3(nt::kThreads), 0,
                      reinterpret_cast<hipStream_t>(stream), x0_dev, B, h->K, h->st, h->box, h->opts.lambda0);
   return hipGetLastError() == hipSuccess ? PAYNE_OK : PAYNE_E_HIP;
 }
@@ -274,17 +171,7 @@ extern "C" int payne_lmfit_update(payne_lmfit* h, const float* rows_dev, int ld,
   if (!h || n < 1 || ld < n || ld_f < n) return PAYNE_E_INVALID;
   if (h->B == 0) return PAYNE_OK;
   if (!rows_dev || !flux_dev || !w_dev) return PAYNE_E_INVALID;
-  OnDevice on(h->device);
-  if (!on.ok()) return PAYNE_E_HIP;
-  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  const bool vec = ld % 4 == 0 && ld_f % 4 == 0 && aligned16(rows_dev) && aligned16(flux_dev) && aligned16(w_dev);
-  if (vec)
-    hipLaunchKernelGGL(payne_lmfit_update_kernel<true>, dim3((unsigned)h->B), dim3(lm::kThreads), 0, st, rows_dev, (long long)ld, flux_dev,
-                       w_dev, (long long)ld_f, n, h->K, h->st, h->box, h->opts);
-  else
-    hipLaunchKernelGGL(payne_lmfit_update_kernel<false>, dim3((unsigned)h->B), dim3(lm::kThreads), 0, st, rows_dev, (long long)ld, flux_dev,
-                       w_dev, (long long)ld_f, n, h->K, h->st, h->box, h->opts);
-  return hipGetLastError() == hipSuccess ? PAYNE_OK : PAYNE_E_HIP;
+  return launch_update(h, 0, rows_dev, ld, flux_dev, w_dev, ld_f, nullptr, n, stream);
 }
 
 extern "C" int payne_lmfit_update_poly(payne_lmfit* h, int P, const float* rows_dev, int ld, const float* flux_dev, const double* w_dev,
@@ -292,17 +179,7 @@ extern "C" int payne_lmfit_update_poly(payne_lmfit* h, int P, const float* rows_
   if (!h || n < 1 || ld < n || ld_f < n || P < 1 || P > h->K) return PAYNE_E_INVALID;
   if (h->B == 0) return PAYNE_OK;
   if (!rows_dev || !flux_dev || !w_dev || !x_dev) return PAYNE_E_INVALID;
-  OnDevice on(h->device);
-  if (!on.ok()) return PAYNE_E_HIP;
-  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  const bool vec = ld % 4 == 0 && ld_f % 4 == 0 && aligned16(rows_dev) && aligned16(flux_dev) && aligned16(w_dev) && aligned16(x_dev);
-  if (vec)
-    hipLaunchKernelGGL(payne_lmfit_update_poly_kernel<true>, dim3((unsigned)h->B), dim3(lm::kThreads), 0, st, rows_dev, (long long)ld,
-                       flux_dev, w_dev, (long long)ld_f, x_dev, n, h->K, P, h->st, h->box, h->opts);
-  else
-    hipLaunchKernelGGL(payne_lmfit_update_poly_kernel<false>, dim3((unsigned)h->B), dim3(lm::kThreads), 0, st, rows_dev, (long long)ld,
-                       flux_dev, w_dev, (long long)ld_f, x_dev, n, h->K, P, h->st, h->box, h->opts);
-  return hipGetLastError() == hipSuccess ? PAYNE_OK : PAYNE_E_HIP;
+  return launch_update(h, P, rows_dev, ld, flux_dev, w_dev, ld_f, x_dev, n, stream);
 }
 
 extern "C" int payne_lmfit_result(payne_lmfit* h, double* x_best, double* chisq, double* A, double* g, double* lambda, int* status,

@@ -14,11 +14,9 @@
 //   No atomics; every sum and every list has one fixed order.
 #include <hip/hip_runtime.h>
 
-#include <cstdint>
-#include <string>
-
 #include "../../include/payne_hip.h"
-#include "ctx_api.hpp"
+#include "host_prologue.hpp"
+#include "normal_tile.hpp"
 #include "tmatch_core.hpp"
 
 namespace tq = payne::tmatch;
@@ -31,7 +29,9 @@ struct payne_tmatch {
 
 namespace {
 
-typedef double tm_d4 __attribute__((ext_vector_type(4)));
+using payne::ntile::d4;
+using payne::host::OnDevice;
+using payne::host::fail;
 
 constexpr int kStageDoubles = 2 * tq::kStars * tq::kPitchA;                              // a1, a2
 constexpr int kStageBytes = kStageDoubles * 8 + tq::kChunk * tq::kPitchT * 4;            // + the templates
@@ -62,11 +62,11 @@ __global__ void __launch_bounds__(tq::kThreads) payne_tmatch_tile_kernel(const f
 
   float fr[tq::kStarRegs], mr[tq::kTemplRegs];
   double wr[tq::kStarRegs], c0acc[tq::kStarRegs];
-  tm_d4 acc[4][2];
+  d4 acc[4][2];
 #pragma unroll
   for (int rb = 0; rb < 4; ++rb)
 #pragma unroll
-    for (int cb = 0; cb < 2; ++cb) acc[rb][cb] = tm_d4{0.0, 0.0, 0.0, 0.0};
+    for (int cb = 0; cb < 2; ++cb) acc[rb][cb] = d4{0.0, 0.0, 0.0, 0.0};
 #pragma unroll
   for (int r = 0; r < tq::kStarRegs; ++r) c0acc[r] = 0.0;
   unsigned poison = 0u;
@@ -197,28 +197,6 @@ __global__ void __launch_bounds__(tq::kStars) payne_tmatch_merge_kernel(const do
     idx[(size_t)s * topk + j] = ix[j];
   }
 }
-
-int fail(int code, const std::string& msg) {
-  payne::set_create_error(msg);
-  return code;
-}
-
-// Selects `device` for its scope and puts the caller's device back on the way out.
-class OnDevice {
- public:
-  explicit OnDevice(int device) {
-    (void)hipGetDevice(&prev_);
-    ok_ = hipSetDevice(device) == hipSuccess;
-  }
-  ~OnDevice() { (void)hipSetDevice(prev_); }
-  OnDevice(const OnDevice&) = delete;
-  OnDevice& operator=(const OnDevice&) = delete;
-  bool ok() const { return ok_; }
-
- private:
-  int prev_ = 0;
-  bool ok_ = false;
-};
 
 }  // namespace
 

@@ -4,7 +4,7 @@
 //   payne_specmlp_train_*  training the spectral networks (trainspec.TrainMod); the kernels are k_specmlp_train.hip
 //   payne_specjac_*        the spectral networks' label gradients, and payne_fisher_batch; the kernels are k_specjac.hip
 // A handle is a device number, a bag of device allocations and the kernels' argument struct.  Every entry point selects the
-// handle's device through a DeviceGuard, which puts the caller's back on every way out; the descriptors are checked by
+// handle's device through an OnDevice (host_prologue.hpp), which puts the caller's back on every way out; the descriptors are checked by
 // mlp_desc.hpp; a create call that fails leaves its message for payne_last_error(NULL).
 #include <hip/hip_runtime.h>
 
@@ -14,7 +14,7 @@
 #include <vector>
 
 #include "../../include/payne_hip.h"
-#include "ctx_api.hpp"
+#include "host_prologue.hpp"
 #include "mlp_desc.hpp"
 #include "specjac_core.hpp"
 
@@ -38,28 +38,9 @@ int payne_fisher_launch(const float* rows, int ld, int K, int n, int B, const do
 
 namespace {
 
-int fail(int code, const std::string& msg) {
-  payne::set_create_error(msg);
-  return code;
-}
+using payne::host::OnDevice;
+using payne::host::fail;
 int fail(const md::Status& s) { return fail(s.code, s.msg); }
-
-// Selects `device` for its scope and puts the caller's device back on the way out.
-class DeviceGuard {
- public:
-  explicit DeviceGuard(int device) {
-    (void)hipGetDevice(&prev_);
-    ok_ = hipSetDevice(device) == hipSuccess;
-  }
-  ~DeviceGuard() { (void)hipSetDevice(prev_); }
-  DeviceGuard(const DeviceGuard&) = delete;
-  DeviceGuard& operator=(const DeviceGuard&) = delete;
-  bool ok() const { return ok_; }
-
- private:
-  int prev_ = 0;
-  bool ok_ = false;
-};
 
 // The device allocations of a handle, made on the selected device; after the first failure `ok` is false and nothing more is tried.
 struct DeviceBag {
@@ -97,7 +78,7 @@ template <class Handle>
 void destroy(Handle* h, bool synchronise) {
   if (!h) return;
   {
-    DeviceGuard on(h->device);
+    OnDevice on(h->device);
     if (on.ok()) {
       if (synchronise) (void)hipDeviceSynchronize();
       for (void* p : h->bag.owned) (void)hipFree(p);
@@ -182,7 +163,7 @@ extern "C" int payne_lnmlp_create(int device, const payne_lnmlp_desc* d, payne_l
   if (md::Status s = md::check_lnmlp_layers(fn, d, true)) return fail(s);
   if (md::Status s = md::check_lnmlp_limits(fn, d)) return fail(s);
 
-  DeviceGuard on(device);
+  OnDevice on(device);
   if (!on.ok()) return fail(PAYNE_E_HIP, "payne_lnmlp_create: hipSetDevice");
   payne_lnmlp* h = new payne_lnmlp;
   h->device = device;
@@ -229,7 +210,7 @@ extern "C" int payne_lnmlp_eval(payne_lnmlp* h, const double* x_dev, int ld_x, i
   if (ld_x < h->net.L[0].n_in || ld_y < h->net.L[h->net.n_layers - 1].n_out) return PAYNE_E_INVALID;
   if (N == 0) return PAYNE_OK;
   if (!x_dev || !y_dev) return PAYNE_E_INVALID;
-  DeviceGuard on(h->device);
+  OnDevice on(h->device);
   if (!on.ok()) return PAYNE_E_HIP;
   return payne_lnmlp_launch(h->net, x_dev, ld_x, N, y_dev, ld_y, stream);
 }
@@ -258,7 +239,7 @@ extern "C" int payne_lnmlp_train_create(int device, const payne_lnmlp_desc* d, c
   if (md::Status s = md::check_optimiser(fn, o->max_rows, o->lr, o->beta1, o->beta2, o->eps)) return fail(s);
   if (md::Status s = md::check_lnmlp_limits(fn, d)) return fail(s);
 
-  DeviceGuard on(device);
+  OnDevice on(device);
   if (!on.ok()) return fail(PAYNE_E_HIP, "payne_lnmlp_train_create: hipSetDevice");
   payne_lnmlp_train* h = new payne_lnmlp_train;
   h->device = device;
@@ -295,7 +276,7 @@ extern "C" int payne_lnmlp_train_step(payne_lnmlp_train* h, const float* x_dev, 
   if (rc) return rc;
   if (N > h->opts.max_rows) return PAYNE_E_INVALID;
   if (N == 0) return PAYNE_OK;
-  DeviceGuard on(h->device);
+  OnDevice on(h->device);
   if (!on.ok()) return PAYNE_E_HIP;
   const int d_out = h->net.L[h->net.n_layers - 1].n_out;
   h->last_stream = stream;
@@ -315,7 +296,7 @@ extern "C" int payne_lnmlp_train_loss(payne_lnmlp_train* h, const float* x_dev, 
   if (rc) return rc;
   if (N == 0) return PAYNE_OK;
   if (!loss_dev) return PAYNE_E_INVALID;
-  DeviceGuard on(h->device);
+  OnDevice on(h->device);
   if (!on.ok()) return PAYNE_E_HIP;
   const double denom = (double)N * (double)h->net.L[h->net.n_layers - 1].n_out;
   h->last_stream = stream;
@@ -335,7 +316,7 @@ extern "C" int payne_lnmlp_train_get(payne_lnmlp_train* h, int what, payne_lnmlp
     if (L.n_in != h->net.L[l].n_in || L.n_out != h->net.L[l].n_out || !L.w || !L.b || (!last && (!L.ln_gain || !L.ln_bias)))
       return PAYNE_E_INVALID;
   }
-  DeviceGuard on(h->device);
+  OnDevice on(h->device);
   if (!on.ok()) return PAYNE_E_HIP;
   Fetch take(h->last_stream);
   for (int l = 0; l < h->net.n_layers; ++l) {
@@ -385,7 +366,7 @@ extern "C" int payne_specmlp_train_create(int device, const payne_specmlp_desc* 
   if (md::Status s = md::check_optimiser(fn, o->max_rows, o->lr, o->beta1, o->beta2, o->eps)) return fail(s);
   if (md::Status s = md::check_specmlp_limits(fn, d, sp::kMaxIn, "inputs")) return fail(s);
 
-  DeviceGuard on(device);
+  OnDevice on(device);
   if (!on.ok()) return fail(PAYNE_E_HIP, "payne_specmlp_train_create: hipSetDevice");
   payne_specmlp_train* h = new payne_specmlp_train;
   h->device = device;
@@ -413,7 +394,7 @@ extern "C" int payne_specmlp_train_step(payne_specmlp_train* h, const float* x_d
   if (rc) return rc;
   if (N > h->opts.max_rows) return PAYNE_E_INVALID;
   if (N == 0) return PAYNE_OK;
-  DeviceGuard on(h->device);
+  OnDevice on(h->device);
   if (!on.ok()) return PAYNE_E_HIP;
   h->last_stream = stream;
   rc = payne_specmlp_train_forward(h->net, x_dev, ld_x, t_dev, ld_t, nullptr, 0, N, 1, stream);
@@ -431,7 +412,7 @@ extern "C" int payne_specmlp_train_loss(payne_specmlp_train* h, const float* x_d
   if (rc) return rc;
   if (N == 0) return PAYNE_OK;
   if (!loss_dev) return PAYNE_E_INVALID;
-  DeviceGuard on(h->device);
+  OnDevice on(h->device);
   if (!on.ok()) return PAYNE_E_HIP;
   h->last_stream = stream;
   return for_row_chunks(N, h->rows, [&](int r0, int n) {
@@ -446,7 +427,7 @@ extern "C" int payne_specmlp_train_predict(payne_specmlp_train* h, const float* 
   if (ld_x < h->net.L[0].n_in || ld_y < h->net.L[h->net.n_layers - 1].n_out) return PAYNE_E_INVALID;
   if (N == 0) return PAYNE_OK;
   if (!x_dev || !y_dev) return PAYNE_E_INVALID;
-  DeviceGuard on(h->device);
+  OnDevice on(h->device);
   if (!on.ok()) return PAYNE_E_HIP;
   h->last_stream = stream;
   return for_row_chunks(N, h->rows, [&](int r0, int n) {
@@ -468,7 +449,7 @@ extern "C" int payne_specmlp_train_get(payne_specmlp_train* h, int what, payne_s
     const payne_specmlp_layer& L = host_out->layers[l];
     if (L.n_in != h->net.L[l].n_in || L.n_out != h->net.L[l].n_out || !L.w || !L.b) return PAYNE_E_INVALID;
   }
-  DeviceGuard on(h->device);
+  OnDevice on(h->device);
   if (!on.ok()) return PAYNE_E_HIP;
   Fetch take(h->last_stream);
   for (int l = 0; l < h->net.n_layers; ++l) {
@@ -505,7 +486,7 @@ extern "C" int payne_specjac_create(int device, const payne_specmlp_desc* d, con
     if (!std::isfinite(xmin[k]) || !std::isfinite(xmax[k]) || xmin[k] == xmax[k])
       return fail(PAYNE_E_INVALID, "payne_specjac_create: label " + std::to_string(k) + ": xmin / xmax not finite or equal");
 
-  DeviceGuard on(device);
+  OnDevice on(device);
   if (!on.ok()) return fail(PAYNE_E_HIP, "payne_specjac_create: hipSetDevice");
   payne_specjac* h = new payne_specjac;
   h->device = device;
@@ -549,7 +530,7 @@ extern "C" int payne_specjac_eval(payne_specjac* h, const double* labels_dev, in
   if (ld_x < d_in || ld_j < d_out || (y_dev && ld_y < d_out)) return PAYNE_E_INVALID;
   if (N == 0) return PAYNE_OK;
   if (!labels_dev || !jac_dev) return PAYNE_E_INVALID;
-  DeviceGuard on(h->device);
+  OnDevice on(h->device);
   if (!on.ok()) return PAYNE_E_HIP;
   sj::JacNet net = h->net;
   if (flags & PAYNE_JAC_ENCODED)
@@ -566,7 +547,7 @@ extern "C" int payne_fisher_batch(int device, const float* rows_dev, int ld, int
   if (K > sj::kMaxFisherRows) return PAYNE_E_UNSUPPORTED;
   if (B == 0) return PAYNE_OK;
   if (!rows_dev || !w_dev || !F_dev) return PAYNE_E_INVALID;
-  DeviceGuard on(device);
+  OnDevice on(device);
   if (!on.ok()) return PAYNE_E_HIP;
   return payne_fisher_launch(rows_dev, ld, K, n, B, w_dev, F_dev, stream);
 }
