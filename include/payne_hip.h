@@ -567,6 +567,60 @@ int payne_lmfit_result(payne_lmfit* h, double* x_best, double* chisq, double* A,
                        unsigned* at_bound, void* stream);
 void payne_lmfit_destroy(payne_lmfit* h);
 
+/* ---- SED fits for many stars: the magnitudes' derivatives and a whole Levenberg-Marquardt fit in one launch ----
+ * payne_sedfit_*: a handle of its own on the per-filter photometric nets (6 -> H -> H -> 1, sigmoids, fp64 arithmetic on fp32
+ * weights).  The magnitudes are the likelihood's (GenMod.genphot / genphot_scaled: Rv = 3.1, at Av >= 5 the nets at Av = 0 and the
+ * high-Av table), in its own parameters: a row is [Teff, logg, FeH, aFe, logR, Dist, Av] (photscale 0, 7 values) or
+ * [Teff, logg, FeH, aFe, logA, Av] (photscale 1, 6 values).  csrc/sedfit_core.hpp holds the arithmetic; in short:
+ *   net      forward mode through one filter's net: next to a star's row of activations run the tangents of the network inputs
+ *            among Teff, logg, FeH, aFe, Av that are asked for.  A workgroup takes one filter for a block of stars: the rows of its
+ *            48-row tile are (star, tangent), 48 / (1 + Kn) stars for Kn tangents; both hidden layers' products run on the fp64
+ *            matrix instruction, s(z) and s'(z) = a (1 - a) are applied in LDS, layer 3 and the chain rule are fp64 fma.  The
+ *            width is padded to a multiple of 16 with zero weights, which is exact.
+ *   chain    d m / d Teff = -dBC/dTeff - 10 / (Teff ln 10); d m / d (logg, FeH, aFe, Av) = -dBC/d(the label); d m / d logR = -5;
+ *            d m / d Dist = 5 / (Dist ln 10); d m / d logA = 5.  At Av >= 5, dBC/dAv = -c1 (c2 + c3 Rv + c4 Rv^2) of the table.
+ *            Where a magnitude is NaN (a NaN label, no table row at Av >= 5) so are its derivatives.
+ *   fit      per star R = [d m / d theta_free ; obs - m] and G = R diag(w) R^T summed over the filters in ascending order, one fma
+ *            an element and filter, no atomics; a filter with w == 0 is ignored whatever obs or the model hold there.  A Gaussian
+ *            prior on free parameter k adds 1 / sigma_k^2 to A_kk, (mu_k - theta_k) / sigma_k^2 to g_k and its term to chi^2.
+ *            The step behind G is payne_lmfit_update's, with its rules and statuses (decide, solve, trial, stop above).
+ * A star's bits depend neither on its place in a tile nor on the batch; the same inputs give the same bits.
+ * payne_sedfit_create: HOST arrays in fastANN's stacking, w1 [F][H][6], b1 [F][H], w2 [F][H][H], b2 [F][H], w3 [F][H], b3 [F], fp32;
+ * xmin, xmax fp64 [6]; hiav fp64 [F][5] or NULL (then a magnitude at Av >= 5 is NaN).  The handle uploads copies of its own.
+ *   PAYNE_E_INVALID      null out or array (but hiav), F < 1, H < 1, an xmin / xmax that is not finite or xmax <= xmin
+ *   PAYNE_E_UNSUPPORTED  H > 64
+ * payne_sedfit_jac: one launch, workgroups over (filter, block of 8 stars).  pars_dev DEVICE fp64 [B][7 | 6]; mags_dev DEVICE fp64
+ * [B][F]; dmags_dev DEVICE fp64 [B][F][7 | 6], the derivative with respect to every parameter of the row.
+ *   PAYNE_E_INVALID      null handle, B < 0, photscale other than 0 / 1, null pars_dev / mags_dev / dmags_dev with B > 0
+ * payne_sedfit_run: the whole fit in one launch.  A workgroup owns 48 / (1 + Kn) stars (Kn: the free parameters among Teff, logg,
+ * FeH, aFe, Av) from their first evaluation to their last: it loops over at most opts.maxiter evaluations, in each over the
+ * filters, whose weights it streams into LDS, and ends early when none of its stars is RUNNING.  free_mask: bit p set = parameter p
+ * of the row is fitted, K of them, in ascending order wherever an array has K entries; the others are read from start_dev and
+ * passed through.  start_dev DEVICE fp64 [B][7 | 6]; obs_dev, w_dev DEVICE fp64 [B][F], the magnitudes and 1 / sigma^2; lo, hi HOST
+ * fp64 [K], the box (the start is clipped into it); prior_mu_dev, prior_sigma_dev DEVICE fp64 [B][K] or both NULL, a sigma that is
+ * not finite and positive meaning no prior on that parameter; opts NULL: payne_lmfit_create's defaults.  Outputs, DEVICE: pars_dev
+ * fp64 [B][7 | 6] (x_best), status_dev int [B]; and, each may be NULL, chisq_dev fp64 [B] (priors included), A_dev fp64 [B][K][K]
+ * (the normal matrix at x_best, priors included), niter_dev int [B] (evaluations), at_bound_dev unsigned [B] (bit k: free parameter k),
+ * nfilt_dev int [B] (filters with w != 0).  A star whose counting filters plus priors are fewer than K is PAYNE_SEDFIT_TOO_FEW: no
+ * evaluation, pars the clipped start, chi^2 NaN, A zero.  A NaN in the start or in obs at a counting filter: PAYNE_LMFIT_NAN.
+ *   PAYNE_E_INVALID      null handle, B < 0, photscale other than 0 / 1, free_mask 0 or with a bit beyond the row, null lo / hi, lo >=
+ *                        hi or not finite, Av free with hi >= 5 (the model jumps there), an option payne_lmfit_create rejects, only
+ *                        one of prior_mu_dev / prior_sigma_dev, null start_dev / obs_dev / w_dev / pars_dev / status_dev with B > 0
+ * B == 0 succeeds and does nothing; both calls are enqueued on `stream` and do not wait.  payne_sedfit_destroy: NULL is allowed. */
+#define PAYNE_SEDFIT_TOO_FEW 6
+#define PAYNE_SEDFIT_MAX_K 7
+
+typedef struct payne_sedfit payne_sedfit;
+
+int payne_sedfit_create(int device, int F, int H, const float* w1, const float* b1, const float* w2, const float* b2, const float* w3,
+                        const float* b3, const double* xmin, const double* xmax, const double* hiav, payne_sedfit** out);
+int payne_sedfit_jac(payne_sedfit* h, const double* pars_dev, int B, int photscale, double* mags_dev, double* dmags_dev, void* stream);
+int payne_sedfit_run(payne_sedfit* h, int photscale, unsigned free_mask, const double* start_dev, const double* obs_dev,
+                     const double* w_dev, int B, const double* lo, const double* hi, const double* prior_mu_dev,
+                     const double* prior_sigma_dev, const payne_lmfit_opts* opts, double* pars_dev, double* chisq_dev, double* A_dev,
+                     int* status_dev, int* niter_dev, unsigned* at_bound_dev, int* nfilt_dev, void* stream);
+void payne_sedfit_destroy(payne_sedfit* h);
+
 /* ---- template-bank chi^2 search: every star against every template, the best few per star ----
  * payne_tmatch_*: chi^2[s][t] = sum_p w[s][p] (flux[s][p] - m[t][p])^2 for N stars and M templates on one pixel grid, expanded into
  * one N x M matrix product over 2 n terms on the fp64 matrix instruction, and per star the topk smallest (starting points for

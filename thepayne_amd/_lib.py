@@ -44,7 +44,8 @@ SYMBOLS = ["payne_version", "payne_ctx_create", "payne_ctx_set_obs", "payne_ctx_
            "payne_lmfit_create", "payne_lmfit_begin", "payne_lmfit_trial", "payne_lmfit_update", "payne_lmfit_update_poly", "payne_lmfit_result",
            "payne_lmfit_destroy",
            "payne_tmatch_create", "payne_tmatch_match", "payne_tmatch_chunk", "payne_tmatch_destroy",
-           "payne_contfit_batch"]
+           "payne_contfit_batch",
+           "payne_sedfit_create", "payne_sedfit_jac", "payne_sedfit_run", "payne_sedfit_destroy"]
 
 PAYNE_MAX_DIM, PAYNE_MAX_FIXED = 24, 16
 PRIOR_UNIFORM, PRIOR_GAUSSIAN, PRIOR_TGAUSSIAN, PRIOR_EXP, PRIOR_TEXP, PRIOR_LOGUNIFORM, PRIOR_TABLE = range(7)
@@ -126,6 +127,7 @@ class ContfitOpts(C.Structure):
 JAC_ENCODED = 1
 LMFIT_RUNNING, LMFIT_CONVERGED, LMFIT_STALLED, LMFIT_MAXITER, LMFIT_SINGULAR, LMFIT_NAN = range(6)
 LMFIT_STATUS_NAMES = ("RUNNING", "CONVERGED", "STALLED", "MAXITER", "SINGULAR", "NAN")
+SEDFIT_TOO_FEW, SEDFIT_MAX_K, SEDFIT_MAX_H = 6, 7, 64       # payne_sedfit_run's own status beside LMFIT_*
 LMFIT_MAX_K = 15
 TMATCH_MAX_TOPK = 8
 CONTFIT_OK, CONTFIT_NONPOSITIVE, CONTFIT_TOO_FEW, CONTFIT_SINGULAR, CONTFIT_NAN, CONTFIT_BAD_MODEL = range(6)
@@ -299,6 +301,15 @@ def load(path=None):
                                         C.c_int, C.c_int, C.POINTER(ContfitOpts), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                         C.c_void_p, C.c_void_p, C.c_longlong, C.c_void_p]
     lib.payne_contfit_batch.restype = C.c_int
+    lib.payne_sedfit_create.argtypes = [C.c_int, C.c_int, C.c_int] + [C.c_void_p] * 9 + [C.POINTER(ctxp)]
+    lib.payne_sedfit_create.restype = C.c_int
+    lib.payne_sedfit_jac.argtypes = [ctxp, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.payne_sedfit_jac.restype = C.c_int
+    lib.payne_sedfit_run.argtypes = [ctxp, C.c_int, C.c_uint, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
+                                     C.c_void_p, C.POINTER(LmfitOpts)] + [C.c_void_p] * 8
+    lib.payne_sedfit_run.restype = C.c_int
+    lib.payne_sedfit_destroy.argtypes = [ctxp]
+    lib.payne_sedfit_destroy.restype = None
     lib.payne_ctx_destroy.argtypes = [ctxp]
     lib.payne_ctx_destroy.restype = None
     lib.payne_last_error.argtypes = [ctxp]

@@ -1,0 +1,1 @@
+from .sedfit import SEDFit  # noqa: F401
