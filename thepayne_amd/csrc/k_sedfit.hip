@@ -1,13 +1,13 @@
 // k_sedfit.hip -- payne_sedfit_*: the photometric magnitudes' derivatives and the SED fit of many stars (include/payne_hip.h).  The
 // arithmetic is sedfit_core.hpp, which runs on the host too (tests/emul/sedfit_emul.cpp); the step is lmfit_core.hpp's update_star.
 //
-//   sedfit_filter             one filter's net for the stars of a workgroup, sed_tile's scheme (sed_core.hpp) with tangent rows: the
-//     rows of the 48-row tile X are (star, tangent), star s at rows s (1 + Kn) ..  Layer 1 runs on the stars' encoded labels
-//     (Xin [48][8], K = 6 padded to 8) and lands in the stars' value rows; the tangent rows behind it are a1 (1 - a1) times the
-//     table W1[:, d] / (xmax_d - xmin_d), a product per element.  Layer 2 runs on all 48 rows, the bias on the value rows only.
-//     Both are v_mfma_f64_16x16x4_f64 with sed_tile's operand map; the raw sums go back to LDS, where one thread per (star, unit)
-//     applies s(z) to the value row (sed_sigmoid_n, four side by side) and a (1 - a) to the Kn tangent rows above it.  Layer 3 is a
-//     dot product per row, sixteen units a wave, the four partial sums added in wave order by whoever reads them.
+//   sedfit_filter             one filter's net for the stars of a workgroup on the photometric nets' tile (sed_tile.hpp) with tangent
+//     rows: the rows of the 48-row tile X are (star, tangent), star s at rows s (1 + Kn) ..  Layer 1 runs on the stars' encoded
+//     labels (Xin [48][8], K = 6 padded to 8) and lands in the stars' value rows; the tangent rows behind it are a1 (1 - a1) times
+//     the table W1[:, d] / (xmax_d - xmin_d), a product per element.  Layer 2 runs on all 48 rows, the bias on the value rows only.
+//     Both are the tile's sed_mfma; the raw sums go back to LDS, where one thread per (star, unit) applies s(z) to the value row
+//     (sed_sigmoid_n, four side by side) and a (1 - a) to the Kn tangent rows above it.  Layer 3 is the tile's, the four partial
+//     sums added in wave order by whoever reads them.
 //   payne_sedfit_jac_kernel   a workgroup per (filter, 8 stars), all five tangents; eight threads apply the chain rule and store.
 //   payne_sedfit_run_kernel   a workgroup per 48 / (1 + Kn) stars for the whole fit: for eval < maxiter { for filter { sedfit_filter;
 //     one thread a star forms R; one thread per (star, i, j) adds R_i w R_j to G in LDS }; one thread a star adds the priors and
@@ -28,11 +28,11 @@ namespace lm = payne::lmfit;
 
 namespace {
 
+using payne::host::DeviceBag;
 using payne::host::OnDevice;
 using payne::host::fail;
 
-constexpr int kThreads = 256;
-static_assert(sf::kMaxH == kSedMaxH && sf::kTileRows == kSedCandsMax, "the tile is sed_core.hpp's");
+constexpr int kThreads = kSedThreads;
 
 // The handle's device copies: the width padded to Hp with zero weights.
 struct Tables {
@@ -46,18 +46,18 @@ struct Tables {
   double xmin[sf::kNetIn], xden[sf::kNetIn];
 };
 
-// LDS of a workgroup with S stars and K fitted parameters (K = 0: payne_sedfit_jac), in bytes from the start.
+// LDS of a workgroup with S stars and K fitted parameters (K = 0: payne_sedfit_jac), in bytes from the start: the tile (SedTileLds),
+// then what is the fit's own.
 struct Layout {
-  size_t X, Xin, W1T, Pt, pars, terms, dm, dbc, G, R, wt, xb, xt, A, g, chisq, lambda, W2, W1, Bv, hi, status, niter, at_bound, nfilt, total;
+  size_t tile, Xin, W1T, pars, terms, dm, dbc, G, R, wt, xb, xt, A, g, chisq, lambda, hi, status, niter, at_bound, nfilt, total;
 };
 __host__ __device__ inline Layout layout_of(int S, int K) {
   Layout L;
   size_t o = 0;
   auto take = [&](size_t bytes) { const size_t at = o; o += (bytes + 15) & ~(size_t)15; return at; };
-  L.X = take((size_t)kSedCandsMax * kSedPitchA * 8);
+  L.tile = take(SedTileLds::bytes);
   L.Xin = take((size_t)kSedCandsMax * 8 * 8);
   L.W1T = take((size_t)sf::kMaxTan * kSedMaxH * 8);
-  L.Pt = take((size_t)4 * kSedCandsMax * 8);
   L.pars = take((size_t)S * sf::kMaxK * 8);
   L.terms = take((size_t)S * sizeof(sf::RowTerms));
   L.dm = take((size_t)S * sf::kMaxK * 8);
@@ -71,9 +71,6 @@ __host__ __device__ inline Layout layout_of(int S, int K) {
   L.g = take((size_t)S * K * 8);
   L.chisq = take((size_t)S * 8);
   L.lambda = take((size_t)S * 8);
-  L.W2 = take((size_t)kSedMaxH * kSedPitchW * 4);
-  L.W1 = take((size_t)8 * kSedPitchW * 4);
-  L.Bv = take((size_t)3 * kSedMaxH * 4);
   L.hi = take((size_t)S * 4);
   L.status = take((size_t)S * 4);
   L.niter = take((size_t)S * 4);
@@ -82,7 +79,7 @@ __host__ __device__ inline Layout layout_of(int S, int K) {
   L.total = o;
   return L;
 }
-// update_star's workspace lies on X, which nobody needs between the last filter of an evaluation and the first of the next
+// update_star's workspace lies on the tile's X, which nobody needs between the last filter of an evaluation and the first of the next
 constexpr bool work_fits_on_x() {
   for (int Kn = 0; Kn <= sf::kMaxTan; ++Kn) {
     const int K = Kn + 2 < sf::kMaxK ? Kn + 2 : sf::kMaxK;                  // the most parameters with Kn of them network inputs
@@ -95,31 +92,18 @@ static_assert(work_fits_on_x(), "X holds the stars' workspaces");
 template <class T>
 __device__ __forceinline__ T* at(unsigned char* smem, size_t off) { return reinterpret_cast<T*>(smem + off); }
 
-__device__ __forceinline__ double row_sum(const double* Pt, int r) {
-  return ((Pt[r] + Pt[kSedCandsMax + r]) + Pt[2 * kSedCandsMax + r]) + Pt[3 * kSedCandsMax + r];
-}
-
 // Filter f for S stars with Kn tangents each (net inputs tan_in[t]).  In: Xin [s][8], the stars' encoded labels (columns 6, 7 and
 // the rows from S on zero).  Out: Pt [4][48], the waves' partial sums of w3 . X[row]; a barrier follows them.  The first barrier
 // in here is also the one behind which the caller's writes to Xin are seen and the previous filter's Pt is free.
 __device__ inline void sedfit_filter(const Tables& T, int f, int S, int Kn, const int* tan_in, unsigned char* smem, const Layout& L) {
-  typedef float f4 __attribute__((ext_vector_type(4)));
   const int Hp = T.Hp, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  double* X = at<double>(smem, L.X);
+  const SedTileView t = sed_tile_view(smem + L.tile);
+  double* X = t.X;
   const double* Xin = at<double>(smem, L.Xin);
   double* W1T = at<double>(smem, L.W1T);
-  double* Pt = at<double>(smem, L.Pt);
-  float* W2 = at<float>(smem, L.W2);
-  float* W1 = at<float>(smem, L.W1);
-  float* Bv = at<float>(smem, L.Bv);
   const int rps = 1 + Kn;                                                   // rows a star
-  // ---- requests (sed_tile's): the W2 tile in 16-byte pieces, W1, the tangent table, the three vectors
-  const f4* w2g = reinterpret_cast<const f4*>(T.w2t + (size_t)f * Hp * Hp);
-  const int n4 = (Hp * Hp) >> 2, hq4 = Hp >> 2;
-  constexpr int WPT = kSedMaxH * kSedMaxH / 4 / kThreads;
-  f4 wreg[WPT];
-#pragma unroll
-  for (int q = 0; q < WPT; ++q) { const int i = tid + kThreads * q; wreg[q] = w2g[i < n4 ? i : n4 - 1]; }
+  // ---- requests: the W2 tile and the three vectors, W1, the tangent table
+  const SedWeights wr = sed_weights_request(T.w2t + (size_t)f * Hp * Hp, Hp, T.b1 + (size_t)f * Hp, T.b2 + (size_t)f * Hp, T.w3 + (size_t)f * Hp);
   float w1reg[2];
   double w1treg[2];
 #pragma unroll
@@ -128,26 +112,15 @@ __device__ inline void sedfit_filter(const Tables& T, int f, int S, int Kn, cons
     w1reg[q] = T.w1[(size_t)f * 8 * Hp + (i < 8 * Hp ? i : 0)];
     w1treg[q] = T.w1t[(size_t)f * sf::kMaxTan * Hp + (i < sf::kMaxTan * Hp ? i : 0)];
   }
-  float vreg = 0.f;
-  if (tid < 3 * kSedMaxH) {
-    const int which = tid / kSedMaxH, h = tid - which * kSedMaxH;
-    const float* src = which == 0 ? T.b1 : (which == 1 ? T.b2 : T.w3);
-    vreg = src[(size_t)f * Hp + (h < Hp ? h : 0)];
-  }
   __syncthreads();
   // ---- commit to LDS
-#pragma unroll
-  for (int q = 0; q < WPT; ++q) {
-    const int i = tid + kThreads * q;
-    if (i < n4) { const int k = i / hq4, h4 = i - k * hq4; *reinterpret_cast<f4*>(W2 + k * kSedPitchW + 4 * h4) = wreg[q]; }
-  }
+  sed_weights_commit(wr, Hp, t);
 #pragma unroll
   for (int q = 0; q < 2; ++q) {
     const int i = tid + kThreads * q;
-    if (i < 8 * Hp) { const int d = i / Hp, h = i - d * Hp; W1[d * kSedPitchW + h] = w1reg[q]; }
+    if (i < 8 * Hp) { const int d = i / Hp, h = i - d * Hp; t.W1[d * kSedPitchW + h] = w1reg[q]; }
     if (i < sf::kMaxTan * Hp) { const int d = i / Hp, h = i - d * Hp; W1T[d * kSedMaxH + h] = w1treg[q]; }
   }
-  if (tid < 3 * kSedMaxH) Bv[tid] = vreg;
   __syncthreads();
   const int nt_n = Hp >> 4, li = lane & 15, lk = lane >> 4;
   const bool on = wave < nt_n;                                              // wave w owns the 16-column tile w (or none)
@@ -184,17 +157,11 @@ __device__ inline void sedfit_filter(const Tables& T, int f, int S, int Kn, cons
   // ---- layer 1 (photANN.py:127): rows are stars
   {
     sed_d4 acc[MT];
-    const double bz = (double)Bv[16 * nt + li];
+    const double bz = (double)t.Bv[16 * nt + li];
 #pragma unroll
     for (int mt = 0; mt < MT; ++mt) acc[mt] = (sed_d4){bz, bz, bz, bz};
     if (on) {
-#pragma unroll
-      for (int ks = 0; ks < 2; ++ks) {
-        const double bfrag = (double)W1[(4 * ks + lk) * kSedPitchW + 16 * nt + li];
-#pragma unroll
-        for (int mt = 0; mt < MT; ++mt)
-          acc[mt] = __builtin_amdgcn_mfma_f64_16x16x4f64(Xin[(16 * mt + li) * 8 + 4 * ks + lk], bfrag, acc[mt], 0, 0, 0);
-      }
+      sed_mfma<MT, 2>(Xin, 8, t.W1, 2, nt, li, lk, acc);
 #pragma unroll
       for (int mt = 0; mt < MT; ++mt)
 #pragma unroll
@@ -210,32 +177,12 @@ __device__ inline void sedfit_filter(const Tables& T, int f, int S, int Kn, cons
   // ---- layer 2 (:128): all rows, the bias on the value rows
   {
     sed_d4 acc[MT];
-    const double bz = (double)Bv[kSedMaxH + 16 * nt + li];
+    const double bz = (double)t.Bv[kSedMaxH + 16 * nt + li];
 #pragma unroll
     for (int mt = 0; mt < MT; ++mt)
 #pragma unroll
       for (int v = 0; v < 4; ++v) acc[mt][v] = (16 * mt + lk + 4 * v) % rps == 0 ? bz : 0.0;
-    if (on) {
-      constexpr int KS = kSedMaxH / 4;
-      float bfr[KS];
-      double afr[MT][KS];
-      const int ks_n = Hp >> 2;
-#pragma unroll
-      for (int ks = 0; ks < KS; ++ks) {
-        const int k0 = 4 * (ks < ks_n ? ks : 0);
-        bfr[ks] = W2[(k0 + lk) * kSedPitchW + 16 * nt + li];
-#pragma unroll
-        for (int mt = 0; mt < MT; ++mt) afr[mt][ks] = X[(16 * mt + li) * kSedPitchA + k0 + lk];
-      }
-#pragma unroll
-      for (int ks = 0; ks < KS; ++ks) {
-        if (ks < ks_n) {
-          const double bfrag = (double)bfr[ks];
-#pragma unroll
-          for (int mt = 0; mt < MT; ++mt) acc[mt] = __builtin_amdgcn_mfma_f64_16x16x4f64(afr[mt][ks], bfrag, acc[mt], 0, 0, 0);
-        }
-      }
-    }
+    if (on) sed_mfma<MT, kSedMaxH / 4>(X, kSedPitchA, t.W2, Hp >> 2, nt, li, lk, acc);
     __syncthreads();                                                        // every wave has read X
     if (on) {
 #pragma unroll
@@ -247,15 +194,8 @@ __device__ inline void sedfit_filter(const Tables& T, int f, int S, int Kn, cons
   __syncthreads();
   activate(false);
   __syncthreads();
-  // ---- layer 3 (:129-131): wave w sums the units 16 w .. 16 w + 15 of row `lane`
-  if (lane < kSedCandsMax) {
-    double part = 0.0;
-    if (on) {
-#pragma unroll
-      for (int q = 0; q < 16; ++q) part = fma((double)Bv[2 * kSedMaxH + 16 * wave + q], X[lane * kSedPitchA + 16 * wave + q], part);
-    }
-    Pt[wave * kSedCandsMax + lane] = part;
-  }
+  // ---- layer 3 (:129-131)
+  sed_layer3_partials(t, lane, wave, on);
   __syncthreads();
 }
 
@@ -274,13 +214,13 @@ __device__ __forceinline__ void stage_star(const Tables& T, int photscale, const
 
 // Star s behind sedfit_filter: the magnitude of filter f and its derivatives (dm [P] in LDS) from the tile's row sums.
 __device__ __forceinline__ double chain_star(const Tables& T, const sf::Plan& pl, int f, int s, unsigned char* smem, const Layout& L) {
-  const double* Pt = at<double>(smem, L.Pt);
+  const double* Pt = sed_tile_view(smem + L.tile).Pt;
   double* dbc = at<double>(smem, L.dbc) + s * sf::kMaxTan;
   const int r0 = s * (1 + pl.Kn);
-  const double bc = (double)T.b3[f] + row_sum(Pt, r0);
+  const double bc = (double)T.b3[f] + sed_row_sum(Pt, r0);
   for (int d = 0; d < sf::kMaxTan; ++d) {
     const int t = pl.tan_of[d < 4 ? d : pl.P - 1];
-    dbc[d] = t >= 0 ? row_sum(Pt, r0 + 1 + t) : 0.0;
+    dbc[d] = t >= 0 ? sed_row_sum(Pt, r0 + 1 + t) : 0.0;
   }
   double m;
   sf::mag_grad(pl.photscale, at<sf::RowTerms>(smem, L.terms)[s], at<double>(smem, L.pars)[s * sf::kMaxK + pl.P - 1], bc, dbc, at<int>(smem, L.hi)[s] != 0,
@@ -389,7 +329,7 @@ __global__ void __launch_bounds__(kThreads) payne_sedfit_run_kernel(const Tables
     __syncthreads();
     if (live && st.status[tid] == PAYNE_LMFIT_RUNNING) {
       sf::add_priors(G + tid * tileK, K, st.x_trial + (size_t)tid * K, mu, sig);
-      lm::update_star(st, (size_t)tid, K, G + tid * tileK, opts, box, at<double>(smem, L.X) + tid * sf::work_doubles(K));
+      lm::update_star(st, (size_t)tid, K, G + tid * tileK, opts, box, sed_tile_view(smem + L.tile).X + tid * sf::work_doubles(K));
     }
   }
   __syncthreads();
@@ -414,20 +354,10 @@ __global__ void __launch_bounds__(kThreads) payne_sedfit_run_kernel(const Tables
 struct payne_sedfit {
   int device = 0, F = 0, H = 0;
   Tables T;
-  std::vector<void*> owned;
+  DeviceBag bag;
 };
 
 namespace {
-
-template <class V>
-bool upload(payne_sedfit* h, const std::vector<V>& host, const V** dev) {
-  void* p = nullptr;
-  if (hipMalloc(&p, host.size() * sizeof(V)) != hipSuccess) return false;
-  h->owned.push_back(p);
-  if (hipMemcpy(p, host.data(), host.size() * sizeof(V), hipMemcpyHostToDevice) != hipSuccess) return false;
-  *dev = static_cast<const V*>(p);
-  return true;
-}
 
 size_t max_lds_bytes() {
   size_t m = 0;
@@ -452,7 +382,7 @@ extern "C" int payne_sedfit_create(int device, int F, int H, const float* w1, co
     if (!sf::finite(xmin[d]) || !sf::finite(xmax[d]) || !(xmin[d] < xmax[d])) return fail(PAYNE_E_INVALID, "payne_sedfit_create: xmin / xmax");
   OnDevice on(device);
   if (!on.ok()) return fail(PAYNE_E_HIP, "payne_sedfit_create: hipSetDevice");
-  const int Hp = sf::padded_width(H);
+  const int Hp = sed_padded_width(H);
   const size_t f_n = (size_t)F, hp = (size_t)Hp;
   std::vector<float> W1(f_n * 8 * hp, 0.f), B1(f_n * hp, 0.f), W2(f_n * hp * hp, 0.f), B2(f_n * hp, 0.f), W3(f_n * hp, 0.f), B3(b3, b3 + F);
   std::vector<double> W1T(f_n * sf::kMaxTan * hp, 0.0);
@@ -476,14 +406,15 @@ extern "C" int payne_sedfit_create(int device, int F, int H, const float* w1, co
       B1[f * hp + hh] = b1[u];
       B2[f * hp + hh] = b2[u];
       W3[f * hp + hh] = w3[u];
-      for (int k = 0; k < H; ++k) W2[(f * hp + k) * hp + hh] = w2[u * H + k];   // [k][h] from fastANN's [h][k]
     }
-  bool ok = upload(h, W1, &T.w1) && upload(h, B1, &T.b1) && upload(h, W2, &T.w2t) && upload(h, B2, &T.b2) && upload(h, W3, &T.w3) &&
-            upload(h, B3, &T.b3) && upload(h, W1T, &T.w1t);
-  if (ok && hiav) ok = upload(h, std::vector<double>(hiav, hiav + 5 * f_n), &T.hiav);
+  sed_transpose_w2(F, H, Hp, w2, W2.data());
+  DeviceBag& bag = h->bag;
+  T.w1 = bag.upload(W1); T.b1 = bag.upload(B1); T.w2t = bag.upload(W2); T.b2 = bag.upload(B2); T.w3 = bag.upload(W3);
+  T.b3 = bag.upload(B3); T.w1t = bag.upload(W1T);
+  if (hiav) T.hiav = bag.upload(std::vector<double>(hiav, hiav + 5 * f_n));
   const int lds = (int)max_lds_bytes();
-  ok = ok && hipFuncSetAttribute(reinterpret_cast<const void*>(payne_sedfit_jac_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, lds) == hipSuccess &&
-       hipFuncSetAttribute(reinterpret_cast<const void*>(payne_sedfit_run_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, lds) == hipSuccess;
+  const bool ok = bag.ok && hipFuncSetAttribute(reinterpret_cast<const void*>(payne_sedfit_jac_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, lds) == hipSuccess &&
+                  hipFuncSetAttribute(reinterpret_cast<const void*>(payne_sedfit_run_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, lds) == hipSuccess;
   if (!ok) {
     payne_sedfit_destroy(h);
     return fail(PAYNE_E_HIP, "payne_sedfit_create: uploading the nets failed");
@@ -534,14 +465,4 @@ extern "C" int payne_sedfit_run(payne_sedfit* h, int photscale, unsigned free_ma
   return hipGetLastError() == hipSuccess ? PAYNE_OK : PAYNE_E_HIP;
 }
 
-extern "C" void payne_sedfit_destroy(payne_sedfit* h) {
-  if (!h) return;
-  {
-    OnDevice on(h->device);
-    if (on.ok()) {
-      (void)hipDeviceSynchronize();
-      for (void* p : h->owned) (void)hipFree(p);
-    }
-  }
-  delete h;
-}
+extern "C" void payne_sedfit_destroy(payne_sedfit* h) { payne::host::destroy(h, true); }

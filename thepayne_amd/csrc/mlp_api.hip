@@ -38,54 +38,11 @@ int payne_fisher_launch(const float* rows, int ld, int K, int n, int B, const do
 
 namespace {
 
+using payne::host::DeviceBag;
 using payne::host::OnDevice;
+using payne::host::destroy;
 using payne::host::fail;
 int fail(const md::Status& s) { return fail(s.code, s.msg); }
-
-// The device allocations of a handle, made on the selected device; after the first failure `ok` is false and nothing more is tried.
-struct DeviceBag {
-  std::vector<void*> owned;
-  bool ok = true;
-
-  void* alloc(size_t bytes) {
-    void* p = nullptr;
-    if (!ok || hipMalloc(&p, bytes) != hipSuccess) {
-      ok = false;
-      return nullptr;
-    }
-    owned.push_back(p);
-    return p;
-  }
-  void* zeros(size_t bytes) {
-    void* p = alloc(bytes);
-    if (p && hipMemset(p, 0, bytes) != hipSuccess) ok = false;
-    return p;
-  }
-  void* upload(const void* src, size_t bytes) {
-    void* p = alloc(bytes);
-    put(p, src, bytes);
-    return p;
-  }
-  void put(void* dst, const void* src, size_t bytes) {
-    if (ok && hipMemcpy(dst, src, bytes, hipMemcpyHostToDevice) != hipSuccess) ok = false;
-  }
-  float* floats(size_t n) { return static_cast<float*>(zeros(n * sizeof(float))); }
-  void put_floats(float* dst, const float* src, size_t n) { put(dst, src, n * sizeof(float)); }
-};
-
-// Frees a handle's allocations on its device, behind the device's pending work where `synchronise` says so, and the handle.
-template <class Handle>
-void destroy(Handle* h, bool synchronise) {
-  if (!h) return;
-  {
-    OnDevice on(h->device);
-    if (on.ok()) {
-      if (synchronise) (void)hipDeviceSynchronize();
-      for (void* p : h->bag.owned) (void)hipFree(p);
-    }
-  }
-  delete h;
-}
 
 // N rows in chunks of the workspace's `rows`: pass(r0, n) for each chunk until one fails.
 template <class Pass>

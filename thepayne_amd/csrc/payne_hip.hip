@@ -593,9 +593,7 @@ static int create_phot(payne_ctx* c, const payne_phot_desc* phot, const payne_op
     std::vector<float> w2((size_t)F * H * H), w2t((size_t)F * H * H);
     he = hipMemcpy(w2.data(), phot->w2, w2.size() * 4, hipMemcpyDeviceToHost);
     if (he != hipSuccess) return fail(c, PAYNE_E_HIP, std::string("hipMemcpy(w2): ") + hipGetErrorString(he));
-    for (int f = 0; f < F; ++f)
-      for (int h = 0; h < H; ++h)
-        for (int k = 0; k < H; ++k) w2t[((size_t)f * H + k) * H + h] = w2[((size_t)f * H + h) * H + k];
+    sed_transpose_w2(F, H, H, w2.data(), w2t.data());
     if ((rc = upload(c, w2t, &P.w2t, c->owned))) return rc;
   }
   if (phot->hiav) {

@@ -11,7 +11,8 @@
 //                 BC = w3 a2 + b3,             dBC/dx_d = w3 a2'_d
 //               The quotient W1[:, d] / (xmax_d - xmin_d) is a table (tangent_weight): the handle forms it once.  net_forward is
 //               the scalar form; the kernels run the two matrix products of a block of stars on the fp64 matrix instruction.
-//   chain       row_terms, mag_grad: the magnitude formulae of sed_core.hpp (sed_row mode 1, sed_mag_terms) and d m / d parameter.  At Av >= 5
+//   chain       row_terms, mag_grad: the magnitude formulae of sed_core.hpp (its label encoding, magnitude terms and high-Av offset are
+//               called here, not restated) and d m / d parameter.  At Av >= 5
 //               the nets are evaluated at Av = 0 and dBC/dAv is the table's -c1 (c2 + c3 Rv + c4 Rv^2).  Where the magnitude is NaN
 //               (a NaN label, a filter without a row in the table at Av >= 5) every derivative is NaN.
 //   fit         R = [d m / d theta_free ; obs - m], G = R diag(w) R^T over the filters in ascending order (tile_add, one fma an
@@ -23,6 +24,7 @@
 
 #include "../../include/payne_hip.h"
 #include "lmfit_core.hpp"
+#include "sed_core.hpp"
 
 namespace payne {
 namespace sedfit {
@@ -34,16 +36,13 @@ using lm::kTile;
 constexpr int kMaxK = PAYNE_SEDFIT_MAX_K;        // parameters of a dist row; a scaled row has six
 constexpr int kNetIn = 6;                        // inputs of a net: Teff, logg, FeH, aFe, Av, Rv
 constexpr int kMaxTan = 5;                       // ... of which Rv never carries a tangent
-constexpr int kMaxH = 64;                        // the tile's width (sed_core.hpp: kSedMaxH)
-constexpr int kTileRows = 48;                    // (star, tangent) rows of a tile (sed_core.hpp: kSedCandsMax)
+constexpr int kMaxH = kSedMaxH;                  // the widest net (the tile's width; a name the host programs use)
 constexpr double kLn10 = 2.302585092994046;
-constexpr double kRv = 3.1;
 
 PAYNE_HD int n_pars(int photscale) { return photscale ? 6 : 7; }
 // the net input that parameter p of a row is, or -1
 PAYNE_HD int net_input(int photscale, int p) { return p < 4 ? p : (p == n_pars(photscale) - 1 ? 4 : -1); }
-PAYNE_HD int padded_width(int H) { return (H + 15) & ~15; }
-PAYNE_HD int stars_per_tile(int Kn) { return kTileRows / (1 + Kn); }
+PAYNE_HD int stars_per_tile(int Kn) { return kSedCandsMax / (1 + Kn); }   // (star, tangent) rows of a tile
 
 // Which parameters are fitted: free parameter k is parameter par[k] of the row (ascending); Kn of them are net inputs, tangent
 // t = 0 .. Kn - 1 is net input tan_in[t], and tan_of[p] is the tangent of parameter p (-1: none).
@@ -86,7 +85,7 @@ struct Net {
   float b3;
 };
 
-// A row's encoded labels (photANN.py:118-120 as sed_row_labels has them) and what the high-Av branch needs.
+// A row's encoded labels (sed_core.hpp: sed_encode) and what the high-Av branch needs.
 struct Row {
   double xs[kNetIn];
   double av;
@@ -94,9 +93,8 @@ struct Row {
 };
 PAYNE_HD void encode(const double* pars, int photscale, const double* xmin, const double* xden, Row* r) {
   r->av = pars[n_pars(photscale) - 1];
-  r->hi = !(r->av < 5.0);                                           // predictsed.py:86-90
-  const double x[kNetIn] = {pars[0], pars[1], pars[2], pars[3], r->hi ? 0.0 : r->av, kRv};
-  for (int d = 0; d < kNetIn; ++d) r->xs[d] = (x[d] - xmin[d]) / xden[d];
+  r->hi = sed_hi_av(r->av);
+  sed_encode(pars, r->av, kSedRv, r->hi, xmin, xden, r->xs);
 }
 
 // W1[h][d] / (xmax_d - xmin_d): what a unit tangent of input d is behind the first layer's product.
@@ -140,7 +138,7 @@ inline void net_forward(const Net& n, const double* xs, const double* xden, int 
 }
 
 // ---- the chain rule -------------------------------------------------------------------------------------------------------------
-// What the magnitudes of a row share over the filters (sed_mag_terms' a1, a2 for a theta row, and the two derivatives that cost a
+// What the magnitudes of a row share over the filters (sed_core.hpp's a1, a2 for a theta row, and the two derivatives that cost a
 // division): two logarithms and two quotients a row, not a filter.  m = (a1 - BC) + a2.
 struct RowTerms {
   double a1, a2, dteff, ddist;
@@ -148,13 +146,10 @@ struct RowTerms {
 PAYNE_HD void row_terms(int photscale, const double* pars, RowTerms* t) {
   const double logt = log10(pars[0]);                               // genmod.py:124,172
   if (photscale) {
-    t->a1 = 5.0 * pars[4] - 10.0 * (logt - log10(5770.0)) - 0.26;   // genphot_scaled, predictsed.py:99-101
-    t->a2 = 0.0;
+    sed_terms_scaled(pars[4], logt, t->a1, t->a2);                  // genphot_scaled, predictsed.py:99-101
     t->ddist = 0.0;
   } else {
-    const double logl = 2.0 * pars[4] + 4.0 * (logt - log10(5770.0));   // genmod.py:126
-    t->a1 = -2.5 * logl + 4.74;
-    t->a2 = 5.0 * log10(pars[5]) - 5.0;
+    sed_terms_dist(sed_theta_logl(pars[4], logt), pars[5], t->a1, t->a2);
     t->ddist = 5.0 / (pars[5] * kLn10);
   }
   t->dteff = 10.0 / (pars[0] * kLn10);
@@ -168,10 +163,8 @@ PAYNE_HD void mag_grad(int photscale, const RowTerms& t, double av, double bc, c
   const int P = n_pars(photscale);
   double dav = dbc[4];
   if (hi) {                                                         // highred.py:19-25
-    const double q = c ? (c[2] + c[3] * kRv + c[4] * (kRv * kRv)) : nan;
-    const double offv = c ? (c[0] + c[1] * av * q) : nan;
-    bc = bc - offv;
-    dav = c ? -(c[1] * q) : nan;
+    bc = bc - sed_hiav_offset(c, av, kSedRv);
+    dav = c ? -(c[1] * sed_hiav_slope(c, kSedRv)) : nan;
   }
   const double mag = (t.a1 - bc) + t.a2;
   *m = mag;
