@@ -537,6 +537,24 @@ int payne_fisher_batch(int device, const float* rows_dev, int ld, int K, int n, 
  * operand map, the handling of w == 0, NaN and pixels beyond n, both load forms (x_dev 16-byte aligned too for the first) and the
  * step that follows are payne_lmfit_update's, over all K parameters; a star's bits do not depend on its batch.  |x| <= 1 is assumed.
  *   PAYNE_E_INVALID      as payne_lmfit_update, and P < 1, P > K, null x_dev with B > 0
+ * payne_lmfit_update_phot: the update for a spectrum and magnitudes fitted together, Gaussian priors included.  The handle's K
+ * parameters are, in this order, Km of the spectral model (rows_dev [B][1 + Km][ld] as above), Kp that only the photometry sees (no
+ * row: rows Km .. Km + Kp - 1 of the spectral tile are none of R's and stay zero) and P >= 0 Chebyshev coefficients (P == 0: the
+ * plain model, x_dev is not read and may be NULL).  The spectral tile is otherwise payne_lmfit_update_poly's (payne_lmfit_update's
+ * for P == 0).  The photometric block is what payne_sedfit_jac wrote at the trial point: mags_dev DEVICE fp64 [B][F], dmags_dev
+ * DEVICE fp64 [B][F][ncol], ncol 7 or 6; obs_dev, pw_dev DEVICE fp64 [B][F], the observed magnitudes and 1 / sigma^2 (pw == 0: the
+ * filter does not count whatever the four arrays hold there, NaN included); sed_col HOST int [K], the column of dmags that parameter
+ * k is or -1 for none (Vrad, Vmic, the coefficients).  With R_k = dmags[f][sed_col[k]] (0 for -1) and R_K = obs_f - mag_f, element
+ * (i, j), i <= j <= K, of the block is g = 0, then g = fma(R_i pw_f, R_j, g) over the counting filters in ascending order;
+ * prior_mu_dev, prior_sigma_dev DEVICE fp64 [B][K] or both NULL add to it as in payne_sedfit_run, at the star's x_trial (a sigma that
+ * is not finite and positive: none); then tile[i][j] = tile[i][j] + g, one addition, and the step is payne_lmfit_update's
+ * (csrc/lmfit_phot_core.hpp).  No atomics, every sum has a fixed order; a star's bits depend on nothing but its own inputs.
+ *   PAYNE_E_INVALID      as payne_lmfit_update; P < 0, Kp < 0, Km < 0, Km + Kp + P != K; null x_dev with P > 0 and B > 0; F < 0, a
+ *                        null photometric array with F > 0 and B > 0; ncol other than 6 / 7; null sed_col, an entry outside
+ *                        [-1, ncol), -1 for one of the Kp parameters, another than -1 for a coefficient; only one of prior_mu_dev /
+ *                        prior_sigma_dev; the box (payne_lmfit_begin's) of the parameter mapped to column ncol - 1, Av, with hi >= 5
+ *                        (the model jumps there)
+ *   PAYNE_E_UNSUPPORTED  F > 64 (a star's filters are staged in LDS)
  * payne_lmfit_result: DEVICE pointers, any may be NULL: x_best fp64 [B][K], chisq fp64 [B] (of x_best), A fp64 [B][K][K] and g fp64
  * [B][K] (at x_best), lambda fp64 [B], status int [B], niter int [B] (evaluations), at_bound unsigned [B].  Copies on `stream`.
  *   PAYNE_E_INVALID      null handle
@@ -563,6 +581,10 @@ int payne_lmfit_update(payne_lmfit* h, const float* rows_dev, int ld, const floa
                        void* stream);
 int payne_lmfit_update_poly(payne_lmfit* h, int P, const float* rows_dev, int ld, const float* flux_dev, const double* w_dev, int ld_f,
                             const double* x_dev, int n, void* stream);
+int payne_lmfit_update_phot(payne_lmfit* h, int Km, int Kp, int P, const float* rows_dev, int ld, const float* flux_dev,
+                            const double* w_dev, int ld_f, const double* x_dev, int n, int F, int ncol, const int* sed_col,
+                            const double* mags_dev, const double* dmags_dev, const double* obs_dev, const double* pw_dev,
+                            const double* prior_mu_dev, const double* prior_sigma_dev, void* stream);
 int payne_lmfit_result(payne_lmfit* h, double* x_best, double* chisq, double* A, double* g, double* lambda, int* status, int* niter,
                        unsigned* at_bound, void* stream);
 void payne_lmfit_destroy(payne_lmfit* h);

@@ -41,7 +41,7 @@ SYMBOLS = ["payne_version", "payne_ctx_create", "payne_ctx_set_obs", "payne_ctx_
            "payne_specmlp_train_create", "payne_specmlp_train_step", "payne_specmlp_train_loss", "payne_specmlp_train_predict",
            "payne_specmlp_train_set_lr", "payne_specmlp_train_get", "payne_specmlp_train_steps", "payne_specmlp_train_destroy",
            "payne_specjac_create", "payne_specjac_eval", "payne_specjac_destroy", "payne_fisher_batch",
-           "payne_lmfit_create", "payne_lmfit_begin", "payne_lmfit_trial", "payne_lmfit_update", "payne_lmfit_update_poly", "payne_lmfit_result",
+           "payne_lmfit_create", "payne_lmfit_begin", "payne_lmfit_trial", "payne_lmfit_update", "payne_lmfit_update_poly", "payne_lmfit_update_phot", "payne_lmfit_result",
            "payne_lmfit_destroy",
            "payne_tmatch_create", "payne_tmatch_match", "payne_tmatch_chunk", "payne_tmatch_destroy",
            "payne_contfit_batch",
@@ -129,6 +129,7 @@ LMFIT_RUNNING, LMFIT_CONVERGED, LMFIT_STALLED, LMFIT_MAXITER, LMFIT_SINGULAR, LM
 LMFIT_STATUS_NAMES = ("RUNNING", "CONVERGED", "STALLED", "MAXITER", "SINGULAR", "NAN")
 SEDFIT_TOO_FEW, SEDFIT_MAX_K, SEDFIT_MAX_H = 6, 7, 64       # payne_sedfit_run's own status beside LMFIT_*
 LMFIT_MAX_K = 15
+LMFIT_PHOT_MAX_F = 64                                      # payne_lmfit_update_phot stages a star's filters in LDS
 TMATCH_MAX_TOPK = 8
 CONTFIT_OK, CONTFIT_NONPOSITIVE, CONTFIT_TOO_FEW, CONTFIT_SINGULAR, CONTFIT_NAN, CONTFIT_BAD_MODEL = range(6)
 CONTFIT_STATUS_NAMES = ("OK", "NONPOSITIVE", "TOO_FEW", "SINGULAR", "NAN", "BAD_MODEL")
@@ -284,6 +285,9 @@ def load(path=None):
     lib.payne_lmfit_update.restype = C.c_int
     lib.payne_lmfit_update_poly.argtypes = [ctxp, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p]
     lib.payne_lmfit_update_poly.restype = C.c_int
+    lib.payne_lmfit_update_phot.argtypes = [ctxp, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int,
+                                            C.c_int, C.c_int, C.c_void_p] + [C.c_void_p] * 7
+    lib.payne_lmfit_update_phot.restype = C.c_int
     lib.payne_lmfit_result.argtypes = [ctxp] + [C.c_void_p] * 9
     lib.payne_lmfit_result.restype = C.c_int
     lib.payne_lmfit_destroy.argtypes = [ctxp]

@@ -1,5 +1,5 @@
 // k_lmfit.hip -- payne_lmfit_*: batched Levenberg-Marquardt (include/payne_hip.h).  The arithmetic is lmfit_core.hpp, which runs on
-// the host too (tests/emul/lmfit_emul.cpp, lmfit_poly_emul.cpp); the tile, its loop and the 16-byte loads are normal_tile.hpp.
+// the host too (tests/emul/lmfit_emul.cpp, lmfit_poly_emul.cpp, lmfit_phot_emul.cpp); the tile, its loop and the 16-byte loads are normal_tile.hpp.
 //
 //   payne_lmfit_update_kernel  one 256-thread workgroup a star, skipped when the star is no longer RUNNING.  Lane (i = lane & 15,
 //     q = lane >> 4) of every wave reads four consecutive fp32 pixels of row i of R and the four fp64 weights and hands them to
@@ -13,6 +13,12 @@
 //         parameters.  R = [p dm/dtheta ; m T_j(x) ; flux - m p] is formed in registers from the caller's 1 + Km rows, the star's
 //         coefficients (x_trial, copied to LDS) and x, and never stored.  Every lane evaluates one series at its four pixels in one
 //         loop of P - 2 steps (cheb_series.hpp: series4): p, or T_j as the series of a unit vector.
+//   payne_lmfit_update_phot_kernel  payne_lmfit_update_phot: the same body (update_body<VEC, POLY, PHOT = true>) for a spectrum and
+//     magnitudes fitted together.  K = Km + Kp + P: the lanes of rows Km .. Km + Kp - 1, the parameters only the photometry sees, are
+//     not live.  Every thread asks for up to two of the star's F ncol <= 448 derivatives (and thread f for filter f's weight and
+//     residual) before the pixel loop and keeps them in registers; behind sum_waves they go to LDS (the space of `part`), thread
+//     (i, j) sums element (i, j) of the photometric block over the filters in ascending order (lmfit_phot_core.hpp: phot_element),
+//     and thread 0 adds the priors and the block to the tile (add_block) before it takes the step.
 //   payne_lmfit_begin_kernel   one thread a star: x_trial = clip(x0), the state reset.
 //   No atomics; every sum has a fixed order.
 #include <hip/hip_runtime.h>
@@ -22,6 +28,7 @@
 #include "../../include/payne_hip.h"
 #include "host_prologue.hpp"
 #include "lmfit_core.hpp"
+#include "lmfit_phot_core.hpp"
 
 namespace lm = payne::lmfit;
 namespace nt = payne::ntile;
@@ -47,12 +54,19 @@ __global__ void __launch_bounds__(nt::kThreads) payne_lmfit_begin_kernel(const d
   if (b < B) lm::begin_star(st, (size_t)b, K, x0 + (size_t)b * (size_t)K, box, lambda0);
 }
 
-// rows holds 1 + K rows a star, or with POLY 1 + Km, Km = K - P; x and P are read with POLY only.
-template <bool VEC, bool POLY>
-__global__ void __launch_bounds__(nt::kThreads) payne_lmfit_update_kernel(const float* __restrict__ rows, long long ld,
-                                                                          const float* __restrict__ flux, const double* __restrict__ w,
-                                                                          long long ld_f, const double* __restrict__ x, int n, int K, int P,
-                                                                          const lm::State st, const lm::Box box, const payne_lmfit_opts opts) {
+// The photometric arrays of payne_lmfit_update_phot, by value: one star's are [F], dmags [F][ncol], the priors [K] (or both NULL).
+struct PhotArgs {
+  const double *mags, *dmags, *obs, *pw, *mu, *sigma;
+  int F;
+  lm::PhotMap map;
+};
+
+// One star's update, the body of both kernels below.  rows holds 1 + K rows a star, or with POLY 1 + Km, Km = K - P; x and P are read
+// with POLY only, ph with PHOT only (then Km = K - P - ph.map.Kp).
+template <bool VEC, bool POLY, bool PHOT>
+__device__ __forceinline__ void update_body(const float* __restrict__ rows, long long ld, const float* __restrict__ flux,
+                                            const double* __restrict__ w, long long ld_f, const double* __restrict__ x, int n, int K, int P,
+                                            const lm::State& st, const lm::Box& box, const payne_lmfit_opts& opts, const PhotArgs& ph) {
   __shared__ double part[nt::kWaves][nt::kTileSize];
   __shared__ double tile[nt::kTileSize];
   __shared__ double work[lm::kWorkDoubles];
@@ -60,14 +74,26 @@ __global__ void __launch_bounds__(nt::kThreads) payne_lmfit_update_kernel(const 
   const size_t b = blockIdx.x;
   if (st.status[b] != PAYNE_LMFIT_RUNNING) return;                  // (the whole workgroup)
   const int tid = threadIdx.x, i = tid & 15;
-  const int Km = POLY ? K - P : K;
+  const int Kp = PHOT ? ph.map.Kp : 0;
+  const int Km = (POLY ? K - P : K) - Kp;
   if constexpr (POLY) {
-    if (tid < P) coef[tid] = st.x_trial[b * (size_t)K + (size_t)(Km + tid)];
+    if (tid < P) coef[tid] = st.x_trial[b * (size_t)K + (size_t)(Km + Kp + tid)];
     __syncthreads();
   }
-  const bool live = i <= K, residual = i == K;
-  const int j = lm::series_index(i, Km, K);
-  const float* ra = rows + (b * (size_t)(1 + Km) + (size_t)(i < Km ? 1 + i : 0)) * (size_t)ld;   // the lane's row (row 0, the model, where it has none)
+  const bool live = PHOT ? lm::has_row(i, Km, Kp, K) : i <= K, residual = i == K;
+  const int j = lm::series_index(i, Km + Kp, K);
+  const float* ra = rows + (b * (size_t)(1 + Km) + (size_t)lm::row_of(i, Km)) * (size_t)ld;   // the lane's row (row 0, the model, where it has none)
+  // PHOT: the star's filters are asked for here and wait in registers behind the pixels: F ncol <= 448 derivatives, two a thread
+  double pd0 = 0.0, pd1 = 0.0, pres = 0.0, pwt = 0.0;
+  if constexpr (PHOT) {
+    const int nd = ph.F * ph.map.ncol;
+    if (tid < nd) pd0 = ph.dmags[b * (size_t)nd + (size_t)tid];
+    if (tid + nt::kThreads < nd) pd1 = ph.dmags[b * (size_t)nd + (size_t)(tid + nt::kThreads)];
+    if (tid < ph.F) {
+      pwt = ph.pw[b * (size_t)ph.F + (size_t)tid];
+      pres = lm::phot_residual(ph.obs[b * (size_t)ph.F + (size_t)tid], ph.mags[b * (size_t)ph.F + (size_t)tid]);
+    }
+  }
   const float* fb = flux + b * (size_t)ld_f;
   const double* wb = w + b * (size_t)ld_f;
   const nt::d4 acc = nt::wave_sums(n, [&](int p) PAYNE_TILE_CALLABLE {
@@ -88,7 +114,42 @@ __global__ void __launch_bounds__(nt::kThreads) payne_lmfit_update_kernel(const 
     };
   });
   nt::sum_waves(acc, part, tile, []() PAYNE_TILE_CALLABLE { __syncthreads(); });
+  if constexpr (PHOT) {                                             // (part is free behind sum_waves' barrier: the block and the filters)
+    double* pt = &part[0][0];
+    double* dm = pt + nt::kTileSize;
+    double* res = dm + lm::kPhotMaxF * lm::kPhotMaxCol;
+    double* pw = res + lm::kPhotMaxF;
+    static_assert(nt::kTileSize + lm::kPhotMaxF * (lm::kPhotMaxCol + 2) <= nt::kWaves * nt::kTileSize, "the filters fit into part");
+    static_assert(lm::kPhotMaxF * lm::kPhotMaxCol <= 2 * nt::kThreads && lm::kPhotMaxF <= nt::kThreads, "two derivatives a thread");
+    const int nd = ph.F * ph.map.ncol;
+    if (tid < nd) dm[tid] = pd0;
+    if (tid + nt::kThreads < nd) dm[tid + nt::kThreads] = pd1;
+    if (tid < ph.F) { res[tid] = pres; pw[tid] = pwt; }
+    __syncthreads();
+    const int ei = tid >> 4, ej = tid & 15;
+    pt[tid] = ei <= ej && ej <= K ? lm::phot_element(ph.map, ei, ej, K, ph.F, dm, res, pw) : 0.0;
+    __syncthreads();
+    if (tid == 0)
+      lm::add_block(tile, pt, K, st.x_trial + b * (size_t)K, ph.mu ? ph.mu + b * (size_t)K : nullptr, ph.sigma ? ph.sigma + b * (size_t)K : nullptr);
+  }
   if (tid == 0) lm::update_star(st, b, K, tile, opts, box, work);
+}
+
+// payne_lmfit_update / _poly, and payne_lmfit_update_phot with the photometric arrays behind the same arguments.
+template <bool VEC, bool POLY>
+__global__ void __launch_bounds__(nt::kThreads) payne_lmfit_update_kernel(const float* __restrict__ rows, long long ld,
+                                                                          const float* __restrict__ flux, const double* __restrict__ w,
+                                                                          long long ld_f, const double* __restrict__ x, int n, int K, int P,
+                                                                          const lm::State st, const lm::Box box, const payne_lmfit_opts opts) {
+  update_body<VEC, POLY, false>(rows, ld, flux, w, ld_f, x, n, K, P, st, box, opts, PhotArgs{});
+}
+template <bool VEC, bool POLY>
+__global__ void __launch_bounds__(nt::kThreads) payne_lmfit_update_phot_kernel(const float* __restrict__ rows, long long ld,
+                                                                               const float* __restrict__ flux, const double* __restrict__ w,
+                                                                               long long ld_f, const double* __restrict__ x, int n, int K, int P,
+                                                                               const lm::State st, const lm::Box box,
+                                                                               const payne_lmfit_opts opts, const PhotArgs ph) {
+  update_body<VEC, POLY, true>(rows, ld, flux, w, ld_f, x, n, K, P, st, box, opts, ph);
 }
 
 template <class T>
@@ -100,16 +161,23 @@ bool alloc(payne_lmfit* h, T** p, size_t count) {
   return true;
 }
 
-// One update of the handle's B stars; P == 0 and x == NULL (which aligned16 passes): the plain form.
+// One update of the handle's B stars; P == 0 and x == NULL (which aligned16 passes): the plain form.  ph: the photometric block, or NULL.
 int launch_update(payne_lmfit* h, int P, const float* rows, int ld, const float* flux, const double* w, int ld_f, const double* x, int n,
-                  void* stream) {
+                  void* stream, const PhotArgs* ph = nullptr) {
   OnDevice on(h->device);
   if (!on.ok()) return PAYNE_E_HIP;
   const bool vec = ld % 4 == 0 && ld_f % 4 == 0 && aligned16(rows) && aligned16(flux) && aligned16(w) && aligned16(x);
-  const auto kernel = P ? (vec ? payne_lmfit_update_kernel<true, true> : payne_lmfit_update_kernel<false, true>)
-                        : (vec ? payne_lmfit_update_kernel<true, false> : payne_lmfit_update_kernel<false, false>);
-  hipLaunchKernelGGL(kernel, dim3((unsigned)h->B), dim3(nt::kThreads), 0, reinterpret_cast<hipStream_t>(stream), rows, (long long)ld, flux, w,
-                     (long long)ld_f, x, n, h->K, P, h->st, h->box, h->opts);
+  const dim3 grid((unsigned)h->B), block(nt::kThreads);
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  if (ph) {
+    const auto kernel = P ? (vec ? payne_lmfit_update_phot_kernel<true, true> : payne_lmfit_update_phot_kernel<false, true>)
+                          : (vec ? payne_lmfit_update_phot_kernel<true, false> : payne_lmfit_update_phot_kernel<false, false>);
+    hipLaunchKernelGGL(kernel, grid, block, 0, s, rows, (long long)ld, flux, w, (long long)ld_f, x, n, h->K, P, h->st, h->box, h->opts, *ph);
+  } else {
+    const auto kernel = P ? (vec ? payne_lmfit_update_kernel<true, true> : payne_lmfit_update_kernel<false, true>)
+                          : (vec ? payne_lmfit_update_kernel<true, false> : payne_lmfit_update_kernel<false, false>);
+    hipLaunchKernelGGL(kernel, grid, block, 0, s, rows, (long long)ld, flux, w, (long long)ld_f, x, n, h->K, P, h->st, h->box, h->opts);
+  }
   return hipGetLastError() == hipSuccess ? PAYNE_OK : PAYNE_E_HIP;
 }
 
@@ -180,6 +248,24 @@ extern "C" int payne_lmfit_update_poly(payne_lmfit* h, int P, const float* rows_
   if (h->B == 0) return PAYNE_OK;
   if (!rows_dev || !flux_dev || !w_dev || !x_dev) return PAYNE_E_INVALID;
   return launch_update(h, P, rows_dev, ld, flux_dev, w_dev, ld_f, x_dev, n, stream);
+}
+
+extern "C" int payne_lmfit_update_phot(payne_lmfit* h, int Km, int Kp, int P, const float* rows_dev, int ld, const float* flux_dev,
+                                       const double* w_dev, int ld_f, const double* x_dev, int n, int F, int ncol, const int* sed_col,
+                                       const double* mags_dev, const double* dmags_dev, const double* obs_dev, const double* pw_dev,
+                                       const double* prior_mu_dev, const double* prior_sigma_dev, void* stream) {
+  if (!h || n < 1 || ld < n || ld_f < n) return PAYNE_E_INVALID;
+  const int rc = lm::check_phot(h->K, Km, Kp, P, F, ncol, sed_col, h->box, prior_mu_dev != nullptr, prior_sigma_dev != nullptr);
+  if (rc == PAYNE_E_UNSUPPORTED) return fail(rc, "payne_lmfit_update_phot: F > 64 (a star's filters are staged in LDS)");
+  if (rc != PAYNE_OK) return rc;
+  if (h->B == 0) return PAYNE_OK;
+  if (!rows_dev || !flux_dev || !w_dev || (P > 0 && !x_dev)) return PAYNE_E_INVALID;
+  if (F > 0 && (!mags_dev || !dmags_dev || !obs_dev || !pw_dev)) return PAYNE_E_INVALID;
+  PhotArgs ph{mags_dev, dmags_dev, obs_dev, pw_dev, prior_mu_dev, prior_sigma_dev, F, lm::PhotMap{}};
+  ph.map.ncol = ncol;
+  ph.map.Kp = Kp;
+  for (int k = 0; k < lm::kMaxK; ++k) ph.map.sed_col[k] = k < h->K ? sed_col[k] : -1;
+  return launch_update(h, P, rows_dev, ld, flux_dev, w_dev, ld_f, P > 0 ? x_dev : nullptr, n, stream, &ph);
 }
 
 extern "C" int payne_lmfit_result(payne_lmfit* h, double* x_best, double* chisq, double* A, double* g, double* lambda, int* status,

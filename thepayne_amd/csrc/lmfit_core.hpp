@@ -70,6 +70,28 @@ inline void tile_sums_poly_host(const float* rows, long long ld, const float* fl
   }, G);
 }
 
+// With Kp parameters that the spectrum does not see (payne_lmfit_update_phot; lmfit_phot_core.hpp adds their block), K = Km + Kp + P:
+// they sit between the model's and the coefficients', rows Km .. Km + Kp - 1 of the tile are none of R's (a lane there is not live:
+// both operands zero by the select), the series of row i >= Km + Kp is series_index(i, Km + Kp, K), and the lane's row of the caller's
+// 1 + Km is row_of(i, Km) as before.
+PAYNE_HD bool has_row(int i, int Km, int Kp, int K) { return i <= K && !(i >= Km && i < Km + Kp); }
+PAYNE_HD int row_of(int i, int Km) { return i < Km ? 1 + i : 0; }
+
+// The tile with that gap on the host.  rows [1 + Km][ld]; P == 0: the plain model (operand), c and x are not read.
+inline void tile_sums_gap_host(const float* rows, long long ld, const float* flux, const double* w, const double* x, int n, int Km, int Kp,
+                               int P, const double* c, double* G) {
+  const int K = Km + Kp + P;
+  nt::tile_sums_host(w, n, K + 1, [&](int p, double* r) {
+    for (int i = 0; i <= K; ++i) {
+      const float a = rows[(size_t)row_of(i, Km) * (size_t)ld + (size_t)p];
+      if (!has_row(i, Km, Kp, K)) r[i] = 0.0;
+      else if (P > 0) r[i] = operand_poly(i, K, a, flux[p], chebs::series_value(c, series_index(i, Km + Kp, K), P, x[p]));
+      else r[i] = operand(i, K, a, flux[p]);
+    }
+    return true;
+  }, G);
+}
+
 // ---- one star's state -------------------------------------------------------------------------------------------------------
 // The handle's arrays, one entry (or block) a star.
 struct State {

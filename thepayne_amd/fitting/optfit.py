@@ -20,7 +20,17 @@ are not supported (``PayneSpecPredict.getgrad`` explains why).
 
 ``OptFit.fit_joint`` fits a continuum polynomial (``polycalc``'s Chebyshev coefficients) along with these parameters, in the same
 loop: its update, payne_lmfit_update_poly, forms the rows of model x polynomial in registers.
+
+``OptFit.fit_specphot`` fits spectrum and photometry together: one chi^2 over the labels both share, Vmic / Vrad / the polynomial,
+which only the spectrum sees, and log R, distance, Av (or log A, Av), which only the magnitudes see, Gaussian priors on any of them
+included.  An iteration has a fourth enqueued step, ``SEDFit.grad_device`` at the trial point, and its update,
+payne_lmfit_update_phot, adds the magnitudes' normal equations and the priors to the spectral tile before the step is taken.  The
+errors that come back are marginal over all fitted parameters.  The spectral model is fp32: where the magnitudes pull the shared labels
+off the spectrum's own minimum, its rounding reaches chi^2 at a few 1e-6, which is more than a step of xtol = 1e-3 sigma gains, and a
+star may end ``STALLED`` (or ``CONVERGED`` after a dozen rejected trials) AT the solution; ``fit_specphot``'s docstring says what to
+make of that.
 """
+import collections
 import ctypes as C
 
 import numpy as np
@@ -30,7 +40,7 @@ from ..engine import THETA_SPEC_COLS
 from ..predict._spec import PayneSpecPredict, smooth_rows
 from .forecast import crlb_from_fisher, weights_from_errors
 
-__all__ = ["OptFit", "check_fit_args", "check_joint_args", "LM_DEFAULTS", "VRAD_BOUND", "COEF_BOUND"]
+__all__ = ["OptFit", "check_fit_args", "check_joint_args", "check_specphot_args", "LM_DEFAULTS", "VRAD_BOUND", "COEF_BOUND"]
 
 LM_DEFAULTS = dict(lambda0=1e-3, down=10.0, up=10.0, lambda_min=1e-12, lambda_max=1e8, xtol=1e-3, maxiter=50)
 VRAD_BOUND = 500.0                                   # km/s: the default box of a fitted Vrad
@@ -130,6 +140,99 @@ def check_joint_args(flux, eflux, start, nobs, n_labels, xmin, xmax, npoly=4, co
     return flux, eflux, start, np.concatenate([lo, cb[:, 0]]), np.concatenate([hi, cb[:, 1]]), o, coef, clip
 
 
+def check_specphot_args(flux, eflux, mags, emags, start, phot_start, nobs, n_labels, xmin, xmax, F, sed_xmin, sed_xmax, photscale=False,
+                        free_phot=("logR", "Av"), npoly=0, coef=None, clip=None, fit_vrad=False, bounds=None, coef_bounds=None, prior=None,
+                        vrad_step=0.25, check_every=4, **opts):
+    """What ``OptFit.fit_specphot`` checks before anything reaches the device; no GPU.  ``F``, ``sed_xmin``, ``sed_xmax``,
+    ``photscale``: the ``SEDFit``'s.  The K = K_m + K_p + npoly parameters are the fitted columns of ``start`` (the labels, Vrad), the
+    free photometric-only parameters in the row's order, the coefficients.  Returns a dict: flux, eflux, start, coef, clip, opts as
+    ``check_joint_args`` returns them; obs, pw [N, F]; phot_start [N, ncol - 4]; names [K]; lo, hi [K]; Km, Kp, P; phot_cols (the K_p
+    columns of the photometric row); sed_col [K] (the column of the row that parameter k is, -1: none); mu, sigma [N, K] or None."""
+    from . import sedfit
+    pnames = sedfit.par_names(photscale)
+    ncol = len(pnames)
+    free = [free_phot] if isinstance(free_phot, str) else list(free_phot)
+    if len(set(free)) != len(free) or any(f not in pnames[4:] for f in free):
+        raise ValueError("free_phot must name parameters among %s, each once; got %r" % (pnames[4:], free))
+    if isinstance(npoly, bool) or int(npoly) != npoly or int(npoly) < 0:
+        raise ValueError("npoly must be an integer >= 0, got %r" % (npoly,))
+    cols = fitted_columns(n_labels, fit_vrad)
+    Km, Kp, P = len(cols), len(free), int(npoly)
+    K = Km + Kp + P
+    if K > _lib.LMFIT_MAX_K:
+        raise ValueError("%d fitted columns of the spectrum, %d photometric parameters and npoly = %d are %d parameters; at most %d (one 16 x 16 "
+                         "tile holds a star's normal equations)" % (Km, Kp, P, K, _lib.LMFIT_MAX_K))
+    if int(F) > _lib.LMFIT_PHOT_MAX_F:
+        raise ValueError("%d filters; payne_lmfit_update_phot takes at most %d" % (F, _lib.LMFIT_PHOT_MAX_F))
+    fit_args = dict(fit_vrad=fit_vrad, vrad_step=vrad_step, check_every=check_every, **opts)
+    if P:
+        flux, eflux, start, lo_s, hi_s, o, coef, clip = check_joint_args(flux, eflux, start, nobs, n_labels, xmin, xmax, npoly=P, coef=coef, clip=clip,
+                                                                         coef_bounds=coef_bounds, **fit_args)
+    else:
+        if coef is not None or clip or coef_bounds is not None:
+            raise ValueError("coef, clip and coef_bounds belong to the polynomial; npoly is 0")
+        flux, eflux, start, lo_s, hi_s, o = check_fit_args(flux, eflux, start, nobs, n_labels, xmin, xmax, **fit_args)
+        coef, clip = None, {}
+    N = flux.shape[0]
+    mags, emags = np.atleast_2d(np.asarray(mags, dtype=np.float64)), np.atleast_2d(np.asarray(emags, dtype=np.float64))
+    if mags.shape != (N, int(F)) or emags.shape != mags.shape:
+        raise ValueError("mags and emags must be [%d, %d], got %s and %s" % (N, F, mags.shape, emags.shape))
+    phot_start = np.atleast_2d(np.asarray(phot_start, dtype=np.float64))
+    if phot_start.shape != (N, ncol - 4) or not np.all(np.isfinite(phot_start)):
+        raise ValueError("phot_start must be [%d, %d] (%s) and finite, got %s" % (N, ncol - 4, ", ".join(pnames[4:]), phot_start.shape))
+    ok = np.isfinite(mags) & np.isfinite(emags) & (emags > 0.0)
+    obs, pw = np.where(ok, mags, 0.0), np.where(ok, 1.0 / np.where(ok, emags, 1.0) ** 2, 0.0)
+    # the box: a shared label's is the intersection of the two networks', a photometric parameter's is SEDFit's
+    plo, phi = sedfit.default_box(np.asarray(sed_xmin, dtype=np.float64), np.asarray(sed_xmax, dtype=np.float64), photscale)
+    phot_cols = sorted(pnames.index(f) for f in free)
+    names = [THETA_SPEC_COLS[c] for c in cols] + [pnames[c] for c in phot_cols] + ["pc_%d" % j for j in range(P)]
+    lo, hi = np.concatenate([lo_s[:Km], plo[phot_cols], lo_s[Km:]]), np.concatenate([hi_s[:Km], phi[phot_cols], hi_s[Km:]])
+    lo[:4], hi[:4] = np.maximum(lo[:4], plo[:4]), np.minimum(hi[:4], phi[:4])
+    if not np.all(lo[:4] < hi[:4]):
+        raise ValueError("the spectral and the photometric networks' ranges of %s do not overlap" % names[int(np.flatnonzero(~(lo[:4] < hi[:4]))[0])])
+    if bounds is not None:
+        if not isinstance(bounds, dict):
+            raise ValueError("bounds must be a dict {name: (lo, hi)} over %s" % (names,))
+        for name, (a, b) in bounds.items():
+            if name not in names:
+                raise ValueError("bounds: %r is not a fitted parameter (%s)" % (name, ", ".join(names)))
+            lo[names.index(name)], hi[names.index(name)] = float(a), float(b)
+    if not (np.all(np.isfinite(lo)) and np.all(np.isfinite(hi)) and np.all(lo < hi)):
+        raise ValueError("bounds: lo < hi, both finite, for every fitted parameter")
+    if "Av" in free and not hi[names.index("Av")] < sedfit.AV_MAX:
+        raise ValueError("the upper Av bound must be below %g: the model jumps there" % sedfit.AV_MAX)
+    sed_col = np.full(K, -1, dtype=np.int32)
+    sed_col[:4] = np.arange(4)
+    sed_col[Km:Km + Kp] = phot_cols
+    mu = sigma = None
+    if prior:
+        mu, sigma = np.zeros((N, K)), np.full((N, K), np.inf)
+        for name, ms in prior.items():
+            if name not in names:
+                raise ValueError("prior: %r is not a fitted parameter (%s)" % (name, ", ".join(names)))
+            m, s = (np.broadcast_to(np.asarray(a, dtype=np.float64), (N,)) for a in ms)
+            if np.any(np.isnan(s)) or np.any(s <= 0.0) or np.any(~np.isfinite(m) & np.isfinite(s)):
+                raise ValueError("prior on %s: sigmas must be positive (inf: no prior) and their centres finite" % name)
+            mu[:, names.index(name)], sigma[:, names.index(name)] = np.where(np.isfinite(s), m, 0.0), s
+    if "logR" in free and "Dist" in free:
+        if sigma is None or not np.all(np.isfinite(sigma[:, names.index("logR")]) | np.isfinite(sigma[:, names.index("Dist")])):
+            raise ValueError("logR and Dist are exactly degenerate in the magnitudes and the spectrum sees neither: every star needs a finite prior "
+                             "sigma on one of them")
+    return dict(flux=flux, eflux=eflux, start=start, coef=coef, clip=clip, opts=o, obs=obs, pw=pw, phot_start=np.ascontiguousarray(phot_start), names=names,
+                lo=lo, hi=hi, Km=Km, Kp=Kp, P=P, cols=cols, phot_cols=phot_cols, sed_col=sed_col, mu=mu, sigma=sigma)
+
+
+PhotBlock = collections.namedtuple("PhotBlock", "sed pars x0 phot_idx sed_col obs pw mu sigma")
+PhotBlock.__doc__ = """The photometric inputs of one block of stars in ``OptFit._fit_block``:
+    sed       the ``SEDFit``
+    pars      fp64 [nb, ncol] on the device: the photometric rows at the start; the fitted columns are overwritten from x_trial every iteration
+    x0        host [nb, Kp]: the start of the free photometric-only parameters
+    phot_idx  int64 [Kp] on the device: their columns of the row
+    sed_col   host int32 [K]: the column of the row that handle parameter k is, or -1
+    obs, pw   fp64 [nb, F] on the device: the magnitudes and 1 / sigma^2 (0: the filter does not count)
+    mu, sigma fp64 [nb, K] on the device, or both None: the Gaussian priors"""
+
+
 class _DeviceArray(object):
     """A device pointer the library owns, as torch reads it (``torch.as_tensor``)."""
 
@@ -204,6 +307,35 @@ class LMHandle(object):
         rc = self.lib.payne_lmfit_update_poly(self._h, P, rows.data_ptr(), n, flux.data_ptr(), w.data_ptr(), n, x.data_ptr(), n, self._stream())
         if rc != 0:
             raise RuntimeError("payne_lmfit_update_poly failed (%d)" % rc)
+
+    def update_phot(self, rows, flux, w, x, P, Kp, sed_col, mags, dmags, obs, pw, mu=None, sigma=None):
+        """The update for spectrum and magnitudes together (payne_lmfit_update_phot): the handle's parameters are K - Kp - P of the
+        spectral model, Kp that only the photometry sees and P >= 0 Chebyshev coefficients.  rows fp32 [B, 1 + K - Kp - P, n], flux,
+        w, x as ``update_poly`` takes them (x None for P = 0); sed_col [K] host ints; mags, obs, pw fp64 [B, F], dmags fp64
+        [B, F, ncol] (``SEDFit.grad_device``'s at the trial point); mu, sigma fp64 [B, K] or neither: device tensors."""
+        torch = self.torch
+        B, n, P, Kp, K = self.B, rows.shape[-1], int(P), int(Kp), self.K
+        Km = K - Kp - P
+        sed_col = np.ascontiguousarray(sed_col, dtype=np.int32)
+        if P < 0 or Kp < 0 or Km < 0 or sed_col.shape != (K,):
+            raise ValueError("P >= 0, Kp >= 0, P + Kp <= %d and sed_col [%d]; got P = %d, Kp = %d, sed_col %s" % (K, K, P, Kp, sed_col.shape))
+        F = mags.shape[-1]
+        if tuple(rows.shape) != (B, 1 + Km, n) or tuple(flux.shape) != (B, n) or tuple(w.shape) != (B, n) or (P > 0 and (x is None or tuple(x.shape) != (n,))):
+            raise ValueError("rows [%d, %d, n], flux and w [%d, n], x [n]; got %s, %s, %s, %s"
+                             % (B, 1 + Km, B, tuple(rows.shape), tuple(flux.shape), tuple(w.shape), None if x is None else tuple(x.shape)))
+        if dmags.dim() != 3 or tuple(dmags.shape[:2]) != (B, F) or any(tuple(a.shape) != (B, F) for a in (mags, obs, pw)):
+            raise ValueError("mags, obs, pw [%d, F] and dmags [%d, F, ncol]; got %s, %s, %s, %s" % (B, B, tuple(mags.shape), tuple(obs.shape), tuple(pw.shape), tuple(dmags.shape)))
+        if (mu is None) != (sigma is None) or (mu is not None and (tuple(mu.shape) != (B, K) or tuple(sigma.shape) != (B, K))):
+            raise ValueError("mu and sigma [%d, %d], both or neither" % (B, K))
+        f32 = [rows, flux]
+        f64 = [w, mags, dmags, obs, pw] + ([x] if P > 0 else []) + ([mu, sigma] if mu is not None else [])
+        if any(a.dtype != torch.float32 or not a.is_contiguous() for a in f32) or any(a.dtype != torch.float64 or not a.is_contiguous() for a in f64):
+            raise ValueError("rows and flux contiguous fp32, every other tensor contiguous fp64")
+        rc = self.lib.payne_lmfit_update_phot(self._h, Km, Kp, P, rows.data_ptr(), n, flux.data_ptr(), w.data_ptr(), n, x.data_ptr() if P > 0 else None, n,
+                                              F, dmags.shape[2], sed_col.ctypes.data, mags.data_ptr(), dmags.data_ptr(), obs.data_ptr(), pw.data_ptr(),
+                                              None if mu is None else mu.data_ptr(), None if sigma is None else sigma.data_ptr(), self._stream())
+        if rc != 0:
+            raise RuntimeError("payne_lmfit_update_phot failed (%d): %s" % (rc, self.lib.payne_last_error(None).decode()))
 
     def status(self):
         torch = self.torch
@@ -295,9 +427,12 @@ class OptFit(object):
         out["err"] = crlb_from_fisher(out["fisher"])
         return out
 
-    def _fit_block(self, handle, flux, w, start, cols, lo, hi, fit_vrad, vrad_step, check_every, maxiter, coef=None, x=None):
+    def _fit_block(self, handle, flux, w, start, cols, lo, hi, fit_vrad, vrad_step, check_every, maxiter, coef=None, x=None, phot=None):
         """One block of stars through the handle.  ``coef`` [nb, P] and ``x``: the handle's parameters are the fitted columns and then
-        the coefficients, and the update is ``update_poly`` on the abscissa ``x`` (``fit_joint``)."""
+        the coefficients, and the update is ``update_poly`` on the abscissa ``x`` (``fit_joint``).  ``phot``: a ``PhotBlock``
+        (``fit_specphot``).  Its Kp parameters sit between the fitted columns and the coefficients; one more enqueued step an iteration
+        copies the fitted columns of the photometric rows from x_trial on the device and evaluates ``sed.grad_device`` there; the update
+        is ``update_phot``."""
         P = self.predictor
         eng, D, jac_net = P.anns.engine, self.n_labels, P._jacobian()
         torch = eng.torch
@@ -305,7 +440,7 @@ class OptFit(object):
         dev = eng.device
         flux_d = torch.as_tensor(np.ascontiguousarray(flux)).to(dev)
         w_d = torch.as_tensor(np.ascontiguousarray(w)).to(dev)
-        handle.begin(start[:, cols] if coef is None else np.concatenate([start[:, cols], coef], axis=1), lo, hi)
+        handle.begin(np.concatenate([start[:, cols]] + ([] if phot is None else [phot.x0]) + ([] if coef is None else [coef]), axis=1), lo, hi)
         xt = handle.trial()
         # the theta blocks, uploaded once: the model's [nb], the derivative rows' [nb * D], and Vrad +- step's [2 nb]
         th = np.full((nb, eng.ncols), np.nan)
@@ -340,7 +475,15 @@ class OptFit(object):
             rows[:, 0] = eng.smooth_batch(y, th_y, stage=2)
             rows[:, 1:1 + D] = smooth_rows(eng, jac.reshape(nb * D, -1), th_j, 2).reshape(nb, D, nobs)
             mark()
-            if coef is None:
+            if phot is not None:
+                Kp = phot.x0.shape[1]
+                phot.pars[:, :4] = xt[:, :4]
+                if Kp:
+                    phot.pars.index_copy_(1, phot.phot_idx, xt[:, K:K + Kp])
+                mags, dmags = phot.sed.grad_device(phot.pars)
+                mark()
+                handle.update_phot(rows, flux_d, w_d, x, 0 if coef is None else coef.shape[1], Kp, phot.sed_col, mags, dmags, phot.obs, phot.pw, phot.mu, phot.sigma)
+            elif coef is None:
                 handle.update(rows, flux_d, w_d)
             else:
                 handle.update_poly(rows, flux_d, w_d, x, coef.shape[1])
@@ -350,10 +493,10 @@ class OptFit(object):
         res = handle.result()
         if tm is not None:
             torch.cuda.synchronize(dev)
-            for i in range(0, len(marks), 4):
-                tm["network"] += marks[i].elapsed_time(marks[i + 1])
-                tm["broadening"] += marks[i + 1].elapsed_time(marks[i + 2])
-                tm["update"] += marks[i + 2].elapsed_time(marks[i + 3])
+            steps = ("network", "broadening") + (() if phot is None else ("sed",)) + ("update",)   # a mark before each and one behind the last
+            for i in range(0, len(marks), len(steps) + 1):
+                for j, name in enumerate(steps):
+                    tm[name] += marks[i + j].elapsed_time(marks[i + j + 1])
             tm["iterations"] += it
         return res
 
@@ -489,6 +632,108 @@ class OptFit(object):
                     out["status"][idx] = res["status"].cpu().numpy()
                     out["niter"][idx] = res["niter"].cpu().numpy()
                     out["at_bound"][idx] = res["at_bound"].cpu().numpy().astype(np.uint32)
+            finally:
+                handle.close()
+        out["err"] = crlb_from_fisher(out["fisher"])
+        return out
+
+    def fit_specphot(self, flux, eflux, mags, emags, start, phot_start, sed, free_phot=("logR", "Av"), npoly=0, coef=None, clip=None, fit_vrad=False,
+                     bounds=None, coef_bounds=None, prior=None, vrad_step=0.25, check_every=4, timing=False, **opts):
+        """Spectrum and photometry in ONE Levenberg-Marquardt fit: chi^2 = sum_p w_p (flux_p - model_p p(x_p))^2 + sum_f (mag_f -
+        model_f)^2 / emag_f^2 + Gaussian priors, over K = K_m + K_p + npoly <= 15 parameters.  Teff, log(g), [Fe/H], [a/Fe] are shared
+        by both; Vmic (five-label network) and Vrad (``fit_vrad``) are the spectrum's; ``free_phot`` names the photometric-only
+        parameters that are fitted (among logR, Dist, Av, or logA, Av with ``sed.photscale``).  ``sed``: a ``SEDFit`` on the same
+        device, whose filters and ``photscale`` define the magnitudes; ``mags``, ``emags`` [N, F] follow ``SEDFit.fit``'s rule for a
+        filter that does not count; ``phot_start`` [N, ncol - 4] holds the photometric-only columns in ``sedfit.par_names(photscale)[4:]``
+        order, those not in ``free_phot`` stay fixed there.  ``flux``, ``eflux``, ``start``, ``npoly``, ``coef``, ``clip``,
+        ``coef_bounds`` are ``fit_joint``'s; ``npoly=0``: no polynomial.
+
+        The default box of a shared label is the intersection of the spectral network's and ``sed``'s; ``bounds`` = {name: (lo, hi)}
+        over all fitted parameters (``labels`` of the result).  ``prior`` = {name: (mu [N], sigma [N])}, Gaussian, on any fitted
+        parameter, an infinite sigma meaning none.  logR and Dist are exactly degenerate in the magnitudes and the spectrum sees
+        neither: ``free_phot`` with both needs a finite prior on one of them for every star (a parallax, say).
+
+        One iteration is four enqueued steps and no host look: payne_specjac_eval, the broadening of the 1 + K_m rows,
+        ``sed.grad_device`` on the photometric rows gathered from x_trial on the device, and payne_lmfit_update_phot, which adds the
+        photometric block and the priors to the spectral normal equations before the step is taken.
+
+        Returns ``fit_joint``'s dict over all K parameters (``fisher`` [N, K, K] with the priors, ``err`` = sqrt(diag(inv(fisher))): the
+        labels' errors are marginalised over logR / Dist / Av and the polynomial; ``chisq`` with the magnitudes' and the priors'
+        terms) plus ``phot_pars`` [N, ncol] (the photometric row at the solution), ``nfilt`` (filters that count) and ``mags_model``
+        [N, F] there (one more ``sed.grad`` a block of stars after the loop, with its copy to the host).  ``timing``: as ``fit``'s,
+        with ``sed`` the third step.
+
+        Status on real data.  The spectral model and its rows are fp32, so chi^2 at a trial point carries a rounding term of about
+        2 w sqrt(n) |r| 6e-8 (r the spectral residual at the solution) that changes from trial to trial: 2e-6 .. 5e-6 measured with 37
+        pixels at S/N 100 once magnitudes that scatter by their 0.02 mag errors pull the labels off the spectrum's own minimum.  The
+        step that decides convergence, xtol = 1e-3 sigma, gains 1e-6.  update_star accepts a trial on chi^2 <= the best so far, so a
+        best point that rounded low is followed by rejections until lambda is large enough for the model not to change (``CONVERGED``
+        after ten or twenty evaluations) or reaches lambda_max (``STALLED``).  Both end within 1e-2 sigma of the fp64 solution
+        (tests/test_lmfit_phot_gpu.py) and both carry a valid ``fisher`` and ``err``: treat ``STALLED`` as converged here, or pass a
+        larger ``xtol``.  ``fit`` and ``fit_joint`` meet the same floor on spectra whose residuals are not small."""
+        from . import sedfit
+        if not isinstance(sed, sedfit.SEDFit):
+            raise TypeError("sed must be a SEDFit")
+        Pr = self.predictor
+        anns, eng, D = Pr.anns, Pr.anns.engine, self.n_labels
+        c = check_specphot_args(flux, eflux, mags, emags, start, phot_start, len(self.obs_wave), D, anns.xmin, anns.xmax, sed.F, sed.xmin, sed.xmax,
+                                photscale=sed.photscale, free_phot=free_phot, npoly=npoly, coef=coef, clip=clip, fit_vrad=fit_vrad, bounds=bounds,
+                                coef_bounds=coef_bounds, prior=prior, vrad_step=vrad_step, check_every=check_every, **opts)
+        from .contfit import ContinuumFit, abscissa
+        torch = sed._setup()
+        if sed.device != eng.device:
+            raise ValueError("sed is on %s, the spectral network on %s" % (sed.device, eng.device))
+        flux, eflux, start, coef, clip, o = c["flux"], c["eflux"], c["start"], c["coef"], c["clip"], c["opts"]
+        cols, Km, Kp, P, lo, hi = c["cols"], c["Km"], c["Kp"], c["P"], c["lo"], c["hi"]
+        K, N, ncol = Km + Kp + P, flux.shape[0], len(sed.names)
+        w = weights_from_errors(eflux)
+        cont_status = np.full(N, _lib.CONTFIT_OK, dtype=np.int32)
+        x = abscissa(self.obs_wave)
+        if P and coef is None:
+            cont = ContinuumFit(self.obs_wave, npoly=P, device=eng.device, drop_clipped=True, **clip)
+            cf = cont.fit(flux, eflux, self.model_spectra(start), normalise=bool(clip))
+            cf = {k: v.cpu().numpy() for k, v in cf.items()}
+            coef, cont_status = cf["coef"], cf["status"].astype(np.int32)
+            if clip:
+                w = np.where((cf["weights"] == 0.0) & (np.polynomial.chebyshev.chebval(x, np.nan_to_num(coef).T) > 0.0), 0.0, w)
+        good = (cont_status == _lib.CONTFIT_OK) | (cont_status == _lib.CONTFIT_NONPOSITIVE)
+        phot_pars = np.concatenate([start[:, :4], c["phot_start"]], axis=1)
+        out = dict(pars=start.copy(), chisq=np.full(N, np.nan), npix=(w != 0.0).sum(axis=1), fisher=np.full((N, K, K), np.nan),
+                   status=np.full(N, _lib.LMFIT_NAN, dtype=np.int32), niter=np.zeros(N, dtype=np.int32), at_bound=np.zeros(N, dtype=np.uint32),
+                   labels=list(c["names"]), coef=np.full((N, P), np.nan), cont_status=cont_status, phot_pars=phot_pars.copy(),
+                   nfilt=(c["pw"] != 0.0).sum(axis=1), mags_model=np.full((N, sed.F), np.nan))
+        out["pars"][:, cols] = np.nan
+        out["phot_pars"][:, :4] = np.nan
+        out["phot_pars"][:, c["phot_cols"]] = np.nan
+        Pr._bind(self.obs_wave)
+        step = max(1, eng.b_max // (1 + Km + 2 * int(bool(fit_vrad))))
+        sel = np.flatnonzero(good)
+        self.timing = dict(network=0.0, broadening=0.0, sed=0.0, update=0.0, iterations=0) if timing else None
+        if len(sel):
+            dev = eng.device
+            handle = LMHandle(K, min(step, len(sel)), dev, **o)
+            x_d = torch.as_tensor(x).to(dev) if P else None
+            idx_d = torch.as_tensor(np.asarray(c["phot_cols"], dtype=np.int64)).to(dev)
+            try:
+                for s in range(0, len(sel), step):
+                    idx = sel[s:s + step]
+                    up = lambda a: torch.as_tensor(np.ascontiguousarray(a[idx], dtype=np.float64)).to(dev)   # noqa: E731
+                    phot = PhotBlock(sed=sed, pars=up(phot_pars), x0=phot_pars[idx][:, c["phot_cols"]], phot_idx=idx_d, sed_col=c["sed_col"], obs=up(c["obs"]),
+                                     pw=up(c["pw"]), mu=None if c["mu"] is None else up(c["mu"]), sigma=None if c["sigma"] is None else up(c["sigma"]))
+                    res = self._fit_block(handle, flux[idx], w[idx], start[idx], cols, lo, hi, bool(fit_vrad), float(vrad_step), int(check_every),
+                                          int(o["maxiter"]), coef=np.ascontiguousarray(coef[idx], dtype=np.float64) if P else None, x=x_d, phot=phot)
+                    xb = res["x_best"].cpu().numpy()
+                    out["pars"][idx[:, None], np.asarray(cols)[None, :]] = xb[:, :Km]
+                    out["phot_pars"][idx, :4] = xb[:, :4]
+                    if Kp:
+                        out["phot_pars"][idx[:, None], np.asarray(c["phot_cols"])[None, :]] = xb[:, Km:Km + Kp]
+                    out["coef"][idx] = xb[:, Km + Kp:]
+                    out["chisq"][idx] = res["chisq"].cpu().numpy()
+                    out["fisher"][idx] = res["A"].cpu().numpy()
+                    out["status"][idx] = res["status"].cpu().numpy()
+                    out["niter"][idx] = res["niter"].cpu().numpy()
+                    out["at_bound"][idx] = res["at_bound"].cpu().numpy().astype(np.uint32)
+                    out["mags_model"][idx] = sed.grad(out["phot_pars"][idx])[0]
             finally:
                 handle.close()
         out["err"] = crlb_from_fisher(out["fisher"])

@@ -4,6 +4,8 @@ payne_lmfit_update an iteration) against scipy.optimize.least_squares around the
     python tools/optfit_bench.py [--stars 4096] [--nobs 3600] [--b-max 2560] [--repeats 5] [--warmup 1] [--scipy-stars 8]
     python tools/optfit_bench.py --npoly 4 [--ref-stars 6] [--alt-rounds 3,10,20,40]     (OptFit.fit_joint: joint_mode below)
 
+    python tools/optfit_bench.py --phot 7 [--npoly 4]                                       (OptFit.fit_specphot: phot_mode below)
+
 The workload: SMLP 4-256-256-256-4096 (synth.make_torch_net), 3600 observed pixels, stars drawn in the inner half of the label box
 with their own Vrad / Vrot / inst_R, spectra from the model itself plus seeded noise at S/N 100, starts 10 % of the box off the
 truth.  A timed unit is one whole ``fit`` (uploads, every iteration, the results back on the host) between two host clocks with a
@@ -190,6 +192,93 @@ def joint_mode(args):
     print(json.dumps(out), flush=True)
 
 
+def phot_mode(args):
+    """--phot F: the --npoly workload (P = 4 unless --npoly says otherwise) with F magnitudes a star from random per-filter nets with
+    colour (synth.make_phot_nets, w1 x 3, w3 x 30, width 64), 0.02 mag errors, logR and Av free and starting 10 % of their box off,
+    the distance fixed.  (a) ``fit_specphot`` stars/s and the per-iteration split network / broadening / SED Jacobian / update, next to
+    ``fit_joint`` on the spectra alone in the same process; (b) the update alone for one block of stars, event pairs on the stream,
+    every star RUNNING: payne_lmfit_update_phot at K = 4 + 2 + P against payne_lmfit_update_poly at the same K (six model rows: it
+    streams two more rows a star) and at K = 4 + P (the same rows)."""
+    import torch
+    from numpy.polynomial.chebyshev import chebvander
+    from thepayne_amd import synth
+    from thepayne_amd.fitting import SEDFit
+    from thepayne_amd.fitting.optfit import OptFit, LMHandle
+    from thepayne_amd.fitting.contfit import abscissa
+    F, P, N, n = args.phot, args.npoly or 4, args.stars, args.nobs
+    net, obs_wave, truth, start, rng = workload(N, n)
+    fit = OptFit(net, "SMLP", obs_wave, b_max=args.b_max)
+    eng = fit.predictor.anns.engine
+    clean = fit.model_spectra(truth).cpu().numpy().astype(np.float64)
+    x = abscissa(obs_wave)
+    ctrue = np.concatenate([rng.uniform(0.5, 2.0, (N, 1)), rng.uniform(-0.1, 0.1, (N, P - 1))], axis=1)
+    poly = np.ascontiguousarray((chebvander(x, P - 1) @ ctrue.T).T)
+    flux = ((clean + rng.normal(0, 0.01, (N, n))) * poly).astype(np.float32)
+    eflux = 0.01 * poly
+    phot = synth.make_phot_nets(filters=["f%03d" % i for i in range(F)], H=64, seed=1)
+    phot["w1"], phot["w3"] = (phot["w1"] * np.float32(3.0)).astype(np.float32), (phot["w3"] * np.float32(30.0)).astype(np.float32)
+    phot["hiav"] = np.zeros((F, 5))
+    sed = SEDFit(usebands=phot["filters"], nnpath=phot, device=eng.device)
+    box = {"logR": (-1.0, 2.0), "Av": (0.0, 4.5)}
+    ptruth = np.column_stack([rng.uniform(-0.3, 1.5, N), rng.uniform(100.0, 3000.0, N), rng.uniform(0.1, 2.0, N)])
+    pstart = ptruth.copy()
+    for c, nm in ((0, "logR"), (2, "Av")):
+        pstart[:, c] = np.clip(ptruth[:, c] + 0.1 * (box[nm][1] - box[nm][0]) * rng.choice([-1.0, 1.0], N), *box[nm])
+    mags = sed.grad(np.concatenate([truth[:, :4], ptruth], axis=1))[0] + rng.normal(0, 0.02, (N, F))
+    emags = np.full((N, F), 0.02)
+
+    def clock(call):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        res = call()
+        torch.cuda.synchronize()
+        return time.perf_counter() - t0, res
+
+    def both(**kw):
+        return fit.fit_specphot(flux, eflux, mags, emags, start, pstart, sed, free_phot=("logR", "Av"), npoly=P, bounds=box, **kw)
+    out = {"mode": "phot", "filters": F, "npoly": P, "stars": N, "nobs": n, "b_max": args.b_max, "repeats": args.repeats, "warmup": args.warmup}
+    for name, call in (("fit_specphot", both), ("fit_joint", lambda **kw: fit.fit_joint(flux, eflux, start, npoly=P, **kw))):
+        for _ in range(args.warmup):
+            clock(call)
+        secs = []
+        for _ in range(args.repeats):
+            s, res = clock(call)
+            secs.append(s)
+        clock(lambda: call(timing=True))
+        tm = fit.timing
+        out[name] = {"s_median": float(np.median(secs)), "s_min": float(np.min(secs)), "stars_per_s": N / float(np.median(secs)),
+                     "status_counts": np.bincount(res["status"], minlength=6).tolist(), "evaluations_median": float(np.median(res["niter"])),
+                     "evaluations_max": int(res["niter"].max()), "block_iterations": tm["iterations"],
+                     "ms_per_iteration": {k: tm[k] / tm["iterations"] for k in tm if k != "iterations"}}
+    # (b) the update alone, every star RUNNING (a fresh begin before each launch, outside the event pair)
+    Km, Kp, B, dev = 4, 2, min(N, max(1, args.b_max // 5)), eng.device
+    K = Km + Kp + P
+    rows = torch.randn((B, 1 + Km + Kp, n), dtype=torch.float32, device=dev)
+    rows[:, 0] = 1.0 + 0.1 * rows[:, 0]
+    rows4 = rows[:, :1 + Km].contiguous()
+    flux_d, w_d, x_d = torch.as_tensor(flux[:B]).to(dev), torch.as_tensor(1.0 / eflux[:B] ** 2).to(dev), torch.as_tensor(x).to(dev)
+    prow = torch.as_tensor(np.concatenate([start[:B, :4], pstart[:B]], axis=1)).to(dev)
+    m_d, dm_d = sed.grad_device(prow)
+    obs_d, pw_d = torch.as_tensor(mags[:B]).to(dev), torch.as_tensor(1.0 / emags[:B] ** 2).to(dev)
+    sed_col = np.array([0, 1, 2, 3, 4, 6] + [-1] * P, dtype=np.int32)
+    lo = np.concatenate([net["xmin"], [box["logR"][0], box["Av"][0]], np.full(P, -1e30)])
+    hi = np.concatenate([net["xmax"], [box["logR"][1], box["Av"][1]], np.full(P, 1e30)])
+    x0 = np.concatenate([start[:B, :4], pstart[:B][:, [0, 2]], ctrue[:B]], axis=1)
+    sel = [0, 1, 2, 3] + list(range(6, K))
+    hK, h4 = LMHandle(K, B, dev), LMHandle(Km + P, B, dev)
+    ms_phot = event_ms(torch, lambda: hK.begin(x0, lo, hi), lambda: hK.update_phot(rows4, flux_d, w_d, x_d, P, Kp, sed_col, m_d, dm_d, obs_d, pw_d),
+                       args.repeats * 4, args.warmup + 2)
+    ms_poly_K = event_ms(torch, lambda: hK.begin(x0, lo, hi), lambda: hK.update_poly(rows, flux_d, w_d, x_d, P), args.repeats * 4, args.warmup + 2)
+    ms_poly_4 = event_ms(torch, lambda: h4.begin(x0[:, sel], lo[sel], hi[sel]), lambda: h4.update_poly(rows4, flux_d, w_d, x_d, P), args.repeats * 4, args.warmup + 2)
+    ms_sed = event_ms(torch, lambda: None, lambda: sed.grad_device(prow), args.repeats * 4, args.warmup + 2)
+    hK.close()
+    h4.close()
+    out.update({"stars_per_block": B, "K": K, "update_phot_ms": ms_phot, "update_poly_ms_same_K": ms_poly_K, "update_poly_ms_same_rows": ms_poly_4, "sed_jac_ms": ms_sed,
+                "update_phot_over_update_poly_same_K": ms_phot / ms_poly_K, "update_phot_over_update_poly_same_rows": ms_phot / ms_poly_4,
+                "fit_specphot_over_fit_joint_time": out["fit_specphot"]["s_median"] / out["fit_joint"]["s_median"]})
+    print(json.dumps(out), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--stars", type=int, default=4096)
@@ -201,7 +290,10 @@ def main():
     ap.add_argument("--npoly", type=int, default=0, help="fit a continuum polynomial of this many coefficients along (fit_joint)")
     ap.add_argument("--ref-stars", type=int, default=6, help="--npoly: stars compared with the fp64 joint reference loop")
     ap.add_argument("--alt-rounds", type=lambda s: [int(v) for v in s.split(",")], default=[3, 10, 20, 40], help="--npoly: fit_with_continuum's rounds")
+    ap.add_argument("--phot", type=int, default=0, help="fit this many magnitudes a star along with the spectrum, logR and Av free (fit_specphot)")
     args = ap.parse_args()
+    if args.phot:
+        return phot_mode(args)
     if args.npoly:
         return joint_mode(args)
     import torch
