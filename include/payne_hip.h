@@ -681,6 +681,34 @@ int payne_tmatch_match(payne_tmatch* h, const float* templates_dev, int ld_t, in
 int payne_tmatch_chunk(void);
 void payne_tmatch_destroy(payne_tmatch* h);
 
+/* The search with a free continuum polynomial per (star, template) pair:
+ *   chi^2[s][t] = min_c sum_p w[s][p] (flux[s][p] - m[t][p] sum_j c_j T_j(x[p]))^2, c the P <= PAYNE_TMATCH_MAX_POLY Chebyshev
+ * coefficients in payne_contfit_batch's basis and abscissa x (|x| <= 1) -- the chi^2 that payne_contfit_batch and
+ * payne_lmfit_update_poly minimise.  3 P - 1 matrix products over n on the fp64 matrix instruction (b_j = sum (w f T_j) m,
+ * S_q = sum (w T_q) m^2, q <= 2 P - 2), A_jk = (S_{j+k} + S_{|j-k|}) / 2, A c = b by the scaled Cholesky solve, and
+ * chi^2 = c0 + c^T A c - 2 c^T b; csrc/tmatch_poly_core.hpp holds the arithmetic and its order.  The rules are payne_tmatch_match's
+ * except:
+ *   NaN      a pair is also NaN when the star has fewer than P pixels with w != 0 or when the solve refuses (a template that is zero
+ *            at every such pixel).  So a star without a weighted pixel lists nothing (idx -1, chisq +inf), where
+ *            payne_tmatch_match lists chi^2 = 0 for it.
+ *   lists    every entry carries its coefficients: coef_dev DEVICE fp64 [N][topk][P] (NaN where idx is -1) and flags_dev DEVICE
+ *            int32 [N][topk]: bit 0 is set when the polynomial is > 0 at every pixel of the star with w != 0.  A template whose
+ *            polynomial turns negative stays listed.
+ *   order    the grid is (tiles of payne_tmatch_poly_stars() stars) x (chunks of payne_tmatch_poly_chunk() templates).
+ * payne_tmatch_create_poly: payne_tmatch_create plus the workspace of match_poly for P <= max_poly; payne_tmatch_match works on
+ * such a handle as on any other.  PAYNE_E_INVALID as payne_tmatch_create, and max_poly outside 1 .. PAYNE_TMATCH_MAX_POLY.
+ * payne_tmatch_match_poly: x_dev DEVICE fp64 [n]; the other arrays as payne_tmatch_match's.  PAYNE_E_INVALID as payne_tmatch_match,
+ * and P outside 1 .. the handle's max_poly (a handle of payne_tmatch_create has max_poly = 0), a null x_dev / coef_dev / flags_dev.
+ * Nothing is touched on a refusal; N == 0 or M == 0 succeeds and does nothing. */
+#define PAYNE_TMATCH_MAX_POLY 8
+
+int payne_tmatch_create_poly(int device, int max_stars, int max_templates, int max_poly, payne_tmatch** out);
+int payne_tmatch_match_poly(payne_tmatch* h, const float* templates_dev, int ld_t, int M, const float* flux_dev, const double* w_dev,
+                            int ld_f, int N, int n, const double* x_dev, int P, int topk, int* idx_dev, double* chisq_dev,
+                            double* coef_dev, int* flags_dev, double* all_dev, long long ld_a, void* stream);
+int payne_tmatch_poly_stars(void);
+int payne_tmatch_poly_chunk(void);
+
 /* ---- continuum polynomials: the blaze's Chebyshev coefficients for many stars against a given model row each ----
  * payne_contfit_batch: per star the c [P] that minimise chi^2 = sum_p w_p (f_p - m_p sum_j c_j T_j(x_p))^2, the likelihood's own
  * objective in its pc_* parameters (modpoly: model x polycalc) for a fixed model, which is linear least squares; optional

@@ -44,6 +44,7 @@ SYMBOLS = ["payne_version", "payne_ctx_create", "payne_ctx_set_obs", "payne_ctx_
            "payne_lmfit_create", "payne_lmfit_begin", "payne_lmfit_trial", "payne_lmfit_update", "payne_lmfit_update_poly", "payne_lmfit_update_phot", "payne_lmfit_result",
            "payne_lmfit_destroy",
            "payne_tmatch_create", "payne_tmatch_match", "payne_tmatch_chunk", "payne_tmatch_destroy",
+           "payne_tmatch_create_poly", "payne_tmatch_match_poly", "payne_tmatch_poly_stars", "payne_tmatch_poly_chunk",
            "payne_contfit_batch",
            "payne_sedfit_create", "payne_sedfit_jac", "payne_sedfit_run", "payne_sedfit_destroy"]
 
@@ -131,6 +132,7 @@ SEDFIT_TOO_FEW, SEDFIT_MAX_K, SEDFIT_MAX_H = 6, 7, 64       # payne_sedfit_run's
 LMFIT_MAX_K = 15
 LMFIT_PHOT_MAX_F = 64                                      # payne_lmfit_update_phot stages a star's filters in LDS
 TMATCH_MAX_TOPK = 8
+TMATCH_MAX_POLY = 8
 CONTFIT_OK, CONTFIT_NONPOSITIVE, CONTFIT_TOO_FEW, CONTFIT_SINGULAR, CONTFIT_NAN, CONTFIT_BAD_MODEL = range(6)
 CONTFIT_STATUS_NAMES = ("OK", "NONPOSITIVE", "TOO_FEW", "SINGULAR", "NAN", "BAD_MODEL")
 CONTFIT_MAX_P, CONTFIT_MAX_NCLIP, CONTFIT_MAX_N = 15, 16, 262144
@@ -301,6 +303,14 @@ def load(path=None):
     lib.payne_tmatch_chunk.restype = C.c_int
     lib.payne_tmatch_destroy.argtypes = [ctxp]
     lib.payne_tmatch_destroy.restype = None
+    lib.payne_tmatch_create_poly.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(ctxp)]
+    lib.payne_tmatch_create_poly.restype = C.c_int
+    lib.payne_tmatch_match_poly.argtypes = [ctxp, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int,
+                                            C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_longlong, C.c_void_p]
+    lib.payne_tmatch_match_poly.restype = C.c_int
+    for name in ("payne_tmatch_poly_stars", "payne_tmatch_poly_chunk"):
+        getattr(lib, name).argtypes = []
+        getattr(lib, name).restype = C.c_int
     lib.payne_contfit_batch.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_longlong, C.c_void_p, C.c_longlong, C.c_int, C.c_void_p, C.c_void_p,
                                         C.c_int, C.c_int, C.POINTER(ContfitOpts), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                         C.c_void_p, C.c_void_p, C.c_longlong, C.c_void_p]

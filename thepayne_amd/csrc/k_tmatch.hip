@@ -21,11 +21,7 @@
 
 namespace tq = payne::tmatch;
 
-struct payne_tmatch {
-  int device = 0, max_stars = 0, max_templates = 0;
-  double* part_c = nullptr;   // [chunks][N][topk]
-  int* part_i = nullptr;
-};
+#include "tmatch_handle.hpp"
 
 namespace {
 
@@ -258,6 +254,9 @@ extern "C" void payne_tmatch_destroy(payne_tmatch* h) {
       (void)hipDeviceSynchronize();
       (void)hipFree(h->part_c);
       (void)hipFree(h->part_i);
+      (void)hipFree(h->poly_c);                                     // (null unless payne_tmatch_create_poly made the handle)
+      (void)hipFree(h->poly_i);
+      (void)hipFree(h->poly_coef);
     }
   }
   delete h;

@@ -167,7 +167,9 @@ class ContinuumFit(object):
     def fit_to_bank(self, flux, eflux, bank, match=None, rank=0):
         """``fit`` against the template of rank ``rank`` that ``bank`` (a ``tmatch.TemplateBank`` on this ``obs_wave``) matched to each
         star: the bank's templates are read in place through the index, nothing is gathered.  ``match``: ``bank.match``'s dict (run
-        here with topk = rank + 1 when None).  A star without such a template (index -1) gets the status BAD_MODEL."""
+        here with topk = rank + 1 when None).  A star without such a template (index -1) gets the status BAD_MODEL.  For spectra
+        that are not on the model's continuum hand in ``bank.match(flux, eflux, npoly=P)``'s dict: its ranking has the polynomial
+        minimised out, and only its ``index`` is read here."""
         if not hasattr(bank, "match") or not hasattr(bank, "obs_wave"):
             raise TypeError("bank must be a TemplateBank")
         if np.shape(bank.obs_wave) != self.obs_wave.shape or not np.array_equal(np.asarray(bank.obs_wave), self.obs_wave):

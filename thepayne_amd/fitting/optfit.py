@@ -776,3 +776,48 @@ class OptFit(object):
                 out[name][dst] = res[name][take]
             out["start_index"][dst], out["start_chisq"][dst], out["start_rank"][dst] = m["index"][dst, r], m["chisq"][dst, r], r
         return out
+
+    def fit_joint_from_bank(self, flux, eflux, bank, npoly=4, topk=1, **fit_joint_kwargs):
+        """``fit_joint`` started from the ``topk`` templates of ``bank`` that match each star best under a free continuum
+        polynomial (``bank.match(npoly=npoly)``): per rank the template's parameters are the start and the match's coefficients
+        the starting ``coef``.  ``fit_from_bank``'s logic otherwise: one ``fit_joint`` call per rank over the stars that have a
+        template of that rank; per star the result of lowest chi^2 among those whose status is not NAN / SINGULAR is kept, the lower
+        rank on a tie (rank 0's if none qualifies).  Returns ``fit_joint``'s dict plus ``start_index``, ``start_chisq`` and
+        ``start_rank``; a star that no template matches keeps status NAN, NaN ``pars`` and ``start_index`` -1.
+        ``fit_joint_kwargs`` go to ``fit_joint``."""
+        if not hasattr(bank, "match") or not hasattr(bank, "obs_wave"):
+            raise TypeError("bank must be a TemplateBank")
+        if np.shape(bank.obs_wave) != self.obs_wave.shape or not np.array_equal(np.asarray(bank.obs_wave), self.obs_wave):
+            raise ValueError("the bank's obs_wave differs from the fitter's")
+        for name in ("start", "coef"):
+            if name in fit_joint_kwargs:
+                raise TypeError("fit_joint_from_bank takes its starts and coefficients from the bank")
+        if isinstance(npoly, bool) or int(npoly) != npoly or not (1 <= int(npoly) <= _lib.TMATCH_MAX_POLY):
+            raise ValueError("npoly must be 1 .. %d, got %r" % (_lib.TMATCH_MAX_POLY, npoly))
+        P = int(npoly)
+        flux = np.atleast_2d(np.asarray(flux, dtype=np.float32))
+        eflux = np.atleast_2d(np.asarray(eflux, dtype=np.float64))
+        m = bank.match(flux, eflux, topk=topk, npoly=P)
+        N, k = m["index"].shape
+        fit_vrad = bool(fit_joint_kwargs.get("fit_vrad", False))
+        K = len(fitted_columns(self.n_labels, fit_vrad)) + P
+        out = dict(pars=np.full((N, 8), np.nan), chisq=np.full(N, np.nan), npix=m["npix"], fisher=np.full((N, K, K), np.nan),
+                   status=np.full(N, _lib.LMFIT_NAN, dtype=np.int32), niter=np.zeros(N, dtype=np.int32), at_bound=np.zeros(N, dtype=np.uint32),
+                   labels=self.labels(fit_vrad) + ["pc_%d" % j for j in range(P)], err=np.full((N, K), np.nan), coef=np.full((N, P), np.nan),
+                   cont_status=np.full(N, _lib.CONTFIT_OK, dtype=np.int32),
+                   start_index=np.full(N, -1, dtype=np.int32), start_chisq=np.full(N, np.inf), start_rank=np.full(N, -1, dtype=np.int32))
+        per_star = ("pars", "chisq", "npix", "fisher", "status", "niter", "at_bound", "err", "coef", "cont_status")
+        for r in range(k):
+            sel = np.flatnonzero(m["index"][:, r] >= 0)
+            if len(sel) == 0:
+                continue
+            res = self.fit_joint(flux[sel], eflux[sel], m["pars"][sel, r], npoly=P, coef=m["coef"][sel, r], **fit_joint_kwargs)
+            valid = (res["status"] != _lib.LMFIT_NAN) & (res["status"] != _lib.LMFIT_SINGULAR)
+            held = out["start_rank"][sel] >= 0
+            held_valid = held & (out["status"][sel] != _lib.LMFIT_NAN) & (out["status"][sel] != _lib.LMFIT_SINGULAR)
+            take = ~held | (valid & (~held_valid | (res["chisq"] < out["chisq"][sel])))
+            dst = sel[take]
+            for name in per_star:
+                out[name][dst] = res[name][take]
+            out["start_index"][dst], out["start_chisq"][dst], out["start_rank"][dst] = m["index"][dst, r], m["chisq"][dst, r], r
+        return out

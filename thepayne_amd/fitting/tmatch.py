@@ -6,8 +6,14 @@ chi^2 = sum_p w_p (flux_p - template_p)^2 with their chi^2 and parameters.  The 
 the fp64 matrix instruction (payne_tmatch_match; include/payne_hip.h states the rules): the three terms of the expanded square are
 ~1e4 times their sum at S/N 100, so the sums are fp64 throughout and the result is within (2 n + 4) 2^-53 of the terms' magnitudes.
 
-No free amplitude or continuum polynomial per template, no interpolation between the lattice's nodes: the best template is a
-start for a fit, not a measurement.  ``OptFit.fit_from_bank`` runs the fit from the best few.
+``match(npoly=P)`` minimises a continuum polynomial of P <= 8 Chebyshev coefficients (``polycalc``'s basis and abscissa) out of
+every (star, template) pair, chi^2 = min_c sum_p w_p (flux_p - template_p sum_j c_j T_j(x_p))^2: the chi^2 of ``ContinuumFit`` and
+``OptFit.fit_joint``, so flux-calibrated or blaze-shaped spectra enter the pipeline here (payne_tmatch_match_poly: 3 P - 1 matrix
+products, a scaled Cholesky solve per pair).  Its dict goes to ``ContinuumFit.fit_to_bank(match=)`` as it is, and
+``OptFit.fit_joint_from_bank`` starts the joint fit from the best few with their coefficients.
+
+No interpolation between the lattice's nodes: the best template is a start for a fit, not a measurement.
+``OptFit.fit_from_bank`` runs the fit from the best few.
 """
 import ctypes as C
 import itertools
@@ -19,7 +25,7 @@ from ..engine import THETA_SPEC_COLS
 from ..predict._spec import PayneSpecPredict
 from .forecast import weights_from_errors
 
-__all__ = ["TemplateBank", "TMatchHandle", "lattice_theta", "check_match_args"]
+__all__ = ["TemplateBank", "TMatchHandle", "lattice_theta", "check_match_args", "check_npoly"]
 
 
 def lattice_theta(xmin, xmax, steps, vrad=(0.0,), vrot=(5.0,), inst_R=(np.nan,), inner=(0.0, 1.0)):
@@ -67,15 +73,26 @@ def check_match_args(flux, eflux, nobs, topk):
     return flux, w
 
 
-class TMatchHandle(object):
-    """Owner of one ``payne_tmatch`` handle (its workspace of partial lists): at most ``max_stars`` x ``max_templates`` a call."""
+def check_npoly(npoly):
+    """``match``'s npoly: 0 (the template as it is) or the 1 .. 8 Chebyshev coefficients minimised out of every pair."""
+    if isinstance(npoly, bool) or int(npoly) != npoly or not (0 <= int(npoly) <= _lib.TMATCH_MAX_POLY):
+        raise ValueError("npoly must be 0 .. %d, got %r" % (_lib.TMATCH_MAX_POLY, npoly))
+    return int(npoly)
 
-    def __init__(self, max_stars, max_templates, device):
+
+class TMatchHandle(object):
+    """Owner of one ``payne_tmatch`` handle (its workspace of partial lists): at most ``max_stars`` x ``max_templates`` a call.
+    ``max_poly`` > 0: the handle also holds ``match_poly``'s workspace for up to that many coefficients."""
+
+    def __init__(self, max_stars, max_templates, device, max_poly=0):
         import torch
         self.torch, self.lib = torch, _lib.load()
-        self.device, self.max_stars, self.max_templates = device, int(max_stars), int(max_templates)
+        self.device, self.max_stars, self.max_templates, self.max_poly = device, int(max_stars), int(max_templates), check_npoly(max_poly)
         self._h = C.c_void_p()
-        rc = self.lib.payne_tmatch_create(self.device.index, self.max_stars, self.max_templates, C.byref(self._h))
+        if self.max_poly:
+            rc = self.lib.payne_tmatch_create_poly(self.device.index, self.max_stars, self.max_templates, self.max_poly, C.byref(self._h))
+        else:
+            rc = self.lib.payne_tmatch_create(self.device.index, self.max_stars, self.max_templates, C.byref(self._h))
         if rc != 0:
             raise RuntimeError("payne_tmatch_create failed (%d): %s" % (rc, self.lib.payne_last_error(None).decode()))
 
@@ -100,6 +117,34 @@ class TMatchHandle(object):
         if rc != 0:
             raise RuntimeError("payne_tmatch_match failed (%d): %s" % (rc, self.lib.payne_last_error(None).decode()))
         return idx, chisq, every
+
+    def match_poly(self, templates, flux, w, x, npoly, topk, n=None, return_all=False):
+        """``match`` with ``npoly`` coefficients minimised out of every pair; x fp64 [n] on the device (``contfit.abscissa``) ->
+        (idx, chisq, coef fp64 [N, topk, npoly], flags int32 [N, topk], all or None)."""
+        torch = self.torch
+        if templates.dtype != torch.float32 or flux.dtype != torch.float32 or w.dtype != torch.float64 or x.dtype != torch.float64:
+            raise ValueError("templates and flux fp32, w and x fp64")
+        if templates.dim() != 2 or flux.dim() != 2 or tuple(w.shape) != tuple(flux.shape) or x.dim() != 1:
+            raise ValueError("templates [M, ld_t], flux and w [N, ld_f], x [n]; got %s, %s, %s, %s"
+                             % (tuple(templates.shape), tuple(flux.shape), tuple(w.shape), tuple(x.shape)))
+        if not (templates.is_contiguous() and flux.is_contiguous() and w.is_contiguous() and x.is_contiguous()):
+            raise ValueError("templates, flux, w and x must be contiguous")
+        M, N, P = templates.shape[0], flux.shape[0], int(npoly)
+        n = min(templates.shape[1], flux.shape[1]) if n is None else int(n)
+        if x.shape[0] < n:
+            raise ValueError("x holds %d abscissae for %d pixels" % (x.shape[0], n))
+        idx = torch.empty((N, topk), dtype=torch.int32, device=self.device)
+        chisq = torch.empty((N, topk), dtype=torch.float64, device=self.device)
+        coef = torch.empty((N, topk, max(P, 1)), dtype=torch.float64, device=self.device)
+        flags = torch.empty((N, topk), dtype=torch.int32, device=self.device)
+        every = torch.empty((N, M), dtype=torch.float64, device=self.device) if return_all else None
+        stream = C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+        rc = self.lib.payne_tmatch_match_poly(self._h, templates.data_ptr(), templates.shape[1], M, flux.data_ptr(), w.data_ptr(), flux.shape[1], N, n,
+                                              x.data_ptr(), P, int(topk), idx.data_ptr(), chisq.data_ptr(), coef.data_ptr(), flags.data_ptr(),
+                                              every.data_ptr() if return_all else None, M, stream)
+        if rc != 0:
+            raise RuntimeError("payne_tmatch_match_poly failed (%d): %s" % (rc, self.lib.payne_last_error(None).decode()))
+        return idx, chisq, coef, flags, every
 
     def close(self):
         if getattr(self, "_h", None) is not None and self._h.value:
@@ -155,11 +200,18 @@ class TemplateBank(object):
     def __len__(self):
         return 0 if self.theta is None else len(self.theta)
 
-    def match(self, flux, eflux, topk=1, return_all=False):
+    def match(self, flux, eflux, topk=1, return_all=False, npoly=0):
         """flux, eflux [N, nobs] on ``obs_wave`` (host arrays or device tensors; eflux zero or not finite, or a flux that is not
         finite: the pixel does not count) -> dict: ``index`` int32 [N, topk] (-1: no such template), ``chisq`` [N, topk] ascending
         (+inf there), ``pars`` [N, topk, 8] the bank's theta rows (NaN there), ``npix`` (pixels with w != 0) and, with
-        ``return_all``, ``all`` [N, M].  Equal chi^2 are listed in ascending template index; a NaN chi^2 is never listed."""
+        ``return_all``, ``all`` [N, M].  Equal chi^2 are listed in ascending template index; a NaN chi^2 is never listed.
+
+        ``npoly`` = P >= 1: chi^2 is minimised over a continuum polynomial of P Chebyshev coefficients per (star, template) pair
+        (``polycalc``'s basis on ``contfit.abscissa(obs_wave)``), and the dict gains ``coef`` [N, topk, P] (NaN where index is -1),
+        ``positive`` bool [N, topk] (the polynomial is > 0 at every counting pixel; a template whose polynomial turns negative stays
+        listed) and ``npoly``.  A star with fewer than P counting pixels, and a template that is zero at all of them, give NaN:
+        a star without a counting pixel lists nothing, where ``npoly=0`` lists chi^2 = 0 for it."""
+        P = check_npoly(npoly)
         if self.templates is None:
             raise RuntimeError("the bank is empty: call build(theta) or lattice(steps, ...) first")
         eng = self.predictor.anns.engine
@@ -177,19 +229,31 @@ class TemplateBank(object):
             fh, wh = check_match_args(flux, eflux, nobs, topk)
             f, w = torch.as_tensor(fh).to(dev), torch.as_tensor(wh).to(dev)
         N, M, k = f.shape[0], len(self), int(topk)
+        if self._handle is not None and P > self._handle.max_poly:
+            self.close()                                             # (the workspace grows only once a polynomial is asked for)
         if self._handle is None:
-            self._handle = TMatchHandle(self.max_stars, M, dev)
+            self._handle = TMatchHandle(self.max_stars, M, dev, max_poly=_lib.TMATCH_MAX_POLY if P else 0)
         index = np.empty((N, k), dtype=np.int32)
         chisq = np.empty((N, k))
         every = np.empty((N, M)) if return_all else None
+        if P:
+            from .contfit import abscissa
+            x = torch.as_tensor(abscissa(self.obs_wave)).to(dev)
+            coef, flags = np.empty((N, k, P)), np.empty((N, k), dtype=np.int32)
         for s in range(0, N, self.max_stars):
             e_ = min(N, s + self.max_stars)
-            i_d, c_d, a_d = self._handle.match(self.templates, f[s:e_], w[s:e_], k, n=nobs, return_all=return_all)
+            if P:
+                i_d, c_d, k_d, f_d, a_d = self._handle.match_poly(self.templates, f[s:e_], w[s:e_], x, P, k, n=nobs, return_all=return_all)
+                coef[s:e_], flags[s:e_] = k_d.cpu().numpy(), f_d.cpu().numpy()
+            else:
+                i_d, c_d, a_d = self._handle.match(self.templates, f[s:e_], w[s:e_], k, n=nobs, return_all=return_all)
             index[s:e_], chisq[s:e_] = i_d.cpu().numpy(), c_d.cpu().numpy()
             if return_all:
                 every[s:e_] = a_d.cpu().numpy()
         pars = np.where((index >= 0)[:, :, None], self.theta[np.maximum(index, 0)], np.nan)
         out = dict(index=index, chisq=chisq, pars=pars, npix=(w != 0.0).sum(dim=1).cpu().numpy())
+        if P:
+            out.update(coef=coef, positive=(flags & 1) != 0, npoly=P)
         if return_all:
             out["all"] = every
         return out

@@ -11,7 +11,13 @@ fp64 matrix rate counts 4 N M n flop (two multiply-adds a pixel and pair) agains
 time of TemplateBank.lattice (the forward pass of every template), synchronised.
 torch's form on the same tensors: (w f) @ (-2 m).T + w @ (m m).T + c0 in fp64, then torch.topk, in template blocks as large as
 half of the free memory allows (its fp64 operand copies and N x block buffers are counted and reported), block lists merged by a
-second topk.  numpy: sum w (f - m)^2 for `numpy-stars` stars against at most 4096 templates, one thread.  Prints one JSON line."""
+second topk.  numpy: sum w (f - m)^2 for `numpy-stars` stars against at most 4096 templates, one thread.  Prints one JSON line.
+
+`--npoly P` (1 .. 8) also times payne_tmatch_match_poly on the same arrays with P Chebyshev coefficients minimised out of every pair
+(the stars are the same spectra times the series 1.3, 0.25, -0.12, 0.06), beside the plain match of the same run: ms, star x
+templates / s, the share of the fp64 matrix rate over 2 n (3 P - 1) flop a pair, the ratio to the plain match and the yardstick
+(3 P - 1) / 2.  torch's route on the same card: the 3 P - 1 products as two fp64 matmuls in template blocks that fit half of the free
+memory, A from S by a gather, linalg.cholesky_ex, cholesky_solve, the quadratic form and topk (`--torch-repeats` calls)."""
 import argparse
 import json
 import os
@@ -61,6 +67,43 @@ def torch_form(torch, templates, f, w, topk, budget):
     return best_i, best_c, block * per_template + 2 * N * n * 8, block
 
 
+def torch_poly_form(torch, templates, f, w, x, P, topk, budget):
+    """(idx, chisq, template block): the search with the polynomial minimised out on torch's fp64 matmul, cholesky_ex and topk."""
+    N, n = f.shape
+    M, Q = templates.shape[0], 2 * P - 1
+    T = [torch.ones_like(x), x]
+    for q in range(2, Q):
+        T.append(2.0 * x * T[-1] - T[-2])
+    T = torch.stack(T[:Q])                                           # [2 P - 1, n]
+    a1 = w * f.double()
+    c0 = (a1 * f.double()).sum(dim=1, keepdim=True)
+    star_b = (a1[:, None, :] * T[None, :P]).reshape(N * P, n)
+    star_s = (w[:, None, :] * T[None]).reshape(N * Q, n)
+    jj, kk = torch.meshgrid(torch.arange(P, device=x.device), torch.arange(P, device=x.device), indexing="ij")
+    per_template = 2 * n * 8 + N * 8 * (2 * (3 * P - 1) + 4 * P * P + 4 * P + 4)
+    block = int(max(1, min(M, budget // per_template)))
+    best_c, best_i = None, None
+    for s in range(0, M, block):
+        m = templates[s:s + block].double()
+        nb = m.shape[0]
+        b = (star_b @ m.T).reshape(N, P, nb).permute(0, 2, 1)
+        S = (star_s @ (m * m).T).reshape(N, Q, nb).permute(0, 2, 1)
+        A = 0.5 * (S[:, :, jj + kk] + S[:, :, (jj - kk).abs()])
+        L, info = torch.linalg.cholesky_ex(A)
+        c = torch.cholesky_solve(b[..., None], L)[..., 0]
+        chi = c0 + (c * ((A @ c[..., None])[..., 0] - 2.0 * b)).sum(dim=-1)
+        chi = torch.where((info == 0) & torch.isfinite(chi), chi, torch.full_like(chi, float("inf")))
+        cc, i = torch.topk(chi, min(topk, nb), dim=1, largest=False)
+        i = i + s
+        if best_c is None:
+            best_c, best_i = cc, i
+        else:
+            cc, ii = torch.cat([best_c, cc], dim=1), torch.cat([best_i, i], dim=1)
+            best_c, pick = torch.topk(cc, topk, dim=1, largest=False)
+            best_i = torch.gather(ii, 1, pick)
+    return best_i, best_c, block
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--stars", type=int, default=4096)
@@ -71,6 +114,8 @@ def main():
     ap.add_argument("--warmup", type=int, default=1)
     ap.add_argument("--numpy-stars", type=int, default=8)
     ap.add_argument("--b-max", type=int, default=512)
+    ap.add_argument("--npoly", type=int, default=0)
+    ap.add_argument("--torch-repeats", type=int, default=2)
     args = ap.parse_args()
     import torch
     from optfit_bench import workload
@@ -88,7 +133,11 @@ def main():
     f_d = torch.as_tensor(flux).to(dev)
     w_d = torch.full(flux.shape, 1e4, dtype=torch.float64, device=dev)
     N, n = flux.shape
-    out = {"stars": N, "nobs": n, "topk": args.topk, "repeats": args.repeats, "warmup": args.warmup, "fp64_matrix_peak": FP64_MATRIX_PEAK, "runs": []}
+    if args.npoly:
+        from thepayne_amd.fitting.contfit import abscissa
+        x_d = torch.as_tensor(abscissa(obs_wave)).to(dev)
+        fp_d = (f_d.double() * (1.3 + 0.25 * x_d - 0.12 * (2.0 * x_d * x_d - 1.0) + 0.06 * (4.0 * x_d ** 3 - 3.0 * x_d))).float()
+    out = {"stars": N, "nobs": n, "topk": args.topk, "npoly": args.npoly, "repeats": args.repeats, "warmup": args.warmup, "fp64_matrix_peak": FP64_MATRIX_PEAK, "runs": []}
     for M in [int(v) for v in args.templates.split(",")]:
         steps = int(round((M / 16.0) ** 0.25))
         bank = TemplateBank(net, "SMLP", obs_wave, b_max=args.b_max, max_stars=N)
@@ -98,7 +147,7 @@ def main():
         torch.cuda.synchronize()
         build_s = time.perf_counter() - t0
         M = len(bank)
-        h = TMatchHandle(N, M, dev)
+        h = TMatchHandle(N, M, dev, max_poly=args.npoly)
         ms, ms_min, (idx, chisq, _) = timed(torch, lambda: h.match(bank.templates, f_d, w_d, args.topk, n=n), args.repeats, args.warmup)
         flop = 4.0 * N * M * n
         run = {"templates": M, "lattice_steps": steps, "build_s": build_s, "template_values_not_finite": int((~torch.isfinite(bank.templates)).sum().item()), "match_ms_median": ms, "match_ms_min": ms_min,
@@ -118,6 +167,21 @@ def main():
                 (ww[None, :] * d * d).sum(axis=1)
             sec = time.perf_counter() - t0
             run.update(numpy_star_templates_per_s=args.numpy_stars * len(tm) / sec, kernel_over_numpy=(N * M / (ms * 1e-3)) / (args.numpy_stars * len(tm) / sec))
+        if args.npoly:
+            Pn = args.npoly
+            p_ms, p_min, (p_idx, p_chisq, p_coef, p_flags, _) = timed(torch, lambda: h.match_poly(bank.templates, fp_d, w_d, x_d, Pn, args.topk, n=n),
+                                                                       args.repeats, args.warmup)
+            p_flop = 2.0 * n * (3 * Pn - 1) * N * M
+            run.update(poly_ms_median=p_ms, poly_ms_min=p_min, poly_star_templates_per_s=N * M / (p_ms * 1e-3),
+                       poly_fraction_of_fp64_matrix_peak=p_flop / (p_ms * 1e-3) / FP64_MATRIX_PEAK, poly_over_plain_time=p_ms / ms,
+                       yardstick_ratio=(3 * Pn - 1) / 2.0, poly_positive_top1=float((p_flags[:, 0] & 1).double().mean().item()),
+                       poly_top1_is_plain_top1_on_the_clean_stars=float((p_idx[:, 0] == idx[:, 0]).double().mean().item()))
+            free, _total = torch.cuda.mem_get_info(dev)
+            tp_ms, tp_min, (tp_idx, tp_c, tp_block) = timed(torch, lambda: torch_poly_form(torch, bank.templates, fp_d, w_d, x_d, Pn, args.topk, free // 2),
+                                                            args.torch_repeats, 1)
+            run.update(torch_poly_ms_median=tp_ms, torch_poly_ms_min=tp_min, torch_poly_template_block=int(tp_block), torch_poly_over_kernel_time=tp_ms / p_ms,
+                       poly_top1_agree_with_torch=float((tp_idx[:, 0] == p_idx[:, 0].long()).double().mean().item()),
+                       poly_max_abs_dchisq_top1=float((tp_c[:, 0] - p_chisq[:, 0]).abs().max().item()))
         out["runs"].append(run)
         h.close()
         bank.close()
