@@ -555,6 +555,19 @@ int payne_fisher_batch(int device, const float* rows_dev, int ld, int K, int n, 
  *                        prior_sigma_dev; the box (payne_lmfit_begin's) of the parameter mapped to column ncol - 1, Av, with hi >= 5
  *                        (the model jumps there)
  *   PAYNE_E_UNSUPPORTED  F > 64 (a star's filters are staged in LDS)
+ * payne_lmfit_update_pair: the update for a spectrum of two components A and B with a light ratio q, times a continuum polynomial:
+ * model = p(x) [(1 - q) m_A + q m_B].  The handle's K parameters are, in this order, Kl that the components see, q, and P >= 0
+ * Chebyshev coefficients (P == 0: p == 1, x_dev is not read and may be NULL), K = Kl + 1 + P.  rows_a_dev is DEVICE fp32
+ * [B][1 + Ka][ld] and rows_b_dev [B][1 + Kb][ld]: row 0 a component's model at the star's x_trial, row 1 + k its k-th derivative.
+ * ia, ib HOST int [Kl]: parameter k is derivative ia[k] of A's block and ib[k] of B's, -1 where the component does not see it; both
+ * >= 0 for a parameter the two share.  q and the coefficients are read from the star's x_trial.  The K + 1 rows of R are formed in
+ * registers and never stored (csrc/lmfit_pair_core.hpp states every product and fma): p [(1 - q) dm_A[ia] + q dm_B[ib]] (i < Kl),
+ * p (m_B - m_A) (i = Kl), [(1 - q) m_A + q m_B] T_j(x) (i = Kl + 1 + j) and flux - p [(1 - q) m_A + q m_B] (i = K), 1 - q rounded once
+ * a star.  Pixel order, operand map, the handling of w == 0, NaN and pixels beyond n, both load forms (both row blocks and x_dev
+ * 16-byte aligned for the first) and the step that follows are payne_lmfit_update's; a star's bits do not depend on its batch.
+ *   PAYNE_E_INVALID      as payne_lmfit_update (either row block); Kl < 0, P < 0, Kl + 1 + P != K, Ka < 0, Kb < 0; null ia / ib with
+ *                        Kl > 0, an entry outside [-1, Ka) / [-1, Kb), both -1 for one parameter; null x_dev with P > 0 and B > 0
+ * A call that is refused leaves the state untouched.
  * payne_lmfit_result: DEVICE pointers, any may be NULL: x_best fp64 [B][K], chisq fp64 [B] (of x_best), A fp64 [B][K][K] and g fp64
  * [B][K] (at x_best), lambda fp64 [B], status int [B], niter int [B] (evaluations), at_bound unsigned [B].  Copies on `stream`.
  *   PAYNE_E_INVALID      null handle
@@ -585,6 +598,9 @@ int payne_lmfit_update_phot(payne_lmfit* h, int Km, int Kp, int P, const float* 
                             const double* w_dev, int ld_f, const double* x_dev, int n, int F, int ncol, const int* sed_col,
                             const double* mags_dev, const double* dmags_dev, const double* obs_dev, const double* pw_dev,
                             const double* prior_mu_dev, const double* prior_sigma_dev, void* stream);
+int payne_lmfit_update_pair(payne_lmfit* h, int Kl, int P, const int* ia, const int* ib, const float* rows_a_dev, int Ka,
+                            const float* rows_b_dev, int Kb, int ld, const float* flux_dev, const double* w_dev, int ld_f,
+                            const double* x_dev, int n, void* stream);
 int payne_lmfit_result(payne_lmfit* h, double* x_best, double* chisq, double* A, double* g, double* lambda, int* status, int* niter,
                        unsigned* at_bound, void* stream);
 void payne_lmfit_destroy(payne_lmfit* h);

@@ -41,7 +41,7 @@ SYMBOLS = ["payne_version", "payne_ctx_create", "payne_ctx_set_obs", "payne_ctx_
            "payne_specmlp_train_create", "payne_specmlp_train_step", "payne_specmlp_train_loss", "payne_specmlp_train_predict",
            "payne_specmlp_train_set_lr", "payne_specmlp_train_get", "payne_specmlp_train_steps", "payne_specmlp_train_destroy",
            "payne_specjac_create", "payne_specjac_eval", "payne_specjac_destroy", "payne_fisher_batch",
-           "payne_lmfit_create", "payne_lmfit_begin", "payne_lmfit_trial", "payne_lmfit_update", "payne_lmfit_update_poly", "payne_lmfit_update_phot", "payne_lmfit_result",
+           "payne_lmfit_create", "payne_lmfit_begin", "payne_lmfit_trial", "payne_lmfit_update", "payne_lmfit_update_poly", "payne_lmfit_update_phot", "payne_lmfit_update_pair", "payne_lmfit_result",
            "payne_lmfit_destroy",
            "payne_tmatch_create", "payne_tmatch_match", "payne_tmatch_chunk", "payne_tmatch_destroy",
            "payne_tmatch_create_poly", "payne_tmatch_match_poly", "payne_tmatch_poly_stars", "payne_tmatch_poly_chunk",
@@ -290,6 +290,9 @@ def load(path=None):
     lib.payne_lmfit_update_phot.argtypes = [ctxp, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int,
                                             C.c_int, C.c_int, C.c_void_p] + [C.c_void_p] * 7
     lib.payne_lmfit_update_phot.restype = C.c_int
+    lib.payne_lmfit_update_pair.argtypes = [ctxp, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p,
+                                            C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p]
+    lib.payne_lmfit_update_pair.restype = C.c_int
     lib.payne_lmfit_result.argtypes = [ctxp] + [C.c_void_p] * 9
     lib.payne_lmfit_result.restype = C.c_int
     lib.payne_lmfit_destroy.argtypes = [ctxp]

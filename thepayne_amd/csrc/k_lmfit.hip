@@ -19,6 +19,11 @@
 //     residual) before the pixel loop and keeps them in registers; behind sum_waves they go to LDS (the space of `part`), thread
 //     (i, j) sums element (i, j) of the photometric block over the filters in ascending order (lmfit_phot_core.hpp: phot_element),
 //     and thread 0 adds the priors and the block to the tile (add_block) before it takes the step.
+//   payne_lmfit_update_pair_kernel  payne_lmfit_update_pair: two components with a light ratio q times a Chebyshev series, K = Kl + 1 + P
+//     (lmfit_pair_core.hpp).  A body of its own (update_pair_body), so that the kernels above keep their code: the same tile, loop and
+//     step.  Every lane reads one row of A's block and one of B's (row 0, the model, where it has no derivative; nothing where the map
+//     says -1), mixes them with (1 - q, q), or (-1, 1) in the ratio's row, and multiplies by its series; q and the coefficients come
+//     from x_trial through LDS.  It streams (2 + Ka + Kb) n fp32 + n fp32 + n fp64 per star once; nothing of R is stored.
 //   payne_lmfit_begin_kernel   one thread a star: x_trial = clip(x0), the state reset.
 //   No atomics; every sum has a fixed order.
 #include <hip/hip_runtime.h>
@@ -28,6 +33,7 @@
 #include "../../include/payne_hip.h"
 #include "host_prologue.hpp"
 #include "lmfit_core.hpp"
+#include "lmfit_pair_core.hpp"
 #include "lmfit_phot_core.hpp"
 
 namespace lm = payne::lmfit;
@@ -152,6 +158,64 @@ __global__ void __launch_bounds__(nt::kThreads) payne_lmfit_update_phot_kernel(c
   update_body<VEC, POLY, true>(rows, ld, flux, w, ld_f, x, n, K, P, st, box, opts, ph);
 }
 
+// One star's update for two components: rows_a [B][1 + Ka][ld], rows_b [B][1 + Kb][ld]; x is read with P > 0 only.
+template <bool VEC>
+__device__ __forceinline__ void update_pair_body(const float* __restrict__ rows_a, int Ka, const float* __restrict__ rows_b, int Kb, long long ld,
+                                                 const float* __restrict__ flux, const double* __restrict__ w, long long ld_f,
+                                                 const double* __restrict__ x, int n, int K, int Kl, int P, const lm::State& st, const lm::Box& box,
+                                                 const payne_lmfit_opts& opts, const lm::PairMap& map) {
+  __shared__ double part[nt::kWaves][nt::kTileSize];
+  __shared__ double tile[nt::kTileSize];
+  __shared__ double work[lm::kWorkDoubles];
+  __shared__ double qc[1 + lm::kMaxK];                              // the star's q, then its coefficients
+  const size_t b = blockIdx.x;
+  if (st.status[b] != PAYNE_LMFIT_RUNNING) return;                  // (the whole workgroup)
+  const int tid = threadIdx.x, i = tid & 15;
+  if (tid <= P) qc[tid] = st.x_trial[b * (size_t)K + (size_t)(Kl + tid)];
+  __syncthreads();
+  const double q = qc[0], omq = 1.0 - q;
+  const double* coef = qc + 1;
+  const bool live = i <= K, residual = i == K;
+  const int j = lm::pair_series_index(i, Kl, K);
+  const int ia = i < Kl ? map.ia[i] : 0, ib = i < Kl ? map.ib[i] : 0;
+  const bool has_a = live && ia >= 0, has_b = live && ib >= 0;
+  const float* ra = rows_a + (b * (size_t)(1 + Ka) + (size_t)(i < Kl && ia >= 0 ? 1 + ia : 0)) * (size_t)ld;
+  const float* rb = rows_b + (b * (size_t)(1 + Kb) + (size_t)(i < Kl && ib >= 0 ? 1 + ib : 0)) * (size_t)ld;
+  double ca, cb;
+  lm::pair_weights(i, Kl, omq, q, &ca, &cb);
+  const float* fb = flux + b * (size_t)ld_f;
+  const double* wb = w + b * (size_t)ld_f;
+  const nt::d4 acc = nt::wave_sums(n, [&](int p) PAYNE_TILE_CALLABLE {
+    float a[4] = {0.0f, 0.0f, 0.0f, 0.0f}, c[4] = {0.0f, 0.0f, 0.0f, 0.0f}, f[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+    double wv[4] = {0.0, 0.0, 0.0, 0.0}, xv[4] = {0.0, 0.0, 0.0, 0.0}, sv[4] = {1.0, 1.0, 1.0, 1.0};
+    if (P > 0) nt::load4<VEC>(x, p, n, p + 3 < n, xv);              // (x holds n values and no more)
+    if (p < n) {                                                    // p + 3 < ld and ld_f where VEC: both are multiples of four
+      nt::load4<VEC>(wb, p, n, true, wv);
+      if (has_a) nt::load4<VEC>(ra, p, n, true, a);
+      if (has_b) nt::load4<VEC>(rb, p, n, true, c);
+      if (residual) nt::load4<VEC>(fb, p, n, true, f);
+    }
+    if (P > 0) chebs::series4(coef, j, P, xv, sv);
+    return [=](int t, double* r, double* wt) PAYNE_TILE_CALLABLE {
+      *r = lm::operand_pair_mix(i, K, ca, cb, a[t], c[t], f[t], sv[t]);
+      *wt = wv[t];
+      return live && p + t < n && wv[t] != 0.0;
+    };
+  });
+  nt::sum_waves(acc, part, tile, []() PAYNE_TILE_CALLABLE { __syncthreads(); });
+  if (tid == 0) lm::update_star(st, b, K, tile, opts, box, work);
+}
+
+template <bool VEC>
+__global__ void __launch_bounds__(nt::kThreads) payne_lmfit_update_pair_kernel(const float* __restrict__ rows_a, int Ka,
+                                                                               const float* __restrict__ rows_b, int Kb, long long ld,
+                                                                               const float* __restrict__ flux, const double* __restrict__ w,
+                                                                               long long ld_f, const double* __restrict__ x, int n, int K, int Kl,
+                                                                               int P, const lm::State st, const lm::Box box,
+                                                                               const payne_lmfit_opts opts, const lm::PairMap map) {
+  update_pair_body<VEC>(rows_a, Ka, rows_b, Kb, ld, flux, w, ld_f, x, n, K, Kl, P, st, box, opts, map);
+}
+
 template <class T>
 bool alloc(payne_lmfit* h, T** p, size_t count) {
   void* v = nullptr;
@@ -266,6 +330,24 @@ extern "C" int payne_lmfit_update_phot(payne_lmfit* h, int Km, int Kp, int P, co
   ph.map.Kp = Kp;
   for (int k = 0; k < lm::kMaxK; ++k) ph.map.sed_col[k] = k < h->K ? sed_col[k] : -1;
   return launch_update(h, P, rows_dev, ld, flux_dev, w_dev, ld_f, P > 0 ? x_dev : nullptr, n, stream, &ph);
+}
+
+extern "C" int payne_lmfit_update_pair(payne_lmfit* h, int Kl, int P, const int* ia, const int* ib, const float* rows_a_dev, int Ka,
+                                       const float* rows_b_dev, int Kb, int ld, const float* flux_dev, const double* w_dev, int ld_f,
+                                       const double* x_dev, int n, void* stream) {
+  if (!h || n < 1 || ld < n || ld_f < n) return PAYNE_E_INVALID;
+  const int rc = lm::check_pair(h->K, Kl, P, Ka, Kb, ia, ib);
+  if (rc != PAYNE_OK) return rc;
+  if (h->B == 0) return PAYNE_OK;
+  if (!rows_a_dev || !rows_b_dev || !flux_dev || !w_dev || (P > 0 && !x_dev)) return PAYNE_E_INVALID;
+  OnDevice on(h->device);
+  if (!on.ok()) return PAYNE_E_HIP;
+  const double* x = P > 0 ? x_dev : nullptr;
+  const bool vec = ld % 4 == 0 && ld_f % 4 == 0 && aligned16(rows_a_dev) && aligned16(rows_b_dev) && aligned16(flux_dev) && aligned16(w_dev) && aligned16(x);
+  const auto kernel = vec ? payne_lmfit_update_pair_kernel<true> : payne_lmfit_update_pair_kernel<false>;
+  hipLaunchKernelGGL(kernel, dim3((unsigned)h->B), dim3(nt::kThreads), 0, reinterpret_cast<hipStream_t>(stream), rows_a_dev, Ka, rows_b_dev, Kb,
+                     (long long)ld, flux_dev, w_dev, (long long)ld_f, x, n, h->K, Kl, P, h->st, h->box, h->opts, lm::pair_map(Kl, ia, ib));
+  return hipGetLastError() == hipSuccess ? PAYNE_OK : PAYNE_E_HIP;
 }
 
 extern "C" int payne_lmfit_result(payne_lmfit* h, double* x_best, double* chisq, double* A, double* g, double* lambda, int* status,

@@ -29,6 +29,10 @@ errors that come back are marginal over all fitted parameters.  The spectral mod
 off the spectrum's own minimum, its rounding reaches chi^2 at a few 1e-6, which is more than a step of xtol = 1e-3 sigma gains, and a
 star may end ``STALLED`` (or ``CONVERGED`` after a dozen rejected trials) AT the solution; ``fit_specphot``'s docstring says what to
 make of that.
+
+``OptFit.fit_binary`` fits a double-lined binary: two components, each with its own labels and Vrad (some labels tied), a light ratio
+q and the polynomial in one fit of chi^2 = sum w (flux - p [(1 - q) m_A + q m_B])^2.  Its update, payne_lmfit_update_pair, reads both
+components' rows and mixes them in registers (csrc/lmfit_pair_core.hpp).
 """
 import collections
 import ctypes as C
@@ -40,7 +44,7 @@ from ..engine import THETA_SPEC_COLS
 from ..predict._spec import PayneSpecPredict, smooth_rows
 from .forecast import crlb_from_fisher, weights_from_errors
 
-__all__ = ["OptFit", "check_fit_args", "check_joint_args", "check_specphot_args", "LM_DEFAULTS", "VRAD_BOUND", "COEF_BOUND"]
+__all__ = ["OptFit", "check_fit_args", "check_joint_args", "check_specphot_args", "check_binary_args", "LM_DEFAULTS", "VRAD_BOUND", "COEF_BOUND"]
 
 LM_DEFAULTS = dict(lambda0=1e-3, down=10.0, up=10.0, lambda_min=1e-12, lambda_max=1e8, xtol=1e-3, maxiter=50)
 VRAD_BOUND = 500.0                                   # km/s: the default box of a fitted Vrad
@@ -222,6 +226,72 @@ def check_specphot_args(flux, eflux, mags, emags, start, phot_start, nobs, n_lab
                 lo=lo, hi=hi, Km=Km, Kp=Kp, P=P, cols=cols, phot_cols=phot_cols, sed_col=sed_col, mu=mu, sigma=sigma)
 
 
+TIE_ALIASES = {"teff": "Teff", "logg": "log(g)", "feh": "[Fe/H]", "afe": "[a/Fe]", "vmic": "Vmic"}
+
+
+def check_binary_args(flux, eflux, start_a, start_b, nobs, n_labels, xmin, xmax, ratio=0.3, tie=(), fit_vrad=True, npoly=0, coef=None, bounds=None,
+                      ratio_bounds=(0.01, 0.99), vrad_step=0.25, check_every=4, **opts):
+    """What ``OptFit.fit_binary`` checks before anything reaches the device; no GPU.  The K = K_l + 1 + npoly parameters are A's fitted
+    columns (the labels, then Vrad), B's that are not tied, the ratio, the coefficients.  ``tie``: names of network labels
+    (``THETA_SPEC_COLS``'s, or teff / logg / feh / afe / vmic) that both components share.  ``bounds``: {name of ``labels``: (lo, hi)}.
+    Returns a dict: flux, eflux, start_a, start_b, ratio [N], coef (or None), opts; cols (a component's fitted columns of getspec's
+    eight); Ka; Kl; P; ia, ib int32 [Kl]; b_pos [Ka] (where B's fitted column k sits among the parameters); names, lo, hi [K]."""
+    flux, eflux, start_a, lo_c, hi_c, o = check_fit_args(flux, eflux, start_a, nobs, n_labels, xmin, xmax, fit_vrad=fit_vrad, vrad_step=vrad_step,
+                                                         check_every=check_every, **opts)
+    start_b = check_fit_args(flux, eflux, start_b, nobs, n_labels, xmin, xmax, fit_vrad=fit_vrad)[2]
+    N = flux.shape[0]
+    cols = fitted_columns(n_labels, fit_vrad)
+    cnames = [THETA_SPEC_COLS[c] for c in cols]
+    Ka, D = len(cols), n_labels
+    tie = [tie] if isinstance(tie, str) else list(tie)
+    tied = []
+    for t in tie:
+        name = TIE_ALIASES.get(t, t)
+        if name not in cnames[:D]:
+            raise ValueError("tie: %r is not a label of the network (%s)" % (t, ", ".join(cnames[:D])))
+        tied.append(cnames.index(name))
+    if len(set(tied)) != len(tied):
+        raise ValueError("tie names a label twice: %r" % (tie,))
+    if isinstance(npoly, bool) or int(npoly) != npoly or int(npoly) < 0:
+        raise ValueError("npoly must be an integer >= 0, got %r" % (npoly,))
+    P = int(npoly)
+    free_b = [k for k in range(Ka) if k not in tied]
+    Kl = Ka + len(free_b)
+    K = Kl + 1 + P
+    if K > _lib.LMFIT_MAX_K:
+        raise ValueError("%d parameters of the two components, the ratio and npoly = %d are %d parameters; at most %d (one 16 x 16 tile holds a "
+                         "star's normal equations): tie labels or lower npoly" % (Kl, P, K, _lib.LMFIT_MAX_K))
+    rb = np.asarray(ratio_bounds, dtype=np.float64)
+    if rb.shape != (2,) or not (0.0 < rb[0] < rb[1] < 1.0):
+        raise ValueError("ratio_bounds must be (lo, hi) with 0 < lo < hi < 1 (at q = 0 or 1 one component's rows vanish), got %r" % (ratio_bounds,))
+    ratio = np.array(np.broadcast_to(np.asarray(ratio, dtype=np.float64), (N,)))   # (a copy: broadcast_to's view is read-only)
+    if not np.all((ratio >= rb[0]) & (ratio <= rb[1])):
+        raise ValueError("ratio must lie inside ratio_bounds = (%g, %g)" % (rb[0], rb[1]))
+    if coef is not None:
+        if P == 0:
+            raise ValueError("coef belongs to the polynomial; npoly is 0")
+        coef = np.atleast_2d(np.asarray(coef.cpu() if hasattr(coef, "cpu") else coef, dtype=np.float64))
+        if coef.shape != (N, P) or not np.all(np.isfinite(coef)):
+            raise ValueError("coef must be [%d, %d] and finite, got %s" % (N, P, coef.shape))
+    ia = np.array(list(range(Ka)) + [-1] * len(free_b), dtype=np.int32)
+    ib = np.array([k if k in tied else -1 for k in range(Ka)] + free_b, dtype=np.int32)
+    b_pos = np.array([k if k in tied else Ka + free_b.index(k) for k in range(Ka)], dtype=np.int64)
+    names = [c + "_a" for c in cnames] + [cnames[k] + "_b" for k in free_b] + ["ratio"] + ["pc_%d" % j for j in range(P)]
+    lo = np.concatenate([lo_c, lo_c[free_b], [rb[0]], np.full(P, -COEF_BOUND)])
+    hi = np.concatenate([hi_c, hi_c[free_b], [rb[1]], np.full(P, COEF_BOUND)])
+    if bounds is not None:
+        if not isinstance(bounds, dict):
+            raise ValueError("bounds must be a dict {name: (lo, hi)} over %s" % (names,))
+        for name, (a, b) in bounds.items():
+            if name not in names or name == "ratio":
+                raise ValueError("bounds: %r is not one of %s (the ratio's box is ratio_bounds)" % (name, ", ".join(n for n in names if n != "ratio")))
+            lo[names.index(name)], hi[names.index(name)] = float(a), float(b)
+    if not (np.all(np.isfinite(lo)) and np.all(np.isfinite(hi)) and np.all(lo < hi)):
+        raise ValueError("bounds: lo < hi, both finite, for every fitted parameter")
+    return dict(flux=flux, eflux=eflux, start_a=start_a, start_b=start_b, ratio=ratio, coef=coef, opts=o, cols=cols, Ka=Ka, Kl=Kl, P=P, ia=ia, ib=ib,
+                b_pos=b_pos, names=names, lo=lo, hi=hi)
+
+
 PhotBlock = collections.namedtuple("PhotBlock", "sed pars x0 phot_idx sed_col obs pw mu sigma")
 PhotBlock.__doc__ = """The photometric inputs of one block of stars in ``OptFit._fit_block``:
     sed       the ``SEDFit``
@@ -336,6 +406,32 @@ class LMHandle(object):
                                               None if mu is None else mu.data_ptr(), None if sigma is None else sigma.data_ptr(), self._stream())
         if rc != 0:
             raise RuntimeError("payne_lmfit_update_phot failed (%d): %s" % (rc, self.lib.payne_last_error(None).decode()))
+
+    def update_pair(self, rows_a, rows_b, flux, w, ia, ib, P=0, x=None):
+        """The update for two components with a light ratio times a polynomial (payne_lmfit_update_pair): the handle's parameters are
+        Kl = K - 1 - P that the components see, the ratio q and P >= 0 Chebyshev coefficients.  rows_a fp32 [B, 1 + Ka, n] and rows_b
+        fp32 [B, 1 + Kb, n] (a component's model, then its derivatives), flux fp32 [B, n], w fp64 [B, n], x fp64 [n] (None for
+        P = 0): device tensors; ia, ib [Kl] host ints: parameter k is derivative ia[k] of A and ib[k] of B, -1 for none."""
+        torch = self.torch
+        B, n, P, K = self.B, rows_a.shape[-1], int(P), self.K
+        Kl = K - 1 - P
+        ia, ib = np.ascontiguousarray(ia, dtype=np.int32), np.ascontiguousarray(ib, dtype=np.int32)
+        if P < 0 or Kl < 0 or ia.shape != (Kl,) or ib.shape != (Kl,):
+            raise ValueError("P >= 0, 1 + P <= %d and ia, ib [%d]; got P = %d, ia %s, ib %s" % (K, max(Kl, 0), P, ia.shape, ib.shape))
+        if rows_a.dim() != 3 or rows_b.dim() != 3 or rows_a.shape[0] != B or rows_b.shape[0] != B or rows_b.shape[2] != n \
+                or tuple(flux.shape) != (B, n) or tuple(w.shape) != (B, n) or (P > 0 and (x is None or tuple(x.shape) != (n,))):
+            raise ValueError("rows_a [%d, 1 + Ka, n], rows_b [%d, 1 + Kb, n], flux and w [%d, n], x [n]; got %s, %s, %s, %s, %s"
+                             % (B, B, B, tuple(rows_a.shape), tuple(rows_b.shape), tuple(flux.shape), tuple(w.shape), None if x is None else tuple(x.shape)))
+        Ka, Kb = rows_a.shape[1] - 1, rows_b.shape[1] - 1
+        if Ka < 0 or Kb < 0 or np.any(ia < -1) or np.any(ia >= Ka) or np.any(ib < -1) or np.any(ib >= Kb) or np.any((ia < 0) & (ib < 0)):
+            raise ValueError("ia in [-1, %d), ib in [-1, %d), not both -1; got %s, %s" % (Ka, Kb, ia.tolist(), ib.tolist()))
+        f32, f64 = [rows_a, rows_b, flux], [w] + ([x] if P > 0 else [])
+        if any(a.dtype != torch.float32 or not a.is_contiguous() for a in f32) or any(a.dtype != torch.float64 or not a.is_contiguous() for a in f64):
+            raise ValueError("rows_a, rows_b and flux contiguous fp32, w and x contiguous fp64")
+        rc = self.lib.payne_lmfit_update_pair(self._h, Kl, P, ia.ctypes.data if Kl else None, ib.ctypes.data if Kl else None, rows_a.data_ptr(), Ka,
+                                              rows_b.data_ptr(), Kb, n, flux.data_ptr(), w.data_ptr(), n, x.data_ptr() if P > 0 else None, n, self._stream())
+        if rc != 0:
+            raise RuntimeError("payne_lmfit_update_pair failed (%d)" % rc)
 
     def status(self):
         torch = self.torch
@@ -776,6 +872,148 @@ class OptFit(object):
                 out[name][dst] = res[name][take]
             out["start_index"][dst], out["start_chisq"][dst], out["start_rank"][dst] = m["index"][dst, r], m["chisq"][dst, r], r
         return out
+
+    def fit_binary(self, flux, eflux, start_a, start_b, ratio=0.3, tie=(), fit_vrad=True, npoly=0, coef=None, bounds=None, ratio_bounds=(0.01, 0.99),
+                   vrad_step=0.25, check_every=4, timing=False, **opts):
+        """A double-lined binary: two emulated spectra fitted to one observation in ONE Levenberg-Marquardt fit of
+        chi^2 = sum w (flux - p(x) [(1 - q) m_A + q m_B])^2.  m_A and m_B are ``fit``'s model, each at its own labels, Vrad, Vrot and
+        Inst_R (``start_a``, ``start_b`` [N, 8], getspec's columns; Vrot and Inst_R stay fixed there); q is the light ratio, started at
+        ``ratio`` (a number or [N]) inside ``ratio_bounds``; p is ``fit_joint``'s Chebyshev series of ``npoly`` coefficients (0: p = 1),
+        started from ``coef`` [N, npoly] or from one ``ContinuumFit.fit`` against the mixed model at the start.  ``tie``: labels the two
+        components share (``('feh', 'afe')``: a binary has one composition) -- one parameter that both see.  The parameters, in this
+        order: A's labels and Vrad, B's that are not tied, q, the coefficients; K <= 15.  ``bounds``: {name of ``labels``: (lo, hi)}.
+
+        An iteration is four enqueued steps and no host look: payne_specjac_eval at both components' trial labels (a tied label is
+        gathered from A's on the device), the broadening of both row sets (Vrad rows by central difference, as ``fit``'s), and
+        payne_lmfit_update_pair, which mixes the two components' rows in registers.
+
+        Returns a dict: ``pars_a``, ``pars_b`` [N, 8], ``ratio`` [N], ``coef`` [N, npoly], ``chisq``, ``npix``, ``fisher`` [N, K, K],
+        ``err`` [N, K] = sqrt(diag(inv(fisher))) -- every error is marginalised over the other component, q and the polynomial --
+        ``status``, ``niter``, ``at_bound`` and ``labels`` (Teff_a .. Vrad_a, Teff_b .., ratio, pc_0 ..; a tied label once, under its A
+        name).  A star whose first chi^2 is not finite, or whose starting continuum fit fails, has status NAN and NaN results.
+
+        What to keep in mind.  Swapping A and B with q -> 1 - q is the same model: which component comes out as A is decided by the
+        start.  A ratio that is constant in wavelength is an approximation for a narrow range.  The evidence for a binary is ``chisq``
+        against ``fit_joint``'s (or ``fit``'s) on the same pixels, not anything this fit reports by itself.  The starting points are the
+        caller's (a search for pairs of templates is not part of this method); two components started at the same labels and Vrad
+        have identical rows, which ends ``SINGULAR``."""
+        Pr = self.predictor
+        anns, eng, D = Pr.anns, Pr.anns.engine, self.n_labels
+        a = check_binary_args(flux, eflux, start_a, start_b, len(self.obs_wave), D, anns.xmin, anns.xmax, ratio=ratio, tie=tie, fit_vrad=fit_vrad, npoly=npoly,
+                              coef=coef, bounds=bounds, ratio_bounds=ratio_bounds, vrad_step=vrad_step, check_every=check_every, **opts)
+        from .contfit import ContinuumFit, abscissa
+        torch = eng.torch
+        flux, eflux, start_a, start_b, q0, coef, o = a["flux"], a["eflux"], a["start_a"], a["start_b"], a["ratio"], a["coef"], a["opts"]
+        cols, Ka, Kl, P, b_pos = a["cols"], a["Ka"], a["Kl"], a["P"], a["b_pos"]
+        K = Kl + 1 + P
+        N = flux.shape[0]
+        start_b = start_b.copy()
+        tied = [k for k in range(Ka) if b_pos[k] < Ka]
+        free_b = [k for k in range(Ka) if b_pos[k] >= Ka]
+        start_b[:, [cols[k] for k in tied]] = start_a[:, [cols[k] for k in tied]]
+        w = weights_from_errors(eflux)
+        good = np.ones(N, dtype=bool)
+        x = abscissa(self.obs_wave) if P else None
+        if P and coef is None:
+            q_d = torch.as_tensor(q0).to(eng.device)[:, None]
+            mixed = ((1.0 - q_d) * self.model_spectra(start_a) + q_d * self.model_spectra(start_b)).to(torch.float32).contiguous()
+            c = ContinuumFit(self.obs_wave, npoly=P, device=eng.device).fit(flux, eflux, mixed, normalise=False)
+            coef, cs = c["coef"].cpu().numpy(), c["status"].cpu().numpy()
+            good = (cs == _lib.CONTFIT_OK) | (cs == _lib.CONTFIT_NONPOSITIVE)
+        out = dict(pars_a=start_a.copy(), pars_b=start_b.copy(), ratio=np.full(N, np.nan), coef=np.full((N, P), np.nan), chisq=np.full(N, np.nan),
+                   npix=(w != 0.0).sum(axis=1), fisher=np.full((N, K, K), np.nan), status=np.full(N, _lib.LMFIT_NAN, dtype=np.int32),
+                   niter=np.zeros(N, dtype=np.int32), at_bound=np.zeros(N, dtype=np.uint32), labels=list(a["names"]))
+        out["pars_a"][:, cols] = np.nan
+        out["pars_b"][:, cols] = np.nan
+        Pr._bind(self.obs_wave)
+        step = max(1, eng.b_max // (2 * (1 + Ka + 2 * int(bool(fit_vrad)))))   # the rows a star needs, both components counted
+        sel = np.flatnonzero(good)
+        self.timing = dict(network=0.0, broadening=0.0, update=0.0, iterations=0) if timing else None
+        if len(sel):
+            handle = LMHandle(K, min(step, len(sel)), eng.device, **o)
+            x_d = torch.as_tensor(x).to(eng.device) if P else None
+            try:
+                for s in range(0, len(sel), step):
+                    idx = sel[s:s + step]
+                    x0 = np.concatenate([start_a[idx][:, cols], start_b[idx][:, [cols[k] for k in free_b]], q0[idx, None]]
+                                        + ([np.ascontiguousarray(coef[idx], dtype=np.float64)] if P else []), axis=1)
+                    res = self._fit_binary_block(handle, flux[idx], w[idx], start_a[idx], start_b[idx], x0, a, bool(fit_vrad), float(vrad_step),
+                                                 int(check_every), int(o["maxiter"]), x_d)
+                    xb = res["x_best"].cpu().numpy()
+                    st = res["status"].cpu().numpy()
+                    xb[st == _lib.LMFIT_NAN] = np.nan
+                    out["pars_a"][idx[:, None], np.asarray(cols)[None, :]] = xb[:, :Ka]
+                    out["pars_b"][idx[:, None], np.asarray(cols)[None, :]] = xb[:, b_pos]
+                    out["ratio"][idx] = xb[:, Kl]
+                    out["coef"][idx] = xb[:, Kl + 1:]
+                    out["chisq"][idx] = res["chisq"].cpu().numpy()
+                    out["fisher"][idx] = np.where((st == _lib.LMFIT_NAN)[:, None, None], np.nan, res["A"].cpu().numpy())
+                    out["status"][idx] = st
+                    out["niter"][idx] = res["niter"].cpu().numpy()
+                    out["at_bound"][idx] = res["at_bound"].cpu().numpy().astype(np.uint32)
+            finally:
+                handle.close()
+        out["chisq"][out["status"] == _lib.LMFIT_NAN] = np.nan
+        out["err"] = crlb_from_fisher(out["fisher"])
+        return out
+
+    def _fit_binary_block(self, handle, flux, w, start_a, start_b, x0, a, fit_vrad, vrad_step, check_every, maxiter, x):
+        """One block of stars of ``fit_binary`` through the handle: the theta blocks hold A's rows, then B's."""
+        Pr = self.predictor
+        eng, D, jac_net = Pr.anns.engine, self.n_labels, Pr._jacobian()
+        torch = eng.torch
+        nb, nobs, Ka, P = flux.shape[0], flux.shape[1], a["Ka"], a["P"]
+        dev = eng.device
+        flux_d = torch.as_tensor(np.ascontiguousarray(flux)).to(dev)
+        w_d = torch.as_tensor(np.ascontiguousarray(w)).to(dev)
+        handle.begin(x0, a["lo"], a["hi"])
+        xt = handle.trial()
+        b_lab = torch.as_tensor(a["b_pos"][:D]).to(dev)               # where B's labels sit in x_trial: a tied one is A's
+        th = np.full((2 * nb, eng.ncols), np.nan)
+        th[:nb, :8], th[nb:, :8] = start_a, start_b
+        th_y = torch.as_tensor(th).to(dev)
+        th_j = th_y.repeat_interleave(D, dim=0)
+        th_pm = th_y.repeat(2, 1) if fit_vrad else None
+        rows = torch.empty((2, nb, 1 + Ka, nobs), dtype=torch.float32, device=dev)
+        rv = rows.view(2 * nb, 1 + Ka, nobs)
+        tm = self.timing
+        marks = []
+
+        def mark():
+            if tm is not None:
+                ev = torch.cuda.Event(enable_timing=True)
+                ev.record(torch.cuda.current_stream(dev))
+                marks.append(ev)
+        it = 0
+        while it < maxiter:
+            it += 1
+            mark()
+            y, jac = jac_net.eval(torch.cat([xt[:, :D], xt.index_select(1, b_lab)], dim=0))
+            mark()
+            if fit_vrad:
+                v = torch.cat([xt[:, D], xt[:, int(a["b_pos"][D])]])
+                th_y[:, 4] = v
+                th_j[:, 4] = v.repeat_interleave(D)
+                th_pm[:2 * nb, 4] = v + vrad_step
+                th_pm[2 * nb:, 4] = v - vrad_step
+                pm = eng.smooth_batch(y.repeat(2, 1), th_pm, stage=2)
+                rv[:, Ka] = (pm[:2 * nb] - pm[2 * nb:]) / (2.0 * vrad_step)
+            rv[:, 0] = eng.smooth_batch(y, th_y, stage=2)
+            rv[:, 1:1 + D] = smooth_rows(eng, jac.reshape(2 * nb * D, -1), th_j, 2).reshape(2 * nb, D, nobs)
+            mark()
+            handle.update_pair(rows[0], rows[1], flux_d, w_d, a["ia"], a["ib"], P, x)
+            mark()
+            if it % check_every == 0 and not bool((handle.status() == _lib.LMFIT_RUNNING).any().item()):
+                break
+        res = handle.result()
+        if tm is not None:
+            torch.cuda.synchronize(dev)
+            steps = ("network", "broadening", "update")
+            for i in range(0, len(marks), len(steps) + 1):
+                for j, name in enumerate(steps):
+                    tm[name] += marks[i + j].elapsed_time(marks[i + j + 1])
+            tm["iterations"] += it
+        return res
 
     def fit_joint_from_bank(self, flux, eflux, bank, npoly=4, topk=1, **fit_joint_kwargs):
         """``fit_joint`` started from the ``topk`` templates of ``bank`` that match each star best under a free continuum

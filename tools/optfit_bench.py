@@ -5,6 +5,7 @@ payne_lmfit_update an iteration) against scipy.optimize.least_squares around the
     python tools/optfit_bench.py --npoly 4 [--ref-stars 6] [--alt-rounds 3,10,20,40]     (OptFit.fit_joint: joint_mode below)
 
     python tools/optfit_bench.py --phot 7 [--npoly 4]                                       (OptFit.fit_specphot: phot_mode below)
+    python tools/optfit_bench.py --binary [--npoly 4]                                       (OptFit.fit_binary: binary_mode below)
 
 The workload: SMLP 4-256-256-256-4096 (synth.make_torch_net), 3600 observed pixels, stars drawn in the inner half of the label box
 with their own Vrad / Vrot / inst_R, spectra from the model itself plus seeded noise at S/N 100, starts 10 % of the box off the
@@ -279,6 +280,104 @@ def phot_mode(args):
     print(json.dumps(out), flush=True)
 
 
+def binary_mode(args):
+    """--binary: the --npoly workload (P = 4 unless --npoly says otherwise) with a second component a star -- another star's Teff and
+    log(g), the primary's [Fe/H] and [a/Fe] (tied in the fit), its Vrad 40 km/s off, light ratio q = 0.3; the starts 10 % of the box
+    off in every label, 1 km/s in both Vrad, q = 0.4.  (a) ``fit_binary`` stars/s, status counts and the per-iteration split;
+    (b) the update alone for one block of stars, event pairs on the stream, every star RUNNING: payne_lmfit_update_pair at
+    K = 5 + 3 + 1 + P against payne_lmfit_update_poly at the same K (it streams 1 + K - P rows a star where the pair update streams
+    2 + 5 + 5) and against the route without it -- torch forms the K + 1 mixed rows in fp32 and payne_lmfit_update sums them;
+    (c) payne_lmfit_update_pair's compulsory bytes, 12 n 4 + n 4 + n 8 a star and x once, against the HBM peak."""
+    import torch
+    from numpy.polynomial.chebyshev import chebvander
+    from thepayne_amd.fitting.optfit import OptFit, LMHandle, check_binary_args
+    from thepayne_amd.fitting.contfit import abscissa
+    P, N, n, q_true, tie = args.npoly or 4, args.stars, args.nobs, 0.3, ("feh", "afe")
+    net, obs_wave, truth, start, rng = workload(N, n)
+    fit = OptFit(net, "SMLP", obs_wave, b_max=args.b_max)
+    eng = fit.predictor.anns.engine
+    perm = np.roll(np.arange(N), 1)
+    truth_b, start_b = truth[perm].copy(), start[perm].copy()
+    for t, s in ((truth_b, truth), (start_b, start)):
+        t[:, 2:4], t[:, 7] = s[:, 2:4], s[:, 7]
+    truth_b[:, 4] = truth[:, 4] + 40.0
+    start_a = start.copy()
+    start_a[:, 4], start_b[:, 4] = truth[:, 4] + 1.0, truth_b[:, 4] - 1.0
+    clean = ((1.0 - q_true) * fit.model_spectra(truth) + q_true * fit.model_spectra(truth_b)).cpu().numpy().astype(np.float64)
+    x = abscissa(obs_wave)
+    ctrue = np.concatenate([rng.uniform(0.5, 2.0, (N, 1)), rng.uniform(-0.1, 0.1, (N, P - 1))], axis=1)
+    poly = np.ascontiguousarray((chebvander(x, P - 1) @ ctrue.T).T)
+    flux = ((clean + rng.normal(0, 0.01, (N, n))) * poly).astype(np.float32)
+    eflux = 0.01 * poly
+
+    def clock(call):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        res = call()
+        torch.cuda.synchronize()
+        return time.perf_counter() - t0, res
+
+    def call(**kw):
+        return fit.fit_binary(flux, eflux, start_a, start_b, ratio=0.4, tie=tie, npoly=P, **kw)
+    for _ in range(args.warmup):
+        clock(call)
+    secs = []
+    for _ in range(args.repeats):
+        s, res = clock(call)
+        secs.append(s)
+    clock(lambda: call(timing=True))
+    tm = fit.timing
+    done = res["status"] == 1
+    out = {"mode": "binary", "npoly": P, "stars": N, "nobs": n, "b_max": args.b_max, "repeats": args.repeats, "warmup": args.warmup,
+           "fit_binary_s_median": float(np.median(secs)), "fit_binary_s_min": float(np.min(secs)), "fit_binary_stars_per_s": N / float(np.median(secs)),
+           "status_counts": np.bincount(res["status"], minlength=6).tolist(), "evaluations_median": float(np.median(res["niter"])),
+           "evaluations_max": int(res["niter"].max()), "block_iterations": tm["iterations"],
+           "ms_per_iteration": {k: tm[k] / tm["iterations"] for k in ("network", "broadening", "update")},
+           "ratio_median_converged": float(np.median(res["ratio"][done])) if done.any() else None,
+           "ratio_err_median_converged": float(np.median(res["err"][done][:, res["labels"].index("ratio")])) if done.any() else None}
+    # (b) the update alone, every star RUNNING (a fresh begin before each launch, outside the event pair)
+    a = check_binary_args(flux[:1], eflux[:1], start_a[:1], start_b[:1], n, 4, net["xmin"], net["xmax"], ratio=0.4, tie=tie, npoly=P)
+    Ka, Kl, ia, ib, lo, hi = a["Ka"], a["Kl"], a["ia"], a["ib"], a["lo"], a["hi"]
+    K, B, dev = Kl + 1 + P, min(N, max(1, args.b_max // 5)), eng.device
+    rows_a = torch.randn((B, 1 + Ka, n), dtype=torch.float32, device=dev)
+    rows_b = torch.randn((B, 1 + Ka, n), dtype=torch.float32, device=dev)
+    rows_a[:, 0], rows_b[:, 0] = 1.0 + 0.1 * rows_a[:, 0], 1.0 + 0.1 * rows_b[:, 0]
+    rows_poly = torch.randn((B, 1 + K - P, n), dtype=torch.float32, device=dev)
+    rows_poly[:, 0] = rows_a[:, 0]
+    flux_d, w_d, x_d = torch.as_tensor(flux[:B]).to(dev), torch.as_tensor(1.0 / eflux[:B] ** 2).to(dev), torch.as_tensor(x).to(dev)
+    T32 = torch.as_tensor(chebvander(x, P - 1).T.copy()).to(dev).to(torch.float32)               # [P, n]
+    free_b = [k for k in range(Ka) if a["b_pos"][k] >= Ka]
+    x0 = np.concatenate([start_a[:B][:, a["cols"]], start_b[:B][:, [a["cols"][k] for k in free_b]], np.full((B, 1), 0.4), ctrue[:B]], axis=1)
+    lo_p, hi_p = lo.copy(), hi.copy()
+    hK = LMHandle(K, B, dev)
+    big = torch.empty((B, 1 + K, n), dtype=torch.float32, device=dev)
+    sel_a = torch.as_tensor(np.where(ia >= 0, 1 + ia, 0)).to(dev)
+    sel_b = torch.as_tensor(np.where(ib >= 0, 1 + ib, 0)).to(dev)
+    has_a = torch.as_tensor((ia >= 0).astype(np.float32)).to(dev)[None, :, None]
+    has_b = torch.as_tensor((ib >= 0).astype(np.float32)).to(dev)[None, :, None]
+
+    def torch_route():
+        xt = hK.trial()
+        q = xt[:, Kl].to(torch.float32)[:, None]
+        p = xt[:, Kl + 1:].to(torch.float32) @ T32                                                # [B, n]
+        mix = (1.0 - q) * rows_a[:, 0] + q * rows_b[:, 0]
+        big[:, 0] = mix * p
+        big[:, 1:1 + Kl] = ((1.0 - q)[:, None] * has_a * rows_a.index_select(1, sel_a) + q[:, None] * has_b * rows_b.index_select(1, sel_b)) * p[:, None, :]
+        big[:, 1 + Kl] = (rows_b[:, 0] - rows_a[:, 0]) * p
+        big[:, 2 + Kl:] = mix[:, None, :] * T32[None, :, :]
+        hK.update(big, flux_d, w_d)
+    ms_pair = event_ms(torch, lambda: hK.begin(x0, lo, hi), lambda: hK.update_pair(rows_a, rows_b, flux_d, w_d, ia, ib, P, x_d), args.repeats * 4, args.warmup + 2)
+    ms_poly = event_ms(torch, lambda: hK.begin(x0, lo_p, hi_p), lambda: hK.update_poly(rows_poly, flux_d, w_d, x_d, P), args.repeats * 4, args.warmup + 2)
+    ms_torch = event_ms(torch, lambda: hK.begin(x0, lo, hi), torch_route, args.repeats * 4, args.warmup + 2)
+    hK.close()
+    nbytes = B * ((2 + 2 * Ka) * n * 4 + n * 4 + n * 8) + n * 8
+    out.update({"stars_per_block": B, "K": K, "update_pair_ms": ms_pair, "update_poly_ms_same_K": ms_poly, "torch_rows_plus_update_ms": ms_torch,
+                "update_pair_over_update_poly_same_K": ms_pair / ms_poly, "torch_route_over_update_pair": ms_torch / ms_pair,
+                "update_pair_bytes": nbytes, "update_pair_bytes_per_s": nbytes / (ms_pair * 1e-3), "update_pair_fraction_of_hbm_peak": nbytes / (ms_pair * 1e-3) / HBM_PEAK,
+                "update_poly_bytes_same_K": B * ((1 + K - P) * n * 4 + n * 4 + n * 8) + n * 8})
+    print(json.dumps(out), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--stars", type=int, default=4096)
@@ -291,7 +390,10 @@ def main():
     ap.add_argument("--ref-stars", type=int, default=6, help="--npoly: stars compared with the fp64 joint reference loop")
     ap.add_argument("--alt-rounds", type=lambda s: [int(v) for v in s.split(",")], default=[3, 10, 20, 40], help="--npoly: fit_with_continuum's rounds")
     ap.add_argument("--phot", type=int, default=0, help="fit this many magnitudes a star along with the spectrum, logR and Av free (fit_specphot)")
+    ap.add_argument("--binary", action="store_true", help="fit two components a star, [Fe/H] and [a/Fe] tied, with a light ratio (fit_binary)")
     args = ap.parse_args()
+    if args.binary:
+        return binary_mode(args)
     if args.phot:
         return phot_mode(args)
     if args.npoly:
