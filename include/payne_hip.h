@@ -725,6 +725,44 @@ int payne_tmatch_match_poly(payne_tmatch* h, const float* templates_dev, int ld_
 int payne_tmatch_poly_stars(void);
 int payne_tmatch_poly_chunk(void);
 
+/* The search against PAIRS of templates with both amplitudes free, the starting points of payne_lmfit_update_pair's fit:
+ *   chi^2[s][a][b] = min over (alpha, beta) of sum_p w[s][p] (flux[s][p] - alpha m[a][p] - beta m[b][p])^2;
+ * alpha + beta is the two-component fit's scale and beta / (alpha + beta) its light ratio.  The primary a runs over the kA <=
+ * PAYNE_TMATCH_MAX_PRIMARIES templates that cand_dev names per star, the secondary b over the whole bank.  Three enqueued launches:
+ * the moments B[s][t] = sum (w f) m_t, S[s][t] = sum w m_t^2 and c0[s] (N x M, the plain search's tile with its two products kept
+ * apart); the cross term X = sum (w m_a) m_b as one (N kA) x M matrix product over n (row s kA + j is star s with primary
+ * cand[s][j]), the 2 x 2 solve and the rows' lists per chunk; the merge.  csrc/tmatch_pair_core.hpp holds the arithmetic and its
+ * order.  D = fma(-X, X, Sa Sb), alpha = (Ba Sb - Bb X) / D, beta = (Bb Sa - Ba X) / D and
+ * chi^2 = c0 + alpha^2 Sa + 2 alpha beta X + beta^2 Sb - 2 (alpha Ba + beta Bb), within (2 n + 16) 2^-53 of the terms' magnitudes.
+ * The rules are payne_tmatch_match's except:
+ *   NaN      a pair is NaN and never listed when a == b; when cand[s][j] lies outside 0 .. M - 1 (-1 marks an unused slot); when
+ *            either template is not finite at a pixel of the star with w != 0; when Sa or Sb is not > 0 (so a star without a
+ *            weighted pixel lists nothing); when the pair is collinear, not (D > 2^-20 Sa Sb); when alpha or beta is not > 0 (one
+ *            template with a scale fits as well: payne_tmatch_match_poly with P = 1); when b is one of the star's primaries in an
+ *            earlier slot j' < j (that pair is (j', a): an unordered pair is listed once).
+ *   lists    ascending in (chi^2, slot j, b).  idx_a_dev and idx_b_dev DEVICE int32 [N][topk] hold TEMPLATE indices (not slots), -1
+ *            in an empty slot; chisq_dev DEVICE fp64 [N][topk], +inf there; amp_dev DEVICE fp64 [N][topk][2] holds (alpha, beta),
+ *            NaN there.  all_dev DEVICE fp64 [N kA][ld_a], every chi^2 of every row, or NULL.
+ *   order    the cross launch's grid is (tiles of payne_tmatch_pair_rows() rows) x (chunks of payne_tmatch_pair_chunk() templates);
+ *            the merge walks a star's rows in j order and each row's chunks in chunk order.  No atomics: the same inputs give the
+ *            same bytes, with or without all_dev, and a star's bytes do not depend on the other stars of the call.
+ *   cand     a primary named twice for one star is the caller's error: its pairs are listed twice.
+ * payne_tmatch_create_pairs: payne_tmatch_create plus the workspace of match_pairs: the moments (2 max_stars max_templates + max_stars
+ * doubles) and the lists of max_stars * max_primaries rows (ceil(max_templates / chunk) * rows * 8 entries of 28 bytes).
+ * payne_tmatch_match works on such a handle as on any other.  PAYNE_E_INVALID as payne_tmatch_create, and max_primaries outside
+ * 1 .. PAYNE_TMATCH_MAX_PRIMARIES.
+ * payne_tmatch_match_pairs: cand_dev DEVICE int32 [N][kA]; the other inputs as payne_tmatch_match's.  PAYNE_E_INVALID as
+ * payne_tmatch_match, and kA outside 1 .. the handle's max_primaries (a handle of payne_tmatch_create has 0), a null cand_dev /
+ * idx_a_dev / idx_b_dev / amp_dev.  Nothing is touched on a refusal; N == 0 or M == 0 succeeds and does nothing. */
+#define PAYNE_TMATCH_MAX_PRIMARIES 16
+
+int payne_tmatch_create_pairs(int device, int max_stars, int max_templates, int max_primaries, payne_tmatch** out);
+int payne_tmatch_match_pairs(payne_tmatch* h, const float* templates_dev, int ld_t, int M, const float* flux_dev, const double* w_dev,
+                             int ld_f, int N, int n, const int* cand_dev, int kA, int topk, int* idx_a_dev, int* idx_b_dev,
+                             double* chisq_dev, double* amp_dev, double* all_dev, long long ld_a, void* stream);
+int payne_tmatch_pair_rows(void);
+int payne_tmatch_pair_chunk(void);
+
 /* ---- continuum polynomials: the blaze's Chebyshev coefficients for many stars against a given model row each ----
  * payne_contfit_batch: per star the c [P] that minimise chi^2 = sum_p w_p (f_p - m_p sum_j c_j T_j(x_p))^2, the likelihood's own
  * objective in its pc_* parameters (modpoly: model x polycalc) for a fixed model, which is linear least squares; optional

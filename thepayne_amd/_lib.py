@@ -45,6 +45,7 @@ SYMBOLS = ["payne_version", "payne_ctx_create", "payne_ctx_set_obs", "payne_ctx_
            "payne_lmfit_destroy",
            "payne_tmatch_create", "payne_tmatch_match", "payne_tmatch_chunk", "payne_tmatch_destroy",
            "payne_tmatch_create_poly", "payne_tmatch_match_poly", "payne_tmatch_poly_stars", "payne_tmatch_poly_chunk",
+           "payne_tmatch_create_pairs", "payne_tmatch_match_pairs", "payne_tmatch_pair_rows", "payne_tmatch_pair_chunk",
            "payne_contfit_batch",
            "payne_sedfit_create", "payne_sedfit_jac", "payne_sedfit_run", "payne_sedfit_destroy"]
 
@@ -133,6 +134,7 @@ LMFIT_MAX_K = 15
 LMFIT_PHOT_MAX_F = 64                                      # payne_lmfit_update_phot stages a star's filters in LDS
 TMATCH_MAX_TOPK = 8
 TMATCH_MAX_POLY = 8
+TMATCH_MAX_PRIMARIES = 16
 CONTFIT_OK, CONTFIT_NONPOSITIVE, CONTFIT_TOO_FEW, CONTFIT_SINGULAR, CONTFIT_NAN, CONTFIT_BAD_MODEL = range(6)
 CONTFIT_STATUS_NAMES = ("OK", "NONPOSITIVE", "TOO_FEW", "SINGULAR", "NAN", "BAD_MODEL")
 CONTFIT_MAX_P, CONTFIT_MAX_NCLIP, CONTFIT_MAX_N = 15, 16, 262144
@@ -311,7 +313,12 @@ def load(path=None):
     lib.payne_tmatch_match_poly.argtypes = [ctxp, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int,
                                             C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_longlong, C.c_void_p]
     lib.payne_tmatch_match_poly.restype = C.c_int
-    for name in ("payne_tmatch_poly_stars", "payne_tmatch_poly_chunk"):
+    lib.payne_tmatch_create_pairs.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(ctxp)]
+    lib.payne_tmatch_create_pairs.restype = C.c_int
+    lib.payne_tmatch_match_pairs.argtypes = [ctxp, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int,
+                                             C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_longlong, C.c_void_p]
+    lib.payne_tmatch_match_pairs.restype = C.c_int
+    for name in ("payne_tmatch_poly_stars", "payne_tmatch_poly_chunk", "payne_tmatch_pair_rows", "payne_tmatch_pair_chunk"):
         getattr(lib, name).argtypes = []
         getattr(lib, name).restype = C.c_int
     lib.payne_contfit_batch.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_longlong, C.c_void_p, C.c_longlong, C.c_int, C.c_void_p, C.c_void_p,

@@ -14,9 +14,9 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libpayne_hip.so")
-SOURCES = ["payne_hip.hip", "k_dense.hip", "k_post_lean.hip", "k_post_full_a.hip", "k_post_full_b.hip", "k_post_big.hip", "k_post_chip2.hip", "k_smooth.hip", "k_quicklook.hip", "k_mad.hip", "k_lnmlp.hip", "k_lnmlp_train.hip", "k_specmlp_train.hip", "k_specjac.hip", "k_lmfit.hip", "k_tmatch.hip", "k_tmatch_poly.hip", "k_contfit.hip", "k_sedfit.hip", "mlp_api.hip", "sampler_api.hip"]
+SOURCES = ["payne_hip.hip", "k_dense.hip", "k_post_lean.hip", "k_post_full_a.hip", "k_post_full_b.hip", "k_post_big.hip", "k_post_chip2.hip", "k_smooth.hip", "k_quicklook.hip", "k_mad.hip", "k_lnmlp.hip", "k_lnmlp_train.hip", "k_specmlp_train.hip", "k_specjac.hip", "k_lmfit.hip", "k_tmatch.hip", "k_tmatch_poly.hip", "k_tmatch_pair.hip", "k_contfit.hip", "k_sedfit.hip", "mlp_api.hip", "sampler_api.hip"]
 HEADERS = ["post_core.hpp", "post_seq.hpp", "host_tables.hpp", "ns_core.hpp", "dense_kernels.hpp", "post_kernels.hpp",
-           "sed_kernel.hpp", "sed_core.hpp", "sed_tile.hpp", "post_onchip.hpp", "post_onchip2.hpp", "sampler_kernels.hpp", "sampler_core.hpp", "select.hpp", "quicklook_core.hpp", "mad_core.hpp", "queue_block.hpp", "lnmlp_core.hpp", "lnmlp_train_core.hpp", "specmlp_train_core.hpp", "specjac_core.hpp", "lmfit_core.hpp", "lmfit_phot_core.hpp", "lmfit_pair_core.hpp", "sedfit_core.hpp", "tmatch_core.hpp", "tmatch_poly_core.hpp", "tmatch_handle.hpp", "contfit_core.hpp", "normal_tile.hpp", "cheb_series.hpp", "host_prologue.hpp", "mlp_tile.hpp", "mlp_train_tail.hpp", "mlp_desc.hpp", "ctx_api.hpp", "out_tile.hpp", "out_plan.hpp"]
+           "sed_kernel.hpp", "sed_core.hpp", "sed_tile.hpp", "post_onchip.hpp", "post_onchip2.hpp", "sampler_kernels.hpp", "sampler_core.hpp", "select.hpp", "quicklook_core.hpp", "mad_core.hpp", "queue_block.hpp", "lnmlp_core.hpp", "lnmlp_train_core.hpp", "specmlp_train_core.hpp", "specjac_core.hpp", "lmfit_core.hpp", "lmfit_phot_core.hpp", "lmfit_pair_core.hpp", "sedfit_core.hpp", "tmatch_core.hpp", "tmatch_poly_core.hpp", "tmatch_pair_core.hpp", "tmatch_handle.hpp", "contfit_core.hpp", "normal_tile.hpp", "cheb_series.hpp", "host_prologue.hpp", "mlp_tile.hpp", "mlp_train_tail.hpp", "mlp_desc.hpp", "ctx_api.hpp", "out_tile.hpp", "out_plan.hpp"]
 # (-amdgpu-kernarg-preload-count: a kernel's leading scalar arguments arrive in registers at wave start instead of by s_load)
 HIPCC_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-fno-gpu-rdc",
                "-DNDEBUG", "-Wall", "-Wno-unused-function", "-mllvm", "-amdgpu-kernarg-preload-count=16"]

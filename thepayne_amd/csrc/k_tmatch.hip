@@ -257,6 +257,11 @@ extern "C" void payne_tmatch_destroy(payne_tmatch* h) {
       (void)hipFree(h->poly_c);                                     // (null unless payne_tmatch_create_poly made the handle)
       (void)hipFree(h->poly_i);
       (void)hipFree(h->poly_coef);
+      (void)hipFree(h->pair_mom);                                   // (null unless payne_tmatch_create_pairs made the handle)
+      (void)hipFree(h->pair_c0);
+      (void)hipFree(h->pair_c);
+      (void)hipFree(h->pair_i);
+      (void)hipFree(h->pair_amp);
     }
   }
   delete h;

@@ -895,7 +895,7 @@ class OptFit(object):
         What to keep in mind.  Swapping A and B with q -> 1 - q is the same model: which component comes out as A is decided by the
         start.  A ratio that is constant in wavelength is an approximation for a narrow range.  The evidence for a binary is ``chisq``
         against ``fit_joint``'s (or ``fit``'s) on the same pixels, not anything this fit reports by itself.  The starting points are the
-        caller's (a search for pairs of templates is not part of this method); two components started at the same labels and Vrad
+        caller's (``fit_binary_from_bank`` takes them from a bank's pair search); two components started at the same labels and Vrad
         have identical rows, which ends ``SINGULAR``."""
         Pr = self.predictor
         anns, eng, D = Pr.anns, Pr.anns.engine, self.n_labels
@@ -1014,6 +1014,60 @@ class OptFit(object):
                     tm[name] += marks[i + j].elapsed_time(marks[i + j + 1])
             tm["iterations"] += it
         return res
+
+    def fit_binary_from_bank(self, flux, eflux, bank, topk=1, primaries=4, **fit_binary_kwargs):
+        """``fit_binary`` started from the ``topk`` pairs of templates of ``bank`` that fit each star best with both amplitudes free
+        (``bank.match_pairs(topk=topk, primaries=primaries)``): per rank the pair's theta rows are ``start_a`` and ``start_b`` (A the
+        brighter), its light ratio, clipped into ``ratio_bounds``, is ``ratio``, and with ``npoly`` >= 1 the starting ``coef`` is
+        (the pair's scale, 0, ...).  ``fit_from_bank``'s logic otherwise: one ``fit_binary`` call per rank over the stars that have
+        a pair of that rank; per star the result of lowest chi^2 among those whose status is not NAN / SINGULAR is kept, the lower
+        rank on a tie (rank 0's if none qualifies).  Returns ``fit_binary``'s dict plus ``start_index_a``, ``start_index_b`` (the
+        templates), ``start_chisq`` (the pair's chi^2 in the search), ``start_rank`` and ``single_chisq`` (the best
+        one-template-and-scale chi^2 of the same pixels: what ``chisq`` has to beat for the star to count as a binary).  A star
+        without a pair keeps status NAN, NaN parameters and ``start_index_a`` -1.  ``fit_binary_kwargs`` go to ``fit_binary``; with
+        ``npoly`` = 0 the model has no scale, so the spectra must be normalised."""
+        if not hasattr(bank, "match_pairs") or not hasattr(bank, "obs_wave"):
+            raise TypeError("bank must be a TemplateBank")
+        if np.shape(bank.obs_wave) != self.obs_wave.shape or not np.array_equal(np.asarray(bank.obs_wave), self.obs_wave):
+            raise ValueError("the bank's obs_wave differs from the fitter's")
+        for name in ("start_a", "start_b", "ratio", "coef"):
+            if name in fit_binary_kwargs:
+                raise TypeError("fit_binary_from_bank takes its starts, ratio and coefficients from the bank")
+        flux = np.atleast_2d(np.asarray(flux, dtype=np.float32))
+        eflux = np.atleast_2d(np.asarray(eflux, dtype=np.float64))
+        N = flux.shape[0]
+        kw = dict(fit_binary_kwargs)
+        rb = kw.get("ratio_bounds", (0.01, 0.99))
+        P = int(kw.get("npoly", 0))
+        probe = np.zeros((N, 8))                                     # (what does not depend on the starts is checked before the search)
+        a = check_binary_args(flux, eflux, probe, probe, len(self.obs_wave), self.n_labels, self.predictor.anns.xmin, self.predictor.anns.xmax,
+                              ratio=0.5 * (rb[0] + rb[1]), **kw)
+        K = a["Kl"] + 1 + P
+        m = bank.match_pairs(flux, eflux, topk=topk, primaries=primaries)
+        k = m["index_a"].shape[1]
+        out = dict(pars_a=np.full((N, 8), np.nan), pars_b=np.full((N, 8), np.nan), ratio=np.full(N, np.nan), coef=np.full((N, P), np.nan),
+                   chisq=np.full(N, np.nan), npix=m["npix"], fisher=np.full((N, K, K), np.nan), status=np.full(N, _lib.LMFIT_NAN, dtype=np.int32),
+                   niter=np.zeros(N, dtype=np.int32), at_bound=np.zeros(N, dtype=np.uint32), labels=list(a["names"]), err=np.full((N, K), np.nan),
+                   start_index_a=np.full(N, -1, dtype=np.int32), start_index_b=np.full(N, -1, dtype=np.int32), start_chisq=np.full(N, np.inf),
+                   start_rank=np.full(N, -1, dtype=np.int32), single_chisq=m["single_chisq"])
+        per_star = ("pars_a", "pars_b", "ratio", "coef", "chisq", "fisher", "status", "niter", "at_bound", "err")
+        for r in range(k):
+            sel = np.flatnonzero(m["index_a"][:, r] >= 0)
+            if len(sel) == 0:
+                continue
+            if P:
+                kw["coef"] = np.concatenate([m["scale"][sel, r][:, None], np.zeros((len(sel), P - 1))], axis=1)
+            res = self.fit_binary(flux[sel], eflux[sel], m["pars_a"][sel, r], m["pars_b"][sel, r], ratio=np.clip(m["ratio"][sel, r], rb[0], rb[1]), **kw)
+            valid = (res["status"] != _lib.LMFIT_NAN) & (res["status"] != _lib.LMFIT_SINGULAR)
+            held = out["start_rank"][sel] >= 0
+            held_valid = held & (out["status"][sel] != _lib.LMFIT_NAN) & (out["status"][sel] != _lib.LMFIT_SINGULAR)
+            take = ~held | (valid & (~held_valid | (res["chisq"] < out["chisq"][sel])))
+            dst = sel[take]
+            for name in per_star:
+                out[name][dst] = res[name][take]
+            out["start_index_a"][dst], out["start_index_b"][dst] = m["index_a"][dst, r], m["index_b"][dst, r]
+            out["start_chisq"][dst], out["start_rank"][dst] = m["chisq"][dst, r], r
+        return out
 
     def fit_joint_from_bank(self, flux, eflux, bank, npoly=4, topk=1, **fit_joint_kwargs):
         """``fit_joint`` started from the ``topk`` templates of ``bank`` that match each star best under a free continuum

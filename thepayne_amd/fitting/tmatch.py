@@ -12,6 +12,10 @@ every (star, template) pair, chi^2 = min_c sum_p w_p (flux_p - template_p sum_j 
 products, a scaled Cholesky solve per pair).  Its dict goes to ``ContinuumFit.fit_to_bank(match=)`` as it is, and
 ``OptFit.fit_joint_from_bank`` starts the joint fit from the best few with their coefficients.
 
+``match_pairs`` searches PAIRS of templates with both amplitudes free, chi^2 = min sum_p w_p (flux_p - alpha m_a - beta m_b)^2: the
+starting points of ``OptFit.fit_binary`` (payne_tmatch_match_pairs: the moments and a cross term per (star, primary) as matrix
+products, a 2 x 2 solve per pair); ``OptFit.fit_binary_from_bank`` starts the two-component fit from the best few.
+
 No interpolation between the lattice's nodes: the best template is a start for a fit, not a measurement.
 ``OptFit.fit_from_bank`` runs the fit from the best few.
 """
@@ -25,7 +29,9 @@ from ..engine import THETA_SPEC_COLS
 from ..predict._spec import PayneSpecPredict
 from .forecast import weights_from_errors
 
-__all__ = ["TemplateBank", "TMatchHandle", "lattice_theta", "check_match_args", "check_npoly"]
+__all__ = ["TemplateBank", "TMatchHandle", "lattice_theta", "check_match_args", "check_npoly", "check_pair_args", "PAIR_WORKSPACE_BYTES"]
+
+PAIR_WORKSPACE_BYTES = 256 * 1024 * 1024             # ``match_pairs`` walks the stars in blocks whose moments stay below this
 
 
 def lattice_theta(xmin, xmax, steps, vrad=(0.0,), vrot=(5.0,), inst_R=(np.nan,), inner=(0.0, 1.0)):
@@ -80,16 +86,51 @@ def check_npoly(npoly):
     return int(npoly)
 
 
+def check_pair_args(topk, primaries, M, shortlist=None, N=None):
+    """What ``TemplateBank.match_pairs`` checks of its own arguments: (topk, primaries, shortlist int32 [N, primaries] or None).  In a
+    shortlist an index outside 0 .. M - 1 becomes -1 (an unused slot), and so does a template that an earlier slot of the same star
+    names already: the device is never handed a primary twice."""
+    if isinstance(topk, bool) or int(topk) != topk or not (1 <= int(topk) <= _lib.TMATCH_MAX_TOPK):
+        raise ValueError("topk must be 1 .. %d, got %r" % (_lib.TMATCH_MAX_TOPK, topk))
+    if isinstance(primaries, bool) or int(primaries) != primaries or not (1 <= int(primaries) <= _lib.TMATCH_MAX_PRIMARIES):
+        raise ValueError("primaries must be 1 .. %d, got %r" % (_lib.TMATCH_MAX_PRIMARIES, primaries))
+    k, kA = int(topk), int(primaries)
+    if shortlist is None:
+        if kA > _lib.TMATCH_MAX_TOPK:
+            raise ValueError("primaries above %d need a shortlist: the single-template search lists at most %d" % (_lib.TMATCH_MAX_TOPK, _lib.TMATCH_MAX_TOPK))
+        return k, kA, None
+    raw = np.asarray(shortlist.cpu() if hasattr(shortlist, "cpu") else shortlist)
+    if raw.dtype.kind not in "iu":
+        raise ValueError("shortlist must hold integers (template indices, -1: an unused slot)")
+    if raw.ndim == 1 and N in (None, 1):
+        raw = raw[None, :]
+    if raw.ndim != 2 or raw.shape[1] != kA or (N is not None and raw.shape[0] != N):
+        raise ValueError("shortlist must be [%s, %d], got %s" % ("N" if N is None else N, kA, raw.shape))
+    raw = raw.astype(np.int64)
+    sl = np.where((raw >= 0) & (raw < M), raw, -1).astype(np.int32)
+    for j in range(1, kA):
+        sl[(sl[:, j:j + 1] == sl[:, :j]).any(axis=1), j] = -1
+    return k, kA, sl
+
+
 class TMatchHandle(object):
     """Owner of one ``payne_tmatch`` handle (its workspace of partial lists): at most ``max_stars`` x ``max_templates`` a call.
-    ``max_poly`` > 0: the handle also holds ``match_poly``'s workspace for up to that many coefficients."""
+    ``max_poly`` > 0: the handle also holds ``match_poly``'s workspace for up to that many coefficients.  ``max_primaries`` > 0 (with
+    ``max_poly`` = 0): it holds ``match_pairs``' workspace, the moments and the lists of ``max_stars * max_primaries`` rows."""
 
-    def __init__(self, max_stars, max_templates, device, max_poly=0):
+    def __init__(self, max_stars, max_templates, device, max_poly=0, max_primaries=0):
         import torch
         self.torch, self.lib = torch, _lib.load()
         self.device, self.max_stars, self.max_templates, self.max_poly = device, int(max_stars), int(max_templates), check_npoly(max_poly)
+        if isinstance(max_primaries, bool) or int(max_primaries) != max_primaries or not (0 <= int(max_primaries) <= _lib.TMATCH_MAX_PRIMARIES):
+            raise ValueError("max_primaries must be 0 .. %d, got %r" % (_lib.TMATCH_MAX_PRIMARIES, max_primaries))
+        self.max_primaries = int(max_primaries)
+        if self.max_poly and self.max_primaries:
+            raise ValueError("a handle holds the polynomial's workspace or the pairs', not both")
         self._h = C.c_void_p()
-        if self.max_poly:
+        if self.max_primaries:
+            rc = self.lib.payne_tmatch_create_pairs(self.device.index, self.max_stars, self.max_templates, self.max_primaries, C.byref(self._h))
+        elif self.max_poly:
             rc = self.lib.payne_tmatch_create_poly(self.device.index, self.max_stars, self.max_templates, self.max_poly, C.byref(self._h))
         else:
             rc = self.lib.payne_tmatch_create(self.device.index, self.max_stars, self.max_templates, C.byref(self._h))
@@ -146,6 +187,33 @@ class TMatchHandle(object):
             raise RuntimeError("payne_tmatch_match_poly failed (%d): %s" % (rc, self.lib.payne_last_error(None).decode()))
         return idx, chisq, coef, flags, every
 
+    def match_pairs(self, templates, flux, w, cand, topk, n=None, return_all=False):
+        """``match`` against pairs of templates: cand int32 [N, kA] on the device names each star's primaries (-1: an unused slot) ->
+        (idx_a, idx_b int32 [N, topk] template indices, chisq fp64 [N, topk], amp fp64 [N, topk, 2] = (alpha, beta), all fp64
+        [N, kA, M] or None)."""
+        torch = self.torch
+        if templates.dtype != torch.float32 or flux.dtype != torch.float32 or w.dtype != torch.float64 or cand.dtype != torch.int32:
+            raise ValueError("templates and flux fp32, w fp64, cand int32")
+        if templates.dim() != 2 or flux.dim() != 2 or tuple(w.shape) != tuple(flux.shape) or cand.dim() != 2 or cand.shape[0] != flux.shape[0]:
+            raise ValueError("templates [M, ld_t], flux and w [N, ld_f], cand [N, kA]; got %s, %s, %s, %s"
+                             % (tuple(templates.shape), tuple(flux.shape), tuple(w.shape), tuple(cand.shape)))
+        if not (templates.is_contiguous() and flux.is_contiguous() and w.is_contiguous() and cand.is_contiguous()):
+            raise ValueError("templates, flux, w and cand must be contiguous")
+        M, N, kA = templates.shape[0], flux.shape[0], cand.shape[1]
+        n = min(templates.shape[1], flux.shape[1]) if n is None else int(n)
+        idx_a = torch.empty((N, topk), dtype=torch.int32, device=self.device)
+        idx_b = torch.empty((N, topk), dtype=torch.int32, device=self.device)
+        chisq = torch.empty((N, topk), dtype=torch.float64, device=self.device)
+        amp = torch.empty((N, topk, 2), dtype=torch.float64, device=self.device)
+        every = torch.empty((N, kA, M), dtype=torch.float64, device=self.device) if return_all else None
+        stream = C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+        rc = self.lib.payne_tmatch_match_pairs(self._h, templates.data_ptr(), templates.shape[1], M, flux.data_ptr(), w.data_ptr(), flux.shape[1], N, n,
+                                               cand.data_ptr(), kA, int(topk), idx_a.data_ptr(), idx_b.data_ptr(), chisq.data_ptr(), amp.data_ptr(),
+                                               every.data_ptr() if return_all else None, M, stream)
+        if rc != 0:
+            raise RuntimeError("payne_tmatch_match_pairs failed (%d): %s" % (rc, self.lib.payne_last_error(None).decode()))
+        return idx_a, idx_b, chisq, amp, every
+
     def close(self):
         if getattr(self, "_h", None) is not None and self._h.value:
             self.lib.payne_tmatch_destroy(self._h)                  # (waits for the device)
@@ -171,7 +239,7 @@ class TemplateBank(object):
         self.predictor = PayneSpecPredict(specANNpath, NNtype=NNtype, device=device, b_max=b_max)
         self.n_labels = self.predictor.anns.n_labels
         self.max_stars = int(max_stars)
-        self.theta, self.templates, self._handle = None, None, None
+        self.theta, self.templates, self._handle, self._pair_handle = None, None, None, None
 
     def lattice(self, steps, vrad=(0.0,), vrot=(5.0,), inst_R=(np.nan,), inner=(0.0, 1.0)):
         """``build`` on ``lattice_theta`` of the network's box; returns self."""
@@ -200,6 +268,24 @@ class TemplateBank(object):
     def __len__(self):
         return 0 if self.theta is None else len(self.theta)
 
+    def _device_inputs(self, flux, eflux, topk):
+        """(flux fp32 [N, nobs], w fp64 [N, nobs]) on the device from host arrays or device tensors, as ``match`` states."""
+        eng = self.predictor.anns.engine
+        torch, dev, nobs = eng.torch, eng.device, len(self.obs_wave)
+        if isinstance(flux, torch.Tensor) or isinstance(eflux, torch.Tensor):
+            if not (1 <= int(topk) <= _lib.TMATCH_MAX_TOPK):
+                raise ValueError("topk must be 1 .. %d, got %r" % (_lib.TMATCH_MAX_TOPK, topk))
+            f = torch.as_tensor(flux).to(device=dev, dtype=torch.float32).reshape(-1, nobs).contiguous()
+            e = torch.as_tensor(eflux).to(device=dev, dtype=torch.float64)
+            if tuple(e.shape) != tuple(f.shape):
+                raise ValueError("eflux %s and flux %s differ in shape" % (tuple(e.shape), tuple(f.shape)))
+            ok = torch.isfinite(e) & (e != 0.0) & torch.isfinite(f)
+            w = torch.where(ok, 1.0 / (e * e), torch.zeros_like(e)).contiguous()
+        else:
+            fh, wh = check_match_args(flux, eflux, nobs, topk)
+            f, w = torch.as_tensor(fh).to(dev), torch.as_tensor(wh).to(dev)
+        return f, w
+
     def match(self, flux, eflux, topk=1, return_all=False, npoly=0):
         """flux, eflux [N, nobs] on ``obs_wave`` (host arrays or device tensors; eflux zero or not finite, or a flux that is not
         finite: the pixel does not count) -> dict: ``index`` int32 [N, topk] (-1: no such template), ``chisq`` [N, topk] ascending
@@ -216,18 +302,7 @@ class TemplateBank(object):
             raise RuntimeError("the bank is empty: call build(theta) or lattice(steps, ...) first")
         eng = self.predictor.anns.engine
         torch, dev, nobs = eng.torch, eng.device, len(self.obs_wave)
-        if isinstance(flux, torch.Tensor) or isinstance(eflux, torch.Tensor):
-            if not (1 <= int(topk) <= _lib.TMATCH_MAX_TOPK):
-                raise ValueError("topk must be 1 .. %d, got %r" % (_lib.TMATCH_MAX_TOPK, topk))
-            f = torch.as_tensor(flux).to(device=dev, dtype=torch.float32).reshape(-1, nobs).contiguous()
-            e = torch.as_tensor(eflux).to(device=dev, dtype=torch.float64)
-            if tuple(e.shape) != tuple(f.shape):
-                raise ValueError("eflux %s and flux %s differ in shape" % (tuple(e.shape), tuple(f.shape)))
-            ok = torch.isfinite(e) & (e != 0.0) & torch.isfinite(f)
-            w = torch.where(ok, 1.0 / (e * e), torch.zeros_like(e)).contiguous()
-        else:
-            fh, wh = check_match_args(flux, eflux, nobs, topk)
-            f, w = torch.as_tensor(fh).to(dev), torch.as_tensor(wh).to(dev)
+        f, w = self._device_inputs(flux, eflux, topk)
         N, M, k = f.shape[0], len(self), int(topk)
         if self._handle is not None and P > self._handle.max_poly:
             self.close()                                             # (the workspace grows only once a polynomial is asked for)
@@ -258,7 +333,77 @@ class TemplateBank(object):
             out["all"] = every
         return out
 
+    def match_pairs(self, flux, eflux, topk=1, primaries=4, shortlist=None, return_all=False):
+        """The ``topk`` PAIRS of templates (a, b) that fit each star best with both amplitudes free,
+        chi^2 = min over (alpha, beta) of sum_p w_p (flux_p - alpha m_a - beta m_b)^2: starting points for ``OptFit.fit_binary``
+        (``OptFit.fit_binary_from_bank`` runs it from them).  flux, eflux as ``match``'s.  The primary a runs over ``primaries`` <= 16
+        templates per star, the secondary b over the whole bank.  ``shortlist`` int [N, primaries] names each star's primaries; by
+        default it is ``match(topk=primaries, npoly=1)['index']``, the single templates that fit best with a free scale
+        (``primaries`` <= 8 then), whose -1 slots are passed through.  In a shortlist of the caller's an index outside the bank and
+        a template named twice for one star become -1.
+
+        Returns a dict: ``index_a``, ``index_b`` int32 [N, topk] (-1: no such pair), ``chisq`` [N, topk] ascending (+inf there),
+        ``scale`` = alpha + beta and ``ratio`` = beta / (alpha + beta) [N, topk] (NaN there) -- ``fit_binary``'s ``coef[:, 0]`` and
+        ``ratio`` --, ``pars_a``, ``pars_b`` [N, topk, 8] the bank's theta rows, ``npix``, ``shortlist`` [N, primaries] as searched,
+        ``single_chisq`` [N], the best one-template-and-scale chi^2 of the same pixels (what a binary's chi^2 is compared with; +inf
+        if no template fits), and with ``return_all`` ``all`` [N, primaries, M], every pair's chi^2 (row j: primary
+        ``shortlist[:, j]``).  THE HOST ORDERS EACH LISTED PAIR SO THAT A IS THE BRIGHTER: ``ratio`` <= 0.5, whichever of the two the
+        shortlist held; the order of the list, ascending in (chi^2, slot of the shortlist, index of the other template), is the
+        device's.
+
+        A pair is left out (NaN in ``all``): the same template twice; a template that is not finite at a counting pixel; two
+        templates that are collinear over the star's pixels (1 - cos^2 <= 2^-20); a fit with an amplitude that is not positive (one
+        template fits as well); a pair that an earlier slot of the shortlist lists already.  A star without a counting pixel lists
+        nothing.  No continuum polynomial beyond the constant scale.
+
+        The stars are walked in blocks sized so that the moments' workspace on the device (16 bytes per star and template) stays
+        under 256 MB, and never more than ``max_stars`` at a time."""
+        if self.templates is None:
+            raise RuntimeError("the bank is empty: call build(theta) or lattice(steps, ...) first")
+        M = len(self)
+        k, kA, sl = check_pair_args(topk, primaries, M, shortlist)
+        eng = self.predictor.anns.engine
+        torch, dev, nobs = eng.torch, eng.device, len(self.obs_wave)
+        f, w = self._device_inputs(flux, eflux, k)
+        N = f.shape[0]
+        single = self.match(flux, eflux, topk=kA if sl is None else 1, npoly=1)
+        if sl is None:
+            sl = np.ascontiguousarray(single["index"], dtype=np.int32)
+        elif sl.shape[0] != N:
+            raise ValueError("shortlist must be [%d, %d], got %s" % (N, kA, sl.shape))
+        block = int(max(1, min(self.max_stars, PAIR_WORKSPACE_BYTES // (16 * M))))
+        h = self._pair_handle
+        if h is not None and (h.max_primaries < kA or h.max_stars < min(block, N) or h.max_templates != M):
+            h.close()
+            h = self._pair_handle = None
+        if h is None:
+            h = self._pair_handle = TMatchHandle(block, M, dev, max_primaries=kA)
+        idx_a, idx_b = np.empty((N, k), dtype=np.int32), np.empty((N, k), dtype=np.int32)
+        chisq, amp = np.empty((N, k)), np.empty((N, k, 2))
+        every = np.empty((N, kA, M)) if return_all else None
+        cand = torch.as_tensor(sl).to(dev)
+        for s in range(0, N, block):
+            e_ = min(N, s + block)
+            a_d, b_d, c_d, m_d, e_d = h.match_pairs(self.templates, f[s:e_], w[s:e_], cand[s:e_].contiguous(), k, n=nobs, return_all=return_all)
+            idx_a[s:e_], idx_b[s:e_], chisq[s:e_], amp[s:e_] = a_d.cpu().numpy(), b_d.cpu().numpy(), c_d.cpu().numpy(), m_d.cpu().numpy()
+            if return_all:
+                every[s:e_] = e_d.cpu().numpy()
+        swap = amp[:, :, 1] > amp[:, :, 0]                           # A is the brighter
+        index_a, index_b = np.where(swap, idx_b, idx_a), np.where(swap, idx_a, idx_b)
+        bright, faint = np.where(swap, amp[:, :, 1], amp[:, :, 0]), np.where(swap, amp[:, :, 0], amp[:, :, 1])
+        scale = bright + faint
+        listed = (index_a >= 0)[:, :, None]
+        out = dict(index_a=index_a, index_b=index_b, chisq=chisq, scale=scale, ratio=faint / scale,
+                   pars_a=np.where(listed, self.theta[np.maximum(index_a, 0)], np.nan), pars_b=np.where(listed, self.theta[np.maximum(index_b, 0)], np.nan),
+                   npix=single["npix"], shortlist=sl, single_chisq=single["chisq"][:, 0].copy())
+        if return_all:
+            out["all"] = every
+        return out
+
     def close(self):
         if getattr(self, "_handle", None) is not None:
             self._handle.close()
             self._handle = None
+        if getattr(self, "_pair_handle", None) is not None:
+            self._pair_handle.close()
+            self._pair_handle = None

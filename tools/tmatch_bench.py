@@ -2,6 +2,7 @@
 the same card and numpy's direct sum on one CPU core.
 
     python tools/tmatch_bench.py [--stars 4096] [--nobs 3600] [--templates 4096,65536] [--topk 4] [--repeats 5] [--warmup 1] [--numpy-stars 8]
+                                 [--npoly P] [--pairs [--primaries 4]]
 
 The workload: tools/optfit_bench.py's SMLP 4-256-256-256-4096, 3600 observed pixels, stars drawn in the inner half of the label box,
 spectra from the model itself plus seeded noise at S/N 100.  The bank: a lattice of the four labels (4 per label for 4096 templates,
@@ -17,7 +18,14 @@ second topk.  numpy: sum w (f - m)^2 for `numpy-stars` stars against at most 409
 (the stars are the same spectra times the series 1.3, 0.25, -0.12, 0.06), beside the plain match of the same run: ms, star x
 templates / s, the share of the fp64 matrix rate over 2 n (3 P - 1) flop a pair, the ratio to the plain match and the yardstick
 (3 P - 1) / 2.  torch's route on the same card: the 3 P - 1 products as two fp64 matmuls in template blocks that fit half of the free
-memory, A from S by a gather, linalg.cholesky_ex, cholesky_solve, the quadratic form and topk (`--torch-repeats` calls)."""
+memory, A from S by a gather, linalg.cholesky_ex, cholesky_solve, the quadratic form and topk (`--torch-repeats` calls).
+
+`--pairs` also times payne_tmatch_match_pairs (`--primaries` per star, the single-template-with-scale search's best) on binaries mixed
+from the same clean spectra, 0.7 of star s and 0.3 of star s + 1, with the same noise: the call's ms between two events, star x pairs / s
+over N kA M pairs, and the share of the fp64 matrix rate over 2 n flop per (row, template) -- of the whole call, so a lower bound of the
+cross launch's own (a kernel trace splits the call into its three launches).  torch's route on the same card: the moments and the cross
+term as fp64 matmuls (the gathered operand w m_a materialised), the 2 x 2 algebra elementwise with the same rules, topk over each star's
+kA M pairs; its buffers are counted and reported."""
 import argparse
 import json
 import os
@@ -104,6 +112,35 @@ def torch_poly_form(torch, templates, f, w, x, P, topk, budget):
     return best_i, best_c, block
 
 
+def torch_pair_form(torch, templates, f, w, cand, topk):
+    """(flat idx [N, topk] = j M + b, chisq, bytes of its buffers): the pair search on torch's fp64 matmul, elementwise algebra and topk."""
+    N, n = f.shape
+    M, kA = templates.shape[0], cand.shape[1]
+    m = templates.double()
+    a1 = w * f.double()
+    c0 = (a1 * f.double()).sum(dim=1)
+    B, S = a1 @ m.T, w @ (m * m).T
+    ok = cand >= 0
+    a = cand.clamp(min=0).long()
+    G = (w[:, None, :] * m[a]).reshape(N * kA, n)
+    X = (G @ m.T).reshape(N, kA, M)
+    Sa, Ba = torch.gather(S, 1, a)[:, :, None], torch.gather(B, 1, a)[:, :, None]
+    Sb, Bb = S[:, None, :], B[:, None, :]
+    SS = Sa * Sb
+    D = SS - X * X
+    al, be = (Ba * Sb - Bb * X) / D, (Bb * Sa - Ba * X) / D
+    chi = c0[:, None, None] + al * (Sa * al + X * be - 2.0 * Ba) + be * (X * al + Sb * be - 2.0 * Bb)
+    cols = torch.arange(M, device=f.device)[None, None, :]
+    earlier = torch.zeros_like(chi, dtype=torch.bool)
+    for j in range(1, kA):
+        earlier[:, j] = (cols[:, 0] == a[:, :j, None]).any(dim=1)
+    good = ok[:, :, None] & (cols != a[:, :, None]) & ~earlier & (Sa > 0) & (Sb > 0) & (D > SS / 1048576.0) & (al > 0) & (be > 0) & torch.isfinite(chi)
+    chi = torch.where(good, chi, torch.full_like(chi, float("inf")))
+    c, i = torch.topk(chi.reshape(N, kA * M), topk, dim=1, largest=False)
+    nbytes = 8 * (m.numel() + a1.numel() + G.numel() + 2 * B.numel() + 6 * X.numel()) + 2 * X.numel()
+    return i, c, nbytes
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--stars", type=int, default=4096)
@@ -116,6 +153,8 @@ def main():
     ap.add_argument("--b-max", type=int, default=512)
     ap.add_argument("--npoly", type=int, default=0)
     ap.add_argument("--torch-repeats", type=int, default=2)
+    ap.add_argument("--pairs", action="store_true")
+    ap.add_argument("--primaries", type=int, default=4)
     args = ap.parse_args()
     import torch
     from optfit_bench import workload
@@ -182,6 +221,29 @@ def main():
             run.update(torch_poly_ms_median=tp_ms, torch_poly_ms_min=tp_min, torch_poly_template_block=int(tp_block), torch_poly_over_kernel_time=tp_ms / p_ms,
                        poly_top1_agree_with_torch=float((tp_idx[:, 0] == p_idx[:, 0].long()).double().mean().item()),
                        poly_max_abs_dchisq_top1=float((tp_c[:, 0] - p_chisq[:, 0]).abs().max().item()))
+        if args.pairs:
+            kA = args.primaries
+            fb_d = (0.7 * clean + 0.3 * torch.roll(clean, -1, dims=0) + (f_d - clean)).float().contiguous()
+            h1 = TMatchHandle(N, M, dev, max_poly=1)
+            x1 = torch.zeros(n, dtype=torch.float64, device=dev)
+            s_ms, _, (cand, s_chisq, _, _, _) = timed(torch, lambda: h1.match_poly(bank.templates, fb_d, w_d, x1, 1, kA, n=n), args.repeats, args.warmup)
+            h1.close()
+            hp = TMatchHandle(N, M, dev, max_primaries=kA)
+            q_ms, q_min, (ia, ib, q_chisq, amp, _) = timed(torch, lambda: hp.match_pairs(bank.templates, fb_d, w_d, cand, args.topk, n=n), args.repeats, args.warmup)
+            hp.close()
+            q_flop = 2.0 * n * N * kA * M
+            ratio = amp[:, 0].min(dim=1).values / amp[:, 0].sum(dim=1)
+            run.update(pairs_primaries=kA, pairs_shortlist_ms_median=s_ms, pairs_ms_median=q_ms, pairs_ms_min=q_min, pairs_star_pairs_per_s=N * kA * M / (q_ms * 1e-3),
+                       pairs_cross_flop_over_call_time_fraction_of_fp64_matrix_peak=q_flop / (q_ms * 1e-3) / FP64_MATRIX_PEAK,
+                       pairs_workspace_bytes=int(16 * N * M + 8 * N + 28 * 8 * N * kA * ((M + 127) // 128)), pairs_listed_top1=float((ib[:, 0] >= 0).double().mean().item()),
+                       pairs_chisq_below_single=float((q_chisq[:, 0] < s_chisq[:, 0]).double().mean().item()), pairs_median_ratio_top1=float(ratio.nanmedian().item()))
+            tq_ms, tq_min, (tq_i, tq_c, tq_bytes) = timed(torch, lambda: torch_pair_form(torch, bank.templates, fb_d, w_d, cand, args.topk), args.torch_repeats, 1)
+            j_of = (cand[:, :, None] == ia[:, None, :1]).float().argmax(dim=1)[:, 0]
+            run.update(torch_pairs_ms_median=tq_ms, torch_pairs_ms_min=tq_min, torch_pairs_buffer_bytes=int(tq_bytes), torch_pairs_over_kernel_time=tq_ms / q_ms,
+                       pairs_top1_agree_with_torch=float((tq_i[:, 0] == j_of * M + ib[:, 0].long()).double().mean().item()),
+                       pairs_max_abs_dchisq_top1=float((tq_c[:, 0] - q_chisq[:, 0]).abs().max().item()))
+            del fb_d, cand, ia, ib, q_chisq, amp, tq_i, tq_c
+            torch.cuda.empty_cache()
         out["runs"].append(run)
         h.close()
         bank.close()
