@@ -232,3 +232,60 @@ def test_invalid_arguments_leave_the_state_untouched(lib):
     torch.cuda.synchronize()
     assert np.all(state_of(h)["niter"] == 1)
     h.close()
+
+
+# ---- 6. timing=True of the four fits --------------------------------------------------------------------------------------------
+def timed_fit(g20, name):
+    """(the OptFit, its stars, the rows a star needs, a call of fit `name` taking timing=): the smallest end-to-end inputs of each fit's
+    own test, on a b_max that holds fewer rows than the stars need, so that they walk through the handle in at least two blocks."""
+    from thepayne_amd.fitting.optfit import OptFit
+    if name == "fit":                                                    # tests/test_lmfit_gpu.py's 37-pixel recovery of smlp
+        from test_lmfit import recovery_inputs
+        from test_lmfit_gpu import device_spectra
+        net, nntype, case, _ = recovery_inputs(g20, "smlp", 37, False)
+        fit, N = OptFit(net, nntype, case["obs_wave"], b_max=RECOVERY_BMAX), 5
+        flux = device_spectra(fit, case["truth"][:N])
+        return fit, N, 1 + 4, lambda **kw: fit.fit(flux, case["eflux"][:N], case["start"][:N], **kw)
+    if name == "fit_joint":
+        from test_contfit import ALT_STARS as S
+        from test_lmfit_poly import JOINT_CASES, joint_inputs
+        nobs, P, fit_vrad = JOINT_CASES[0]
+        net, nntype, case, coef, flux, x = joint_inputs(g20, nobs)
+        fit = OptFit(net, nntype, case["obs_wave"], b_max=RECOVERY_BMAX)
+        f32 = flux.astype(np.float32)
+        return fit, S, 1 + len(case["cols"]) + 3 * int(fit_vrad), lambda **kw: fit.fit_joint(f32, case["eflux"][:S], case["start"][:S], npoly=P, fit_vrad=fit_vrad, **kw)
+    if name == "fit_specphot":
+        from test_lmfit_phot import SP_CASES, specphot_inputs
+        from test_lmfit_phot_gpu import fitters
+        small = min(sorted(SP_CASES), key=lambda nm: (SP_CASES[nm]["which"] != "smlp") + SP_CASES[nm]["fit_vrad"] + len(SP_CASES[nm]["free"]) + SP_CASES[nm]["P"])   # the fewest parameters
+        inp = specphot_inputs(g20, small)
+        fit, sed = fitters(inp, small)
+        cfg = inp["cfg"]
+        return fit, len(inp["flux"]), 1 + inp["Km"] + 2 * int(cfg["fit_vrad"]), lambda **kw: fit.fit_specphot(
+            inp["flux"], inp["eflux"], inp["mags"], inp["emags"], inp["start"], inp["phot_start"], sed, free_phot=cfg["free"], npoly=cfg["P"],
+            fit_vrad=cfg["fit_vrad"], bounds=inp["bounds"], prior=inp["prior"], **kw)
+    nobs, tie, P = BINARY_CASES[0]
+    inp = binary_inputs(g20, nobs, tie, P)
+    fit = OptFit(inp["net"], inp["nntype"], inp["obs_wave"], b_max=RECOVERY_BMAX)
+    return fit, BINARY_PAIRS, 2 * (1 + inp["args"]["Ka"] + 2), lambda **kw: fit.fit_binary(inp["flux"], inp["eflux"], inp["start_a"], inp["start_b"], ratio=inp["q0"],
+                                                                                           tie=tie, npoly=P, **kw)
+
+
+@pytest.mark.parametrize("name", ("fit", "fit_joint", "fit_specphot", "fit_binary"))
+def test_timing_changes_no_result_and_times_every_step(g20, name):
+    """``timing=True`` puts event pairs round the steps of every iteration and sums them into ``fit.timing``: the arrays that come back
+    are those of ``timing=False`` byte for byte, and every step of the fit has a time."""
+    fit, N, rows, call = timed_fit(g20, name)
+    assert N > max(1, RECOVERY_BMAX // rows)                                                       # at least two blocks
+    plain = call(timing=False)
+    assert fit.timing is None
+    timed = call(timing=True)
+    assert sorted(timed) == sorted(plain) and timed["labels"] == plain["labels"]
+    for key in plain:
+        if key != "labels":
+            assert np.array_equal(np.asarray(timed[key]), np.asarray(plain[key]), equal_nan=True), (name, key)
+    tm = fit.timing
+    print("%s, %d stars: %s" % (name, N, tm))
+    assert sorted(tm) == sorted(["network", "broadening", "update", "iterations"] + (["sed"] if name == "fit_specphot" else []))
+    assert isinstance(tm["iterations"], int) and tm["iterations"] >= 1
+    assert all(np.isfinite(tm[k]) and tm[k] > 0.0 for k in tm if k != "iterations"), tm

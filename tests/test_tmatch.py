@@ -357,3 +357,36 @@ def test_match_and_fit_from_bank_argument_checks():
         F.fit_from_bank(flux, eflux, B, start=np.zeros((3, 8)))
     assert all(s in _lib.SYMBOLS for s in ("payne_tmatch_create", "payne_tmatch_match", "payne_tmatch_chunk", "payne_tmatch_destroy"))
     assert _lib.TMATCH_MAX_TOPK == 8
+
+
+def test_one_result_per_star_over_the_ranks():
+    """optfit.keep_best_rank, the rule of the three ``*_from_bank`` fits, on fabricated results of 4 stars at 3 ranks:
+    star 0  valid at every rank, chi^2 5, 3, 3: rank 1 replaces rank 0, and rank 2's equal chi^2 does not replace rank 1;
+    star 1  valid at rank 0, NAN at rank 1, SINGULAR with the lowest chi^2 at rank 2: neither replaces the valid one;
+    star 2  SINGULAR at rank 0, NAN at rank 1, no template at rank 2: rank 0's is kept;
+    star 3  SINGULAR at rank 0, valid with a higher chi^2 at rank 1 (which replaces it), no template at rank 2."""
+    from thepayne_amd.fitting import optfit
+    ok, sing, nan = _lib.LMFIT_CONVERGED, _lib.LMFIT_SINGULAR, _lib.LMFIT_NAN
+    index = np.array([[10, 11, 12], [20, 21, 22], [30, 31, -1], [40, 41, -1]], dtype=np.int32)
+    status = np.array([[ok, _lib.LMFIT_MAXITER, _lib.LMFIT_STALLED], [ok, nan, sing], [sing, nan, -9], [sing, ok, -9]], dtype=np.int32)
+    chisq = np.array([[5.0, 3.0, 3.0], [4.0, np.nan, 1.0], [2.0, np.nan, -9.0], [1.0, 9.0, -9.0]])
+    out = dict(optfit.empty_results(4, 2), pars=np.full((4, 8), np.nan), start_index=np.full(4, -1, dtype=np.int32),
+               start_rank=np.full(4, -1, dtype=np.int32))
+    asked = []
+
+    def fit_rank(sel, r):
+        asked.append((r, sel.tolist()))
+        return dict(status=status[sel, r], chisq=chisq[sel, r], pars=np.tile((100.0 * r + sel)[:, None], (1, 8)), niter=np.full(len(sel), 7, dtype=np.int32))
+
+    def record(dst, r):
+        out["start_index"][dst] = index[dst, r]
+    assert optfit.keep_best_rank(index, out, ("pars", "chisq", "status"), fit_rank, record) is out
+    assert asked == [(0, [0, 1, 2, 3]), (1, [0, 1, 2, 3]), (2, [0, 1])]                              # a star without a template of a rank is not fitted there
+    assert out["start_rank"].tolist() == [1, 0, 0, 1] and out["start_index"].tolist() == [11, 20, 30, 41]
+    assert out["status"].tolist() == [_lib.LMFIT_MAXITER, ok, sing, ok] and out["chisq"].tolist() == [3.0, 4.0, 2.0, 9.0]
+    assert np.array_equal(out["pars"], np.tile(np.array([100.0, 1.0, 2.0, 103.0])[:, None], (1, 8)))
+    assert np.all(out["niter"] == 0) and np.all(np.isnan(out["fisher"]))                             # only the keys named are written
+    # no template at any rank: nothing is fitted and the star stays as it was allocated
+    out = dict(optfit.empty_results(1, 2), start_rank=np.full(1, -1, dtype=np.int32))
+    optfit.keep_best_rank(np.full((1, 3), -1, dtype=np.int32), out, ("chisq", "status"), None, None)
+    assert out["start_rank"][0] == -1 and out["status"][0] == nan and np.isnan(out["chisq"][0])

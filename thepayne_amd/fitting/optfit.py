@@ -34,7 +34,6 @@ make of that.
 q and the polynomial in one fit of chi^2 = sum w (flux - p [(1 - q) m_A + q m_B])^2.  Its update, payne_lmfit_update_pair, reads both
 components' rows and mixes them in registers (csrc/lmfit_pair_core.hpp).
 """
-import collections
 import ctypes as C
 
 import numpy as np
@@ -53,6 +52,40 @@ VRAD_BOUND = 500.0                                   # km/s: the default box of 
 def fitted_columns(n_labels, fit_vrad):
     """The columns of getspec's eight that are fitted: the network's labels, then Vrad."""
     return [0, 1, 2, 3] + ([6] if n_labels == 5 else []) + ([4] if fit_vrad else [])
+
+
+def _npoly_int(npoly, least):
+    """``npoly`` as an int: an integer (no bool) of at least ``least``."""
+    if isinstance(npoly, bool) or int(npoly) != npoly or int(npoly) < least:
+        raise ValueError("npoly must be an integer >= %d, got %r" % (least, npoly))
+    return int(npoly)
+
+
+def _coef_array(coef, N, P):
+    """Starting coefficients as fp64 [N, P], finite."""
+    coef = np.atleast_2d(np.asarray(coef.cpu() if hasattr(coef, "cpu") else coef, dtype=np.float64))     # (ContinuumFit's may be a device tensor)
+    if coef.shape != (N, P):
+        raise ValueError("coef must be [%d, %d], got %s" % (N, P, coef.shape))
+    if not np.all(np.isfinite(coef)):
+        raise ValueError("coef is not finite")
+    return coef
+
+
+def _named_bounds(bounds, names, lo, hi, what, elsewhere=None):
+    """``bounds`` = {name: (lo, hi)} written into the box lo, hi [K] of the parameters ``names``.  ``elsewhere``: (a name whose box is
+    not set here, where it is set)."""
+    if not isinstance(bounds, dict):
+        raise ValueError("bounds must be a dict {name: (lo, hi)} over %s" % (names,))
+    for name, (a, b) in bounds.items():
+        if name not in names or (elsewhere is not None and name == elsewhere[0]):
+            have = ", ".join(n for n in names if elsewhere is None or n != elsewhere[0])
+            raise ValueError("bounds: %r is not a fitted %s (%s)%s" % (name, what, have, "" if elsewhere is None else " (%s's box is %s)" % elsewhere))
+        lo[names.index(name)], hi[names.index(name)] = float(a), float(b)
+
+
+def _check_box(lo, hi, what, each):
+    if not (np.all(np.isfinite(lo)) and np.all(np.isfinite(hi)) and np.all(lo < hi)):
+        raise ValueError("%s: lo < hi, both finite, for every %s" % (what, each))
 
 
 def check_fit_args(flux, eflux, start, nobs, n_labels, xmin, xmax, fit_vrad=False, bounds=None, vrad_step=0.25, check_every=4, **opts):
@@ -80,18 +113,13 @@ def check_fit_args(flux, eflux, start, nobs, n_labels, xmin, xmax, fit_vrad=Fals
     hi = np.concatenate([np.asarray(xmax, dtype=np.float64)[:n_labels], [VRAD_BOUND] if fit_vrad else []])
     if bounds is not None:
         if isinstance(bounds, dict):
-            names = [THETA_SPEC_COLS[c] for c in cols]
-            for name, (a, b) in bounds.items():
-                if name not in names:
-                    raise ValueError("bounds: %r is not a fitted column (%s)" % (name, ", ".join(names)))
-                lo[names.index(name)], hi[names.index(name)] = float(a), float(b)
+            _named_bounds(bounds, [THETA_SPEC_COLS[c] for c in cols], lo, hi, "column")
         else:
             bd = np.asarray(bounds, dtype=np.float64)
             if bd.shape != (K, 2):
                 raise ValueError("bounds must be [%d, 2] or a dict, got %s" % (K, bd.shape))
             lo, hi = bd[:, 0].copy(), bd[:, 1].copy()
-    if not (np.all(np.isfinite(lo)) and np.all(np.isfinite(hi)) and np.all(lo < hi)):
-        raise ValueError("bounds: lo < hi, both finite, for every fitted column")
+    _check_box(lo, hi, "bounds", "fitted column")
     if not (np.isfinite(vrad_step) and vrad_step > 0.0):
         raise ValueError("vrad_step must be positive")
     if int(check_every) < 1:
@@ -115,18 +143,12 @@ def check_joint_args(flux, eflux, start, nobs, n_labels, xmin, xmax, npoly=4, co
     polynomial's.  Returns (flux, eflux, start, lo [K], hi [K], opts dict, coef fp64 [N, npoly] or None, clip dict) with
     K = K_m + npoly, the coefficients' box behind the fitted columns'."""
     flux, eflux, start, lo, hi, o = check_fit_args(flux, eflux, start, nobs, n_labels, xmin, xmax, **fit_args)
-    if isinstance(npoly, bool) or int(npoly) != npoly or int(npoly) < 1:
-        raise ValueError("npoly must be an integer >= 1, got %r" % (npoly,))
-    P, Km = int(npoly), len(lo)
+    P, Km = _npoly_int(npoly, 1), len(lo)
     if Km + P > _lib.LMFIT_MAX_K:
         raise ValueError("%d fitted columns and npoly = %d are %d parameters; at most %d (one 16 x 16 tile holds a star's normal equations)"
                          % (Km, P, Km + P, _lib.LMFIT_MAX_K))
     if coef is not None:
-        coef = np.atleast_2d(np.asarray(coef.cpu() if hasattr(coef, "cpu") else coef, dtype=np.float64))     # (ContinuumFit's may be a device tensor)
-        if coef.shape != (flux.shape[0], P):
-            raise ValueError("coef must be [%d, %d], got %s" % (flux.shape[0], P, coef.shape))
-        if not np.all(np.isfinite(coef)):
-            raise ValueError("coef is not finite")
+        coef = _coef_array(coef, flux.shape[0], P)
     clip = dict(clip or {})
     unknown = sorted(set(clip) - {"nclip", "kappa", "rescale"})
     if unknown:
@@ -139,8 +161,7 @@ def check_joint_args(flux, eflux, start, nobs, n_labels, xmin, xmax, npoly=4, co
         cb = np.asarray(coef_bounds, dtype=np.float64)
         if cb.shape != (P, 2):
             raise ValueError("coef_bounds must be [%d, 2], got %s" % (P, cb.shape))
-        if not (np.all(np.isfinite(cb)) and np.all(cb[:, 0] < cb[:, 1])):
-            raise ValueError("coef_bounds: lo < hi, both finite, for every coefficient")
+        _check_box(cb[:, 0], cb[:, 1], "coef_bounds", "coefficient")
     return flux, eflux, start, np.concatenate([lo, cb[:, 0]]), np.concatenate([hi, cb[:, 1]]), o, coef, clip
 
 
@@ -158,10 +179,9 @@ def check_specphot_args(flux, eflux, mags, emags, start, phot_start, nobs, n_lab
     free = [free_phot] if isinstance(free_phot, str) else list(free_phot)
     if len(set(free)) != len(free) or any(f not in pnames[4:] for f in free):
         raise ValueError("free_phot must name parameters among %s, each once; got %r" % (pnames[4:], free))
-    if isinstance(npoly, bool) or int(npoly) != npoly or int(npoly) < 0:
-        raise ValueError("npoly must be an integer >= 0, got %r" % (npoly,))
+    P = _npoly_int(npoly, 0)
     cols = fitted_columns(n_labels, fit_vrad)
-    Km, Kp, P = len(cols), len(free), int(npoly)
+    Km, Kp = len(cols), len(free)
     K = Km + Kp + P
     if K > _lib.LMFIT_MAX_K:
         raise ValueError("%d fitted columns of the spectrum, %d photometric parameters and npoly = %d are %d parameters; at most %d (one 16 x 16 "
@@ -195,14 +215,8 @@ def check_specphot_args(flux, eflux, mags, emags, start, phot_start, nobs, n_lab
     if not np.all(lo[:4] < hi[:4]):
         raise ValueError("the spectral and the photometric networks' ranges of %s do not overlap" % names[int(np.flatnonzero(~(lo[:4] < hi[:4]))[0])])
     if bounds is not None:
-        if not isinstance(bounds, dict):
-            raise ValueError("bounds must be a dict {name: (lo, hi)} over %s" % (names,))
-        for name, (a, b) in bounds.items():
-            if name not in names:
-                raise ValueError("bounds: %r is not a fitted parameter (%s)" % (name, ", ".join(names)))
-            lo[names.index(name)], hi[names.index(name)] = float(a), float(b)
-    if not (np.all(np.isfinite(lo)) and np.all(np.isfinite(hi)) and np.all(lo < hi)):
-        raise ValueError("bounds: lo < hi, both finite, for every fitted parameter")
+        _named_bounds(bounds, names, lo, hi, "parameter")
+    _check_box(lo, hi, "bounds", "fitted parameter")
     if "Av" in free and not hi[names.index("Av")] < sedfit.AV_MAX:
         raise ValueError("the upper Av bound must be below %g: the model jumps there" % sedfit.AV_MAX)
     sed_col = np.full(K, -1, dtype=np.int32)
@@ -252,9 +266,7 @@ def check_binary_args(flux, eflux, start_a, start_b, nobs, n_labels, xmin, xmax,
         tied.append(cnames.index(name))
     if len(set(tied)) != len(tied):
         raise ValueError("tie names a label twice: %r" % (tie,))
-    if isinstance(npoly, bool) or int(npoly) != npoly or int(npoly) < 0:
-        raise ValueError("npoly must be an integer >= 0, got %r" % (npoly,))
-    P = int(npoly)
+    P = _npoly_int(npoly, 0)
     free_b = [k for k in range(Ka) if k not in tied]
     Kl = Ka + len(free_b)
     K = Kl + 1 + P
@@ -270,9 +282,7 @@ def check_binary_args(flux, eflux, start_a, start_b, nobs, n_labels, xmin, xmax,
     if coef is not None:
         if P == 0:
             raise ValueError("coef belongs to the polynomial; npoly is 0")
-        coef = np.atleast_2d(np.asarray(coef.cpu() if hasattr(coef, "cpu") else coef, dtype=np.float64))
-        if coef.shape != (N, P) or not np.all(np.isfinite(coef)):
-            raise ValueError("coef must be [%d, %d] and finite, got %s" % (N, P, coef.shape))
+        coef = _coef_array(coef, N, P)
     ia = np.array(list(range(Ka)) + [-1] * len(free_b), dtype=np.int32)
     ib = np.array([k if k in tied else -1 for k in range(Ka)] + free_b, dtype=np.int32)
     b_pos = np.array([k if k in tied else Ka + free_b.index(k) for k in range(Ka)], dtype=np.int64)
@@ -280,27 +290,40 @@ def check_binary_args(flux, eflux, start_a, start_b, nobs, n_labels, xmin, xmax,
     lo = np.concatenate([lo_c, lo_c[free_b], [rb[0]], np.full(P, -COEF_BOUND)])
     hi = np.concatenate([hi_c, hi_c[free_b], [rb[1]], np.full(P, COEF_BOUND)])
     if bounds is not None:
-        if not isinstance(bounds, dict):
-            raise ValueError("bounds must be a dict {name: (lo, hi)} over %s" % (names,))
-        for name, (a, b) in bounds.items():
-            if name not in names or name == "ratio":
-                raise ValueError("bounds: %r is not one of %s (the ratio's box is ratio_bounds)" % (name, ", ".join(n for n in names if n != "ratio")))
-            lo[names.index(name)], hi[names.index(name)] = float(a), float(b)
-    if not (np.all(np.isfinite(lo)) and np.all(np.isfinite(hi)) and np.all(lo < hi)):
-        raise ValueError("bounds: lo < hi, both finite, for every fitted parameter")
+        _named_bounds(bounds, names, lo, hi, "parameter", elsewhere=("ratio", "ratio_bounds"))
+    _check_box(lo, hi, "bounds", "fitted parameter")
     return dict(flux=flux, eflux=eflux, start_a=start_a, start_b=start_b, ratio=ratio, coef=coef, opts=o, cols=cols, Ka=Ka, Kl=Kl, P=P, ia=ia, ib=ib,
                 b_pos=b_pos, names=names, lo=lo, hi=hi)
 
 
-PhotBlock = collections.namedtuple("PhotBlock", "sed pars x0 phot_idx sed_col obs pw mu sigma")
-PhotBlock.__doc__ = """The photometric inputs of one block of stars in ``OptFit._fit_block``:
-    sed       the ``SEDFit``
-    pars      fp64 [nb, ncol] on the device: the photometric rows at the start; the fitted columns are overwritten from x_trial every iteration
-    x0        host [nb, Kp]: the start of the free photometric-only parameters
-    phot_idx  int64 [Kp] on the device: their columns of the row
-    sed_col   host int32 [K]: the column of the row that handle parameter k is, or -1
-    obs, pw   fp64 [nb, F] on the device: the magnitudes and 1 / sigma^2 (0: the filter does not count)
-    mu, sigma fp64 [nb, K] on the device, or both None: the Gaussian priors"""
+def empty_results(N, K):
+    """The result arrays every fit has, for N stars that no fit has reached yet: chisq and fisher NaN, status NAN, niter and at_bound 0."""
+    return dict(chisq=np.full(N, np.nan), fisher=np.full((N, K, K), np.nan), status=np.full(N, _lib.LMFIT_NAN, dtype=np.int32),
+                niter=np.zeros(N, dtype=np.int32), at_bound=np.zeros(N, dtype=np.uint32))
+
+
+def keep_best_rank(index, out, per_star, fit_rank, record):
+    """One result per star over the ranks of a bank search.  ``index`` [N, k]: < 0 where a star has no template of that rank.
+    ``fit_rank(sel, r)``: the result dict of the fit of stars ``sel`` started from rank r, called once per rank that any star has.  A
+    star takes the result of lowest chi^2 among those whose status is not NAN / SINGULAR, the lower rank on a tie, and rank 0's (its
+    first) if none qualifies: the keys ``per_star`` of ``out`` and ``start_rank`` are written, and ``record(dst, r)`` records the starts
+    of the stars ``dst`` that took rank r.  Returns ``out``."""
+    def valid(status):
+        return (status != _lib.LMFIT_NAN) & (status != _lib.LMFIT_SINGULAR)
+    for r in range(index.shape[1]):
+        sel = np.flatnonzero(index[:, r] >= 0)
+        if len(sel) == 0:
+            continue
+        res = fit_rank(sel, r)
+        held = out["start_rank"][sel] >= 0
+        held_valid = held & valid(out["status"][sel])
+        take = ~held | (valid(res["status"]) & (~held_valid | (res["chisq"] < out["chisq"][sel])))
+        dst = sel[take]
+        for name in per_star:
+            out[name][dst] = res[name][take]
+        out["start_rank"][dst] = r
+        record(dst, r)
+    return out
 
 
 class _DeviceArray(object):
@@ -348,14 +371,24 @@ class LMHandle(object):
         """x_trial [B, K]: a view of the handle's own memory, valid in stream order."""
         return self._trial[:self.B]
 
+    def _check_blocks(self, blocks, flux, w, x=None, P=0):
+        """What the four updates ask of the tensors they share: every (rows, r) of ``blocks`` contiguous fp32 [B, r, n] (r None: any
+        number of rows), flux contiguous fp32 [B, n], w contiguous fp64 [B, n] and, with P > 0, x contiguous fp64 [n].  Returns n."""
+        torch, B, n = self.torch, self.B, blocks[0][0].shape[-1]
+        need_x = P > 0
+        if any(t.dim() != 3 or t.shape[0] != B or t.shape[2] != n or (r is not None and t.shape[1] != r) for t, r in blocks) \
+                or tuple(flux.shape) != (B, n) or tuple(w.shape) != (B, n) or (need_x and (x is None or tuple(x.shape) != (n,))):
+            raise ValueError("rows %s, flux and w [%d, n]%s; got %s, %s, %s, %s"
+                             % (" and ".join("[%d, %s, n]" % (B, "any" if r is None else r) for _, r in blocks), B, ", x [n]" if need_x else "",
+                                [tuple(t.shape) for t, _ in blocks], tuple(flux.shape), tuple(w.shape), None if x is None else tuple(x.shape)))
+        f32, f64 = [t for t, _ in blocks] + [flux], [w] + ([x] if need_x else [])
+        if any(a.dtype != torch.float32 or not a.is_contiguous() for a in f32) or any(a.dtype != torch.float64 or not a.is_contiguous() for a in f64):
+            raise ValueError("rows and flux contiguous fp32, w and x contiguous fp64")
+        return n
+
     def update(self, rows, flux, w):
         """rows fp32 [B, 1 + K, n] (the model, then its derivatives), flux fp32 [B, n], w fp64 [B, n]: device tensors."""
-        B, n = self.B, rows.shape[-1]
-        if tuple(rows.shape) != (B, 1 + self.K, n) or tuple(flux.shape) != (B, n) or tuple(w.shape) != (B, n):
-            raise ValueError("rows [%d, %d, n], flux and w [%d, n]; got %s, %s, %s" % (B, 1 + self.K, B, tuple(rows.shape), tuple(flux.shape), tuple(w.shape)))
-        torch = self.torch
-        if rows.dtype != torch.float32 or flux.dtype != torch.float32 or w.dtype != torch.float64 or not (rows.is_contiguous() and flux.is_contiguous() and w.is_contiguous()):
-            raise ValueError("rows and flux contiguous fp32, w contiguous fp64")
+        n = self._check_blocks([(rows, 1 + self.K)], flux, w)
         rc = self.lib.payne_lmfit_update(self._h, rows.data_ptr(), n, flux.data_ptr(), w.data_ptr(), n, n, self._stream())
         if rc != 0:
             raise RuntimeError("payne_lmfit_update failed (%d)" % rc)
@@ -364,16 +397,10 @@ class LMHandle(object):
         """The update for model x polynomial, the handle's last P parameters the Chebyshev coefficients (payne_lmfit_update_poly):
         rows fp32 [B, 1 + K - P, n] (the un-normalised model, then its derivatives), flux fp32 [B, n], w fp64 [B, n], x fp64 [n]
         (``contfit.abscissa``): device tensors."""
-        B, n, P = self.B, rows.shape[-1], int(P)
+        P = int(P)
         if not 1 <= P <= self.K:
             raise ValueError("P must be 1 .. %d, got %d" % (self.K, P))
-        if tuple(rows.shape) != (B, 1 + self.K - P, n) or tuple(flux.shape) != (B, n) or tuple(w.shape) != (B, n) or tuple(x.shape) != (n,):
-            raise ValueError("rows [%d, %d, n], flux and w [%d, n], x [n]; got %s, %s, %s, %s"
-                             % (B, 1 + self.K - P, B, tuple(rows.shape), tuple(flux.shape), tuple(w.shape), tuple(x.shape)))
-        torch = self.torch
-        if rows.dtype != torch.float32 or flux.dtype != torch.float32 or w.dtype != torch.float64 or x.dtype != torch.float64 \
-                or not (rows.is_contiguous() and flux.is_contiguous() and w.is_contiguous() and x.is_contiguous()):
-            raise ValueError("rows and flux contiguous fp32, w and x contiguous fp64")
+        n = self._check_blocks([(rows, 1 + self.K - P)], flux, w, x, P)
         rc = self.lib.payne_lmfit_update_poly(self._h, P, rows.data_ptr(), n, flux.data_ptr(), w.data_ptr(), n, x.data_ptr(), n, self._stream())
         if rc != 0:
             raise RuntimeError("payne_lmfit_update_poly failed (%d)" % rc)
@@ -384,23 +411,19 @@ class LMHandle(object):
         w, x as ``update_poly`` takes them (x None for P = 0); sed_col [K] host ints; mags, obs, pw fp64 [B, F], dmags fp64
         [B, F, ncol] (``SEDFit.grad_device``'s at the trial point); mu, sigma fp64 [B, K] or neither: device tensors."""
         torch = self.torch
-        B, n, P, Kp, K = self.B, rows.shape[-1], int(P), int(Kp), self.K
+        B, P, Kp, K = self.B, int(P), int(Kp), self.K
         Km = K - Kp - P
         sed_col = np.ascontiguousarray(sed_col, dtype=np.int32)
         if P < 0 or Kp < 0 or Km < 0 or sed_col.shape != (K,):
             raise ValueError("P >= 0, Kp >= 0, P + Kp <= %d and sed_col [%d]; got P = %d, Kp = %d, sed_col %s" % (K, K, P, Kp, sed_col.shape))
+        n = self._check_blocks([(rows, 1 + Km)], flux, w, x, P)
         F = mags.shape[-1]
-        if tuple(rows.shape) != (B, 1 + Km, n) or tuple(flux.shape) != (B, n) or tuple(w.shape) != (B, n) or (P > 0 and (x is None or tuple(x.shape) != (n,))):
-            raise ValueError("rows [%d, %d, n], flux and w [%d, n], x [n]; got %s, %s, %s, %s"
-                             % (B, 1 + Km, B, tuple(rows.shape), tuple(flux.shape), tuple(w.shape), None if x is None else tuple(x.shape)))
         if dmags.dim() != 3 or tuple(dmags.shape[:2]) != (B, F) or any(tuple(a.shape) != (B, F) for a in (mags, obs, pw)):
             raise ValueError("mags, obs, pw [%d, F] and dmags [%d, F, ncol]; got %s, %s, %s, %s" % (B, B, tuple(mags.shape), tuple(obs.shape), tuple(pw.shape), tuple(dmags.shape)))
         if (mu is None) != (sigma is None) or (mu is not None and (tuple(mu.shape) != (B, K) or tuple(sigma.shape) != (B, K))):
             raise ValueError("mu and sigma [%d, %d], both or neither" % (B, K))
-        f32 = [rows, flux]
-        f64 = [w, mags, dmags, obs, pw] + ([x] if P > 0 else []) + ([mu, sigma] if mu is not None else [])
-        if any(a.dtype != torch.float32 or not a.is_contiguous() for a in f32) or any(a.dtype != torch.float64 or not a.is_contiguous() for a in f64):
-            raise ValueError("rows and flux contiguous fp32, every other tensor contiguous fp64")
+        if any(a.dtype != torch.float64 or not a.is_contiguous() for a in [mags, dmags, obs, pw] + ([mu, sigma] if mu is not None else [])):
+            raise ValueError("mags, dmags, obs, pw, mu and sigma contiguous fp64")
         rc = self.lib.payne_lmfit_update_phot(self._h, Km, Kp, P, rows.data_ptr(), n, flux.data_ptr(), w.data_ptr(), n, x.data_ptr() if P > 0 else None, n,
                                               F, dmags.shape[2], sed_col.ctypes.data, mags.data_ptr(), dmags.data_ptr(), obs.data_ptr(), pw.data_ptr(),
                                               None if mu is None else mu.data_ptr(), None if sigma is None else sigma.data_ptr(), self._stream())
@@ -412,22 +435,15 @@ class LMHandle(object):
         Kl = K - 1 - P that the components see, the ratio q and P >= 0 Chebyshev coefficients.  rows_a fp32 [B, 1 + Ka, n] and rows_b
         fp32 [B, 1 + Kb, n] (a component's model, then its derivatives), flux fp32 [B, n], w fp64 [B, n], x fp64 [n] (None for
         P = 0): device tensors; ia, ib [Kl] host ints: parameter k is derivative ia[k] of A and ib[k] of B, -1 for none."""
-        torch = self.torch
-        B, n, P, K = self.B, rows_a.shape[-1], int(P), self.K
+        P, K = int(P), self.K
         Kl = K - 1 - P
         ia, ib = np.ascontiguousarray(ia, dtype=np.int32), np.ascontiguousarray(ib, dtype=np.int32)
         if P < 0 or Kl < 0 or ia.shape != (Kl,) or ib.shape != (Kl,):
             raise ValueError("P >= 0, 1 + P <= %d and ia, ib [%d]; got P = %d, ia %s, ib %s" % (K, max(Kl, 0), P, ia.shape, ib.shape))
-        if rows_a.dim() != 3 or rows_b.dim() != 3 or rows_a.shape[0] != B or rows_b.shape[0] != B or rows_b.shape[2] != n \
-                or tuple(flux.shape) != (B, n) or tuple(w.shape) != (B, n) or (P > 0 and (x is None or tuple(x.shape) != (n,))):
-            raise ValueError("rows_a [%d, 1 + Ka, n], rows_b [%d, 1 + Kb, n], flux and w [%d, n], x [n]; got %s, %s, %s, %s, %s"
-                             % (B, B, B, tuple(rows_a.shape), tuple(rows_b.shape), tuple(flux.shape), tuple(w.shape), None if x is None else tuple(x.shape)))
+        n = self._check_blocks([(rows_a, None), (rows_b, None)], flux, w, x, P)
         Ka, Kb = rows_a.shape[1] - 1, rows_b.shape[1] - 1
         if Ka < 0 or Kb < 0 or np.any(ia < -1) or np.any(ia >= Ka) or np.any(ib < -1) or np.any(ib >= Kb) or np.any((ia < 0) & (ib < 0)):
             raise ValueError("ia in [-1, %d), ib in [-1, %d), not both -1; got %s, %s" % (Ka, Kb, ia.tolist(), ib.tolist()))
-        f32, f64 = [rows_a, rows_b, flux], [w] + ([x] if P > 0 else [])
-        if any(a.dtype != torch.float32 or not a.is_contiguous() for a in f32) or any(a.dtype != torch.float64 or not a.is_contiguous() for a in f64):
-            raise ValueError("rows_a, rows_b and flux contiguous fp32, w and x contiguous fp64")
         rc = self.lib.payne_lmfit_update_pair(self._h, Kl, P, ia.ctypes.data if Kl else None, ib.ctypes.data if Kl else None, rows_a.data_ptr(), Ka,
                                               rows_b.data_ptr(), Kb, n, flux.data_ptr(), w.data_ptr(), n, x.data_ptr() if P > 0 else None, n, self._stream())
         if rc != 0:
@@ -492,59 +508,90 @@ class OptFit(object):
         three steps of every iteration, summed into ``self.timing`` (ms; for tools/optfit_bench.py)."""
         if lsf is not None:
             raise NotImplementedError("OptFit with an LSF vector: the rows are not pushed through it (PayneSpecPredict.getgrad)")
-        P = self.predictor
-        anns, eng, D = P.anns, P.anns.engine, self.n_labels
+        anns, D = self.predictor.anns, self.n_labels
         flux, eflux, start, lo, hi, o = check_fit_args(flux, eflux, start, len(self.obs_wave), D, anns.xmin, anns.xmax, fit_vrad=fit_vrad,
                                                        bounds=bounds, vrad_step=vrad_step, check_every=check_every, **opts)
-        torch = eng.torch
-        N, nobs = flux.shape
+        N = flux.shape[0]
         cols = fitted_columns(D, fit_vrad)
-        K = len(cols)
         w = weights_from_errors(eflux)
-        P._bind(self.obs_wave)
-        step = max(1, eng.b_max // (1 + K + 2 * int(bool(fit_vrad))))
-        handle = LMHandle(K, min(step, N), eng.device, **o)
-        out = dict(pars=start.copy(), chisq=np.empty(N), npix=(w != 0.0).sum(axis=1), fisher=np.empty((N, K, K)), status=np.empty(N, dtype=np.int32),
-                   niter=np.empty(N, dtype=np.int32), at_bound=np.empty(N, dtype=np.uint32), labels=self.labels(fit_vrad))
-        self.timing = dict(network=0.0, broadening=0.0, update=0.0, iterations=0) if timing else None
-        try:
-            for s in range(0, N, step):
-                e = min(N, s + step)
-                res = self._fit_block(handle, flux[s:e], w[s:e], start[s:e], cols, lo, hi, bool(fit_vrad), float(vrad_step), int(check_every),
-                                      int(o["maxiter"]))
-                out["pars"][s:e][:, cols] = res["x_best"].cpu().numpy()
-                out["chisq"][s:e] = res["chisq"].cpu().numpy()
-                out["fisher"][s:e] = res["A"].cpu().numpy()
-                out["status"][s:e] = res["status"].cpu().numpy()
-                out["niter"][s:e] = res["niter"].cpu().numpy()
-                out["at_bound"][s:e] = res["at_bound"].cpu().numpy().astype(np.uint32)
-        finally:
-            handle.close()
+        out = dict(pars=start.copy(), npix=(w != 0.0).sum(axis=1), labels=self.labels(fit_vrad), **empty_results(N, len(cols)))
+
+        def block(handle, idx):
+            return start[idx][:, cols], start[idx], lambda rows, flux_d, w_d, mark: handle.update(rows, flux_d, w_d)
+
+        def place(idx, xb):
+            out["pars"][idx][:, cols] = xb                           # (idx is a slice here, so this writes through a view)
+        return self._fit_blocks(out, None, flux, w, lo, hi, o, block, place, cols=cols, fit_vrad=fit_vrad, vrad_step=vrad_step, check_every=check_every,
+                                timing=timing)
+
+    def _fit_blocks(self, out, sel, flux, w, lo, hi, opts, block, place, *, cols, fit_vrad, vrad_step, check_every, timing, nc=1, labels_of=None,
+                    vrad_of=None, steps=("network", "broadening", "update"), nan_results=False):
+        """The driver of every fit: the stars ``sel`` (indices; None: every star, and a block's ``idx`` is then a slice, so that
+        ``flux[idx]`` copies nothing) walk in blocks through one handle of K = len(lo) parameters, and what the handle
+        gives for a block goes into ``out`` -- chisq, fisher, status, niter and at_bound here, x_best [nb, K] through the fit's own
+        ``place(idx, x_best)``; ``err`` is added and ``out`` returned.  A block holds as many stars as ``b_max`` rows allow: a star
+        needs, for each of its ``nc`` components, the model's row, one per fitted column ``cols`` and two for a fitted Vrad.
+        ``block(handle, idx)`` gives the stars ``idx`` their ``_run_block`` arguments (x0, theta, update); ``labels_of``, ``vrad_of``,
+        ``steps`` are ``_run_block``'s, one component's by default.  ``nan_results``: x_best, fisher and chisq of a star whose status
+        is NAN are NaN (``fit_binary``).  ``timing``: the ``steps`` are timed and summed into ``self.timing``."""
+        eng, D = self.predictor.anns.engine, self.n_labels
+        fit_vrad = bool(fit_vrad)
+        if labels_of is None:
+            def labels_of(xt):
+                return xt[:, :D] if xt.shape[1] > D else xt
+
+            def vrad_of(xt):
+                return xt[:, D]
+        self.predictor._bind(self.obs_wave)
+        step = max(1, eng.b_max // (nc * (1 + len(cols) + 2 * int(fit_vrad))))
+        self.timing = dict([(name, 0.0) for name in steps], iterations=0) if timing else None
+        n = len(flux) if sel is None else len(sel)
+        if n:
+            handle = LMHandle(len(lo), min(step, n), eng.device, **opts)
+            try:
+                for s in range(0, n, step):
+                    idx = slice(s, min(n, s + step)) if sel is None else sel[s:s + step]
+                    x0, theta, update = block(handle, idx)
+                    res = self._run_block(handle, flux[idx], w[idx], x0, lo, hi, theta, labels_of, vrad_of if fit_vrad else None, update, len(cols),
+                                          float(vrad_step), int(check_every), int(opts["maxiter"]), steps)
+                    xb, st, fisher, chisq = (res[k].cpu().numpy() for k in ("x_best", "status", "A", "chisq"))
+                    if nan_results:
+                        nan = st == _lib.LMFIT_NAN
+                        xb[nan], fisher[nan], chisq[nan] = np.nan, np.nan, np.nan
+                    out["chisq"][idx] = chisq
+                    out["fisher"][idx] = fisher
+                    out["status"][idx] = st
+                    out["niter"][idx] = res["niter"].cpu().numpy()
+                    out["at_bound"][idx] = res["at_bound"].cpu().numpy().astype(np.uint32)
+                    place(idx, xb)
+            finally:
+                handle.close()
         out["err"] = crlb_from_fisher(out["fisher"])
         return out
 
-    def _fit_block(self, handle, flux, w, start, cols, lo, hi, fit_vrad, vrad_step, check_every, maxiter, coef=None, x=None, phot=None):
-        """One block of stars through the handle.  ``coef`` [nb, P] and ``x``: the handle's parameters are the fitted columns and then
-        the coefficients, and the update is ``update_poly`` on the abscissa ``x`` (``fit_joint``).  ``phot``: a ``PhotBlock``
-        (``fit_specphot``).  Its Kp parameters sit between the fitted columns and the coefficients; one more enqueued step an iteration
-        copies the fitted columns of the photometric rows from x_trial on the device and evaluates ``sed.grad_device`` there; the update
-        is ``update_phot``."""
-        P = self.predictor
-        eng, D, jac_net = P.anns.engine, self.n_labels, P._jacobian()
-        torch = eng.torch
-        nb, nobs, K = flux.shape[0], flux.shape[1], len(cols)
-        dev = eng.device
+    def _run_block(self, handle, flux, w, x0, lo, hi, theta, labels_of, vrad_of, update, Kc, vrad_step, check_every, maxiter, steps):
+        """One block of nb stars through the handle, from ``begin(x0, lo, hi)`` to ``result()``.  ``theta`` [nc * nb, 8]: getspec's
+        columns of every component at the start, the nc components stacked along the batch axis, as the rows are: rows [nc * nb, 1 + Kc,
+        nobs] holds a component's model, the derivatives by its labels and, with a fitted Vrad, by Vrad (a central difference of the
+        broadened model at Vrad +- ``vrad_step``).  ``labels_of(x_trial)``: the labels [nc * nb, D] the network is evaluated at;
+        ``vrad_of(x_trial)``: the fitted Vrad [nc * nb], None where Vrad is fixed.  They are two functions because a gather they
+        enqueue belongs to the step that uses it.  ``update(rows, flux_d, w_d, mark)`` issues the handle's update from the filled
+        rows, and calls ``mark()`` behind each further step it enqueues before that; ``steps`` names the timed steps in order."""
+        Pr = self.predictor
+        eng, D, jac_net = Pr.anns.engine, self.n_labels, Pr._jacobian()
+        torch, dev = eng.torch, eng.device
+        nobs, nr = flux.shape[1], theta.shape[0]
         flux_d = torch.as_tensor(np.ascontiguousarray(flux)).to(dev)
         w_d = torch.as_tensor(np.ascontiguousarray(w)).to(dev)
-        handle.begin(np.concatenate([start[:, cols]] + ([] if phot is None else [phot.x0]) + ([] if coef is None else [coef]), axis=1), lo, hi)
+        handle.begin(x0, lo, hi)
         xt = handle.trial()
-        # the theta blocks, uploaded once: the model's [nb], the derivative rows' [nb * D], and Vrad +- step's [2 nb]
-        th = np.full((nb, eng.ncols), np.nan)
-        th[:, :8] = start
+        # the theta blocks, uploaded once: the model's [nr], the derivative rows' [nr * D], and Vrad +- step's [2 nr]
+        th = np.full((nr, eng.ncols), np.nan)
+        th[:, :8] = theta
         th_y = torch.as_tensor(th).to(dev)
         th_j = th_y.repeat_interleave(D, dim=0)
-        th_pm = th_y.repeat(2, 1) if fit_vrad else None
-        rows = torch.empty((nb, 1 + K, nobs), dtype=torch.float32, device=dev)
+        th_pm = th_y.repeat(2, 1) if vrad_of is not None else None
+        rows = torch.empty((nr, 1 + Kc, nobs), dtype=torch.float32, device=dev)
         tm = self.timing
         marks = []
 
@@ -557,40 +604,27 @@ class OptFit(object):
         while it < maxiter:
             it += 1
             mark()
-            labels = xt[:, :D] if handle.K > D else xt
-            y, jac = jac_net.eval(labels)
+            y, jac = jac_net.eval(labels_of(xt))
             mark()
-            if fit_vrad:
-                v = xt[:, D]
+            if vrad_of is not None:
+                v = vrad_of(xt)
                 th_y[:, 4] = v
                 th_j[:, 4] = v.repeat_interleave(D)
-                th_pm[:nb, 4] = v + vrad_step
-                th_pm[nb:, 4] = v - vrad_step
+                th_pm[:nr, 4] = v + vrad_step
+                th_pm[nr:, 4] = v - vrad_step
                 pm = eng.smooth_batch(y.repeat(2, 1), th_pm, stage=2)
-                rows[:, K] = (pm[:nb] - pm[nb:]) / (2.0 * vrad_step)
+                rows[:, Kc] = (pm[:nr] - pm[nr:]) / (2.0 * vrad_step)
             rows[:, 0] = eng.smooth_batch(y, th_y, stage=2)
-            rows[:, 1:1 + D] = smooth_rows(eng, jac.reshape(nb * D, -1), th_j, 2).reshape(nb, D, nobs)
+            rows[:, 1:1 + D] = smooth_rows(eng, jac.reshape(nr * D, -1), th_j, 2).reshape(nr, D, nobs)
             mark()
-            if phot is not None:
-                Kp = phot.x0.shape[1]
-                phot.pars[:, :4] = xt[:, :4]
-                if Kp:
-                    phot.pars.index_copy_(1, phot.phot_idx, xt[:, K:K + Kp])
-                mags, dmags = phot.sed.grad_device(phot.pars)
-                mark()
-                handle.update_phot(rows, flux_d, w_d, x, 0 if coef is None else coef.shape[1], Kp, phot.sed_col, mags, dmags, phot.obs, phot.pw, phot.mu, phot.sigma)
-            elif coef is None:
-                handle.update(rows, flux_d, w_d)
-            else:
-                handle.update_poly(rows, flux_d, w_d, x, coef.shape[1])
+            update(rows, flux_d, w_d, mark)
             mark()
             if it % check_every == 0 and not bool((handle.status() == _lib.LMFIT_RUNNING).any().item()):
                 break
         res = handle.result()
         if tm is not None:
             torch.cuda.synchronize(dev)
-            steps = ("network", "broadening") + (() if phot is None else ("sed",)) + ("update",)   # a mark before each and one behind the last
-            for i in range(0, len(marks), len(steps) + 1):
+            for i in range(0, len(marks), len(steps) + 1):                                         # a mark before each step and one behind the last
                 for j, name in enumerate(steps):
                     tm[name] += marks[i + j].elapsed_time(marks[i + j + 1])
             tm["iterations"] += it
@@ -637,10 +671,9 @@ class OptFit(object):
         N, K = flux.shape[0], len(cols)
         cont = ContinuumFit(self.obs_wave, npoly=npoly, device=self.predictor.anns.engine.device, **(clip or {}))
         pars = start.copy()
-        out = dict(pars=start.copy(), chisq=np.full(N, np.nan), npix=np.zeros(N, dtype=np.int64), fisher=np.full((N, K, K), np.nan),
-                   status=np.full(N, _lib.LMFIT_NAN, dtype=np.int32), niter=np.zeros(N, dtype=np.int32), at_bound=np.zeros(N, dtype=np.uint32),
-                   labels=self.labels(fit_vrad), err=np.full((N, K), np.nan), coef=np.full((N, int(npoly)), np.nan),
-                   cont_status=np.full(N, _lib.CONTFIT_OK, dtype=np.int32), chisq_rounds=np.full((N, int(rounds)), np.nan))
+        out = dict(pars=start.copy(), npix=np.zeros(N, dtype=np.int64), labels=self.labels(fit_vrad), err=np.full((N, K), np.nan),
+                   coef=np.full((N, int(npoly)), np.nan), cont_status=np.full(N, _lib.CONTFIT_OK, dtype=np.int32),
+                   chisq_rounds=np.full((N, int(rounds)), np.nan), **empty_results(N, K))
         out["pars"][:, cols] = np.nan
         alive = np.ones(N, dtype=bool)
         for r in range(int(rounds)):
@@ -687,51 +720,47 @@ class OptFit(object):
         flux, eflux, start, lo, hi, o, coef, clip = check_joint_args(flux, eflux, start, len(self.obs_wave), D, anns.xmin, anns.xmax, npoly=npoly, coef=coef,
                                                                      clip=clip, fit_vrad=fit_vrad, bounds=bounds, coef_bounds=coef_bounds,
                                                                      vrad_step=vrad_step, check_every=check_every, **opts)
-        from .contfit import ContinuumFit, abscissa
-        torch = eng.torch
-        N, nobs = flux.shape
+        from .contfit import abscissa
+        N = flux.shape[0]
         cols = fitted_columns(D, fit_vrad)
         Km, P = len(cols), int(npoly)
-        K = Km + P
         w = weights_from_errors(eflux)
         cont_status = np.full(N, _lib.CONTFIT_OK, dtype=np.int32)
-        x = abscissa(self.obs_wave)
         if coef is None:
-            cont = ContinuumFit(self.obs_wave, npoly=P, device=eng.device, drop_clipped=True, **clip)
-            c = cont.fit(flux, eflux, self.model_spectra(start), normalise=bool(clip))
-            c = {k: v.cpu().numpy() for k, v in c.items()}            # (a device model gives device tensors)
-            coef, cont_status = c["coef"], c["status"].astype(np.int32)
-            if clip:                                                  # a counting pixel whose weight came back 0 under a positive polynomial was clipped
-                w = np.where((c["weights"] == 0.0) & (np.polynomial.chebyshev.chebval(x, np.nan_to_num(coef).T) > 0.0), 0.0, w)
-        good = (cont_status == _lib.CONTFIT_OK) | (cont_status == _lib.CONTFIT_NONPOSITIVE)
-        out = dict(pars=start.copy(), chisq=np.full(N, np.nan), npix=(w != 0.0).sum(axis=1), fisher=np.full((N, K, K), np.nan),
-                   status=np.full(N, _lib.LMFIT_NAN, dtype=np.int32), niter=np.zeros(N, dtype=np.int32), at_bound=np.zeros(N, dtype=np.uint32),
-                   labels=self.labels(fit_vrad) + ["pc_%d" % j for j in range(P)], coef=np.full((N, P), np.nan), cont_status=cont_status)
+            coef, cont_status, w = self._start_continuum(flux, eflux, self.model_spectra(start), P, clip, w)
+        out = dict(pars=start.copy(), npix=(w != 0.0).sum(axis=1), labels=self.labels(fit_vrad) + ["pc_%d" % j for j in range(P)],
+                   coef=np.full((N, P), np.nan), cont_status=cont_status, **empty_results(N, Km + P))
         out["pars"][:, cols] = np.nan
-        Pr._bind(self.obs_wave)
-        step = max(1, eng.b_max // (1 + Km + 2 * int(bool(fit_vrad))))
-        sel = np.flatnonzero(good)
-        self.timing = dict(network=0.0, broadening=0.0, update=0.0, iterations=0) if timing else None
-        if len(sel):
-            handle = LMHandle(K, min(step, len(sel)), eng.device, **o)
-            x_d = torch.as_tensor(x).to(eng.device)
-            try:
-                for s in range(0, len(sel), step):
-                    idx = sel[s:s + step]
-                    res = self._fit_block(handle, flux[idx], w[idx], start[idx], cols, lo, hi, bool(fit_vrad), float(vrad_step), int(check_every),
-                                          int(o["maxiter"]), coef=np.ascontiguousarray(coef[idx], dtype=np.float64), x=x_d)
-                    xb = res["x_best"].cpu().numpy()
-                    out["pars"][idx[:, None], np.asarray(cols)[None, :]] = xb[:, :Km]
-                    out["coef"][idx] = xb[:, Km:]
-                    out["chisq"][idx] = res["chisq"].cpu().numpy()
-                    out["fisher"][idx] = res["A"].cpu().numpy()
-                    out["status"][idx] = res["status"].cpu().numpy()
-                    out["niter"][idx] = res["niter"].cpu().numpy()
-                    out["at_bound"][idx] = res["at_bound"].cpu().numpy().astype(np.uint32)
-            finally:
-                handle.close()
-        out["err"] = crlb_from_fisher(out["fisher"])
-        return out
+        x_d = eng.torch.as_tensor(abscissa(self.obs_wave)).to(eng.device)
+
+        def block(handle, idx):
+            x0 = np.concatenate([start[idx][:, cols], np.ascontiguousarray(coef[idx], dtype=np.float64)], axis=1)
+            return x0, start[idx], lambda rows, flux_d, w_d, mark: handle.update_poly(rows, flux_d, w_d, x_d, P)
+
+        def place(idx, xb):
+            out["pars"][idx[:, None], np.asarray(cols)[None, :]] = xb[:, :Km]
+            out["coef"][idx] = xb[:, Km:]
+        return self._fit_blocks(out, self._with_continuum(cont_status), flux, w, lo, hi, o, block, place, cols=cols, fit_vrad=fit_vrad, vrad_step=vrad_step,
+                                check_every=check_every, timing=timing)
+
+    @staticmethod
+    def _with_continuum(cont_status):
+        """The stars a starting continuum fit left fit to go on with: status OK or NONPOSITIVE."""
+        return np.flatnonzero((cont_status == _lib.CONTFIT_OK) | (cont_status == _lib.CONTFIT_NONPOSITIVE))
+
+    def _start_continuum(self, flux, eflux, model, P, clip, w):
+        """The starting coefficients where the caller gave none: one ``ContinuumFit.fit`` of P coefficients against ``model`` (fp32
+        [N, nobs] on the device).  ``clip``: ``fit_joint``'s dict (empty: no clipping) -- the pixels the last solve dropped get weight 0
+        in ``w`` -- or None: ``ContinuumFit``'s own defaults and ``w`` as it is (``fit_binary``).  Returns (coef [N, P], cont_status
+        int32 [N], w)."""
+        from .contfit import ContinuumFit, abscissa
+        cont = ContinuumFit(self.obs_wave, npoly=P, device=self.predictor.anns.engine.device, **({} if clip is None else dict(drop_clipped=True, **clip)))
+        c = cont.fit(flux, eflux, model, normalise=bool(clip))
+        coef = c["coef"].cpu().numpy()                                # (a device model gives device tensors)
+        if clip:                                                      # a counting pixel whose weight came back 0 under a positive polynomial was clipped
+            positive = np.polynomial.chebyshev.chebval(abscissa(self.obs_wave), np.nan_to_num(coef).T) > 0.0
+            w = np.where((c["weights"].cpu().numpy() == 0.0) & positive, 0.0, w)
+        return coef, c["status"].cpu().numpy().astype(np.int32), w
 
     def fit_specphot(self, flux, eflux, mags, emags, start, phot_start, sed, free_phot=("logR", "Av"), npoly=0, coef=None, clip=None, fit_vrad=False,
                      bounds=None, coef_bounds=None, prior=None, vrad_step=0.25, check_every=4, timing=False, **opts):
@@ -775,65 +804,54 @@ class OptFit(object):
         c = check_specphot_args(flux, eflux, mags, emags, start, phot_start, len(self.obs_wave), D, anns.xmin, anns.xmax, sed.F, sed.xmin, sed.xmax,
                                 photscale=sed.photscale, free_phot=free_phot, npoly=npoly, coef=coef, clip=clip, fit_vrad=fit_vrad, bounds=bounds,
                                 coef_bounds=coef_bounds, prior=prior, vrad_step=vrad_step, check_every=check_every, **opts)
-        from .contfit import ContinuumFit, abscissa
+        from .contfit import abscissa
         torch = sed._setup()
-        if sed.device != eng.device:
-            raise ValueError("sed is on %s, the spectral network on %s" % (sed.device, eng.device))
+        dev = eng.device
+        if sed.device != dev:
+            raise ValueError("sed is on %s, the spectral network on %s" % (sed.device, dev))
         flux, eflux, start, coef, clip, o = c["flux"], c["eflux"], c["start"], c["coef"], c["clip"], c["opts"]
-        cols, Km, Kp, P, lo, hi = c["cols"], c["Km"], c["Kp"], c["P"], c["lo"], c["hi"]
-        K, N, ncol = Km + Kp + P, flux.shape[0], len(sed.names)
+        cols, Km, Kp, P, lo, hi, phot_cols = c["cols"], c["Km"], c["Kp"], c["P"], c["lo"], c["hi"], c["phot_cols"]
+        N = flux.shape[0]
         w = weights_from_errors(eflux)
         cont_status = np.full(N, _lib.CONTFIT_OK, dtype=np.int32)
-        x = abscissa(self.obs_wave)
         if P and coef is None:
-            cont = ContinuumFit(self.obs_wave, npoly=P, device=eng.device, drop_clipped=True, **clip)
-            cf = cont.fit(flux, eflux, self.model_spectra(start), normalise=bool(clip))
-            cf = {k: v.cpu().numpy() for k, v in cf.items()}
-            coef, cont_status = cf["coef"], cf["status"].astype(np.int32)
-            if clip:
-                w = np.where((cf["weights"] == 0.0) & (np.polynomial.chebyshev.chebval(x, np.nan_to_num(coef).T) > 0.0), 0.0, w)
-        good = (cont_status == _lib.CONTFIT_OK) | (cont_status == _lib.CONTFIT_NONPOSITIVE)
+            coef, cont_status, w = self._start_continuum(flux, eflux, self.model_spectra(start), P, clip, w)
         phot_pars = np.concatenate([start[:, :4], c["phot_start"]], axis=1)
-        out = dict(pars=start.copy(), chisq=np.full(N, np.nan), npix=(w != 0.0).sum(axis=1), fisher=np.full((N, K, K), np.nan),
-                   status=np.full(N, _lib.LMFIT_NAN, dtype=np.int32), niter=np.zeros(N, dtype=np.int32), at_bound=np.zeros(N, dtype=np.uint32),
-                   labels=list(c["names"]), coef=np.full((N, P), np.nan), cont_status=cont_status, phot_pars=phot_pars.copy(),
-                   nfilt=(c["pw"] != 0.0).sum(axis=1), mags_model=np.full((N, sed.F), np.nan))
+        out = dict(pars=start.copy(), npix=(w != 0.0).sum(axis=1), labels=list(c["names"]), coef=np.full((N, P), np.nan), cont_status=cont_status,
+                   phot_pars=phot_pars.copy(), nfilt=(c["pw"] != 0.0).sum(axis=1), mags_model=np.full((N, sed.F), np.nan),
+                   **empty_results(N, Km + Kp + P))
         out["pars"][:, cols] = np.nan
         out["phot_pars"][:, :4] = np.nan
-        out["phot_pars"][:, c["phot_cols"]] = np.nan
-        Pr._bind(self.obs_wave)
-        step = max(1, eng.b_max // (1 + Km + 2 * int(bool(fit_vrad))))
-        sel = np.flatnonzero(good)
-        self.timing = dict(network=0.0, broadening=0.0, sed=0.0, update=0.0, iterations=0) if timing else None
-        if len(sel):
-            dev = eng.device
-            handle = LMHandle(K, min(step, len(sel)), dev, **o)
-            x_d = torch.as_tensor(x).to(dev) if P else None
-            idx_d = torch.as_tensor(np.asarray(c["phot_cols"], dtype=np.int64)).to(dev)
-            try:
-                for s in range(0, len(sel), step):
-                    idx = sel[s:s + step]
-                    up = lambda a: torch.as_tensor(np.ascontiguousarray(a[idx], dtype=np.float64)).to(dev)   # noqa: E731
-                    phot = PhotBlock(sed=sed, pars=up(phot_pars), x0=phot_pars[idx][:, c["phot_cols"]], phot_idx=idx_d, sed_col=c["sed_col"], obs=up(c["obs"]),
-                                     pw=up(c["pw"]), mu=None if c["mu"] is None else up(c["mu"]), sigma=None if c["sigma"] is None else up(c["sigma"]))
-                    res = self._fit_block(handle, flux[idx], w[idx], start[idx], cols, lo, hi, bool(fit_vrad), float(vrad_step), int(check_every),
-                                          int(o["maxiter"]), coef=np.ascontiguousarray(coef[idx], dtype=np.float64) if P else None, x=x_d, phot=phot)
-                    xb = res["x_best"].cpu().numpy()
-                    out["pars"][idx[:, None], np.asarray(cols)[None, :]] = xb[:, :Km]
-                    out["phot_pars"][idx, :4] = xb[:, :4]
-                    if Kp:
-                        out["phot_pars"][idx[:, None], np.asarray(c["phot_cols"])[None, :]] = xb[:, Km:Km + Kp]
-                    out["coef"][idx] = xb[:, Km + Kp:]
-                    out["chisq"][idx] = res["chisq"].cpu().numpy()
-                    out["fisher"][idx] = res["A"].cpu().numpy()
-                    out["status"][idx] = res["status"].cpu().numpy()
-                    out["niter"][idx] = res["niter"].cpu().numpy()
-                    out["at_bound"][idx] = res["at_bound"].cpu().numpy().astype(np.uint32)
-                    out["mags_model"][idx] = sed.grad(out["phot_pars"][idx])[0]
-            finally:
-                handle.close()
-        out["err"] = crlb_from_fisher(out["fisher"])
-        return out
+        out["phot_pars"][:, phot_cols] = np.nan
+        x_d = torch.as_tensor(abscissa(self.obs_wave)).to(dev) if P else None
+        idx_d = torch.as_tensor(np.asarray(phot_cols, dtype=np.int64)).to(dev)
+
+        def block(handle, idx):
+            # on the device: the photometric rows (their fitted columns are overwritten from x_trial every iteration), the magnitudes
+            # and 1 / sigma^2, the priors
+            pars_d, obs_d, pw_d, mu_d, sigma_d = (None if a is None else torch.as_tensor(np.ascontiguousarray(a[idx], dtype=np.float64)).to(dev)
+                                                  for a in (phot_pars, c["obs"], c["pw"], c["mu"], c["sigma"]))
+            x0 = np.concatenate([start[idx][:, cols], phot_pars[idx][:, phot_cols]] + ([np.ascontiguousarray(coef[idx], dtype=np.float64)] if P else []), axis=1)
+
+            def update(rows, flux_d, w_d, mark):
+                xt = handle.trial()
+                pars_d[:, :4] = xt[:, :4]
+                if Kp:
+                    pars_d.index_copy_(1, idx_d, xt[:, Km:Km + Kp])
+                mags, dmags = sed.grad_device(pars_d)
+                mark()
+                handle.update_phot(rows, flux_d, w_d, x_d, P, Kp, c["sed_col"], mags, dmags, obs_d, pw_d, mu_d, sigma_d)
+            return x0, start[idx], update
+
+        def place(idx, xb):
+            out["pars"][idx[:, None], np.asarray(cols)[None, :]] = xb[:, :Km]
+            out["phot_pars"][idx, :4] = xb[:, :4]
+            if Kp:
+                out["phot_pars"][idx[:, None], np.asarray(phot_cols)[None, :]] = xb[:, Km:Km + Kp]
+            out["coef"][idx] = xb[:, Km + Kp:]
+            out["mags_model"][idx] = sed.grad(out["phot_pars"][idx])[0]
+        return self._fit_blocks(out, self._with_continuum(cont_status), flux, w, lo, hi, o, block, place, cols=cols, fit_vrad=fit_vrad, vrad_step=vrad_step,
+                                check_every=check_every, timing=timing, steps=("network", "broadening", "sed", "update"))
 
     def fit_from_bank(self, flux, eflux, bank, topk=1, **fit_kwargs):
         """``fit`` started from the ``topk`` templates of ``bank`` (a ``tmatch.TemplateBank`` on this fitter's ``obs_wave``) that
@@ -842,36 +860,32 @@ class OptFit(object):
         whose status is not NAN / SINGULAR is kept, the lower rank on a tie (rank 0's if none qualifies).  Returns ``fit``'s dict
         plus ``start_index`` (the template), ``start_chisq`` (its chi^2 in the search) and ``start_rank``.  A star that no template
         matches (every chi^2 NaN) keeps status NAN, NaN ``pars`` and ``start_index`` -1.  ``fit_kwargs`` go to ``fit``."""
-        if not hasattr(bank, "match") or not hasattr(bank, "obs_wave"):
+        flux, eflux = self._bank_inputs(flux, eflux, bank, "match", fit_kwargs, ("start",), "fit_from_bank takes its starts from the bank")
+        m = bank.match(flux, eflux, topk=topk)
+        N = m["index"].shape[0]
+        labels = self.labels(bool(fit_kwargs.get("fit_vrad", False)))
+        out = dict(pars=np.full((N, 8), np.nan), npix=m["npix"], labels=labels, start_index=np.full(N, -1, dtype=np.int32), **self._bank_results(N, len(labels)))
+
+        def record(dst, r):
+            out["start_index"][dst], out["start_chisq"][dst] = m["index"][dst, r], m["chisq"][dst, r]
+        return keep_best_rank(m["index"], out, ("pars", "chisq", "fisher", "status", "niter", "at_bound", "err"),
+                              lambda sel, r: self.fit(flux[sel], eflux[sel], m["pars"][sel, r], **fit_kwargs), record)
+
+    def _bank_inputs(self, flux, eflux, bank, search, kwargs, taken, message):
+        """What the ``*_from_bank`` fits check first: ``bank`` has the method ``search`` and this fitter's grid, and ``kwargs`` names
+        none of ``taken``, the arguments the bank supplies (``message`` says so).  Returns flux fp32 [N, nobs] and eflux fp64."""
+        if not hasattr(bank, search) or not hasattr(bank, "obs_wave"):
             raise TypeError("bank must be a TemplateBank")
         if np.shape(bank.obs_wave) != self.obs_wave.shape or not np.array_equal(np.asarray(bank.obs_wave), self.obs_wave):
             raise ValueError("the bank's obs_wave differs from the fitter's")
-        if "start" in fit_kwargs:
-            raise TypeError("fit_from_bank takes its starts from the bank")
-        flux = np.atleast_2d(np.asarray(flux, dtype=np.float32))
-        eflux = np.atleast_2d(np.asarray(eflux, dtype=np.float64))
-        m = bank.match(flux, eflux, topk=topk)
-        N, k = m["index"].shape
-        K = len(fitted_columns(self.n_labels, bool(fit_kwargs.get("fit_vrad", False))))
-        out = dict(pars=np.full((N, 8), np.nan), chisq=np.full(N, np.nan), npix=m["npix"], fisher=np.full((N, K, K), np.nan),
-                   status=np.full(N, _lib.LMFIT_NAN, dtype=np.int32), niter=np.zeros(N, dtype=np.int32), at_bound=np.zeros(N, dtype=np.uint32),
-                   labels=self.labels(bool(fit_kwargs.get("fit_vrad", False))), err=np.full((N, K), np.nan),
-                   start_index=np.full(N, -1, dtype=np.int32), start_chisq=np.full(N, np.inf), start_rank=np.full(N, -1, dtype=np.int32))
-        per_star = ("pars", "chisq", "fisher", "status", "niter", "at_bound", "err")
-        for r in range(k):
-            sel = np.flatnonzero(m["index"][:, r] >= 0)
-            if len(sel) == 0:
-                continue
-            res = self.fit(flux[sel], eflux[sel], m["pars"][sel, r], **fit_kwargs)
-            valid = (res["status"] != _lib.LMFIT_NAN) & (res["status"] != _lib.LMFIT_SINGULAR)
-            held = out["start_rank"][sel] >= 0
-            held_valid = held & (out["status"][sel] != _lib.LMFIT_NAN) & (out["status"][sel] != _lib.LMFIT_SINGULAR)
-            take = ~held | (valid & (~held_valid | (res["chisq"] < out["chisq"][sel])))
-            dst = sel[take]
-            for name in per_star:
-                out[name][dst] = res[name][take]
-            out["start_index"][dst], out["start_chisq"][dst], out["start_rank"][dst] = m["index"][dst, r], m["chisq"][dst, r], r
-        return out
+        if any(name in kwargs for name in taken):
+            raise TypeError(message)
+        return np.atleast_2d(np.asarray(flux, dtype=np.float32)), np.atleast_2d(np.asarray(eflux, dtype=np.float64))
+
+    @staticmethod
+    def _bank_results(N, K):
+        """``empty_results`` plus what a fit from a bank adds to them: ``err``, ``start_chisq`` and ``start_rank`` (-1: no rank yet)."""
+        return dict(empty_results(N, K), err=np.full((N, K), np.nan), start_chisq=np.full(N, np.inf), start_rank=np.full(N, -1, dtype=np.int32))
 
     def fit_binary(self, flux, eflux, start_a, start_b, ratio=0.3, tie=(), fit_vrad=True, npoly=0, coef=None, bounds=None, ratio_bounds=(0.01, 0.99),
                    vrad_step=0.25, check_every=4, timing=False, **opts):
@@ -901,119 +915,51 @@ class OptFit(object):
         anns, eng, D = Pr.anns, Pr.anns.engine, self.n_labels
         a = check_binary_args(flux, eflux, start_a, start_b, len(self.obs_wave), D, anns.xmin, anns.xmax, ratio=ratio, tie=tie, fit_vrad=fit_vrad, npoly=npoly,
                               coef=coef, bounds=bounds, ratio_bounds=ratio_bounds, vrad_step=vrad_step, check_every=check_every, **opts)
-        from .contfit import ContinuumFit, abscissa
-        torch = eng.torch
+        from .contfit import abscissa
+        torch, dev = eng.torch, eng.device
         flux, eflux, start_a, start_b, q0, coef, o = a["flux"], a["eflux"], a["start_a"], a["start_b"], a["ratio"], a["coef"], a["opts"]
         cols, Ka, Kl, P, b_pos = a["cols"], a["Ka"], a["Kl"], a["P"], a["b_pos"]
-        K = Kl + 1 + P
         N = flux.shape[0]
         start_b = start_b.copy()
         tied = [k for k in range(Ka) if b_pos[k] < Ka]
         free_b = [k for k in range(Ka) if b_pos[k] >= Ka]
         start_b[:, [cols[k] for k in tied]] = start_a[:, [cols[k] for k in tied]]
         w = weights_from_errors(eflux)
-        good = np.ones(N, dtype=bool)
-        x = abscissa(self.obs_wave) if P else None
+        cont_status = np.full(N, _lib.CONTFIT_OK, dtype=np.int32)
         if P and coef is None:
-            q_d = torch.as_tensor(q0).to(eng.device)[:, None]
+            q_d = torch.as_tensor(q0).to(dev)[:, None]
             mixed = ((1.0 - q_d) * self.model_spectra(start_a) + q_d * self.model_spectra(start_b)).to(torch.float32).contiguous()
-            c = ContinuumFit(self.obs_wave, npoly=P, device=eng.device).fit(flux, eflux, mixed, normalise=False)
-            coef, cs = c["coef"].cpu().numpy(), c["status"].cpu().numpy()
-            good = (cs == _lib.CONTFIT_OK) | (cs == _lib.CONTFIT_NONPOSITIVE)
-        out = dict(pars_a=start_a.copy(), pars_b=start_b.copy(), ratio=np.full(N, np.nan), coef=np.full((N, P), np.nan), chisq=np.full(N, np.nan),
-                   npix=(w != 0.0).sum(axis=1), fisher=np.full((N, K, K), np.nan), status=np.full(N, _lib.LMFIT_NAN, dtype=np.int32),
-                   niter=np.zeros(N, dtype=np.int32), at_bound=np.zeros(N, dtype=np.uint32), labels=list(a["names"]))
+            coef, cont_status, w = self._start_continuum(flux, eflux, mixed, P, None, w)
+        out = dict(pars_a=start_a.copy(), pars_b=start_b.copy(), ratio=np.full(N, np.nan), coef=np.full((N, P), np.nan), npix=(w != 0.0).sum(axis=1),
+                   labels=list(a["names"]), **empty_results(N, Kl + 1 + P))
         out["pars_a"][:, cols] = np.nan
         out["pars_b"][:, cols] = np.nan
-        Pr._bind(self.obs_wave)
-        step = max(1, eng.b_max // (2 * (1 + Ka + 2 * int(bool(fit_vrad)))))   # the rows a star needs, both components counted
-        sel = np.flatnonzero(good)
-        self.timing = dict(network=0.0, broadening=0.0, update=0.0, iterations=0) if timing else None
-        if len(sel):
-            handle = LMHandle(K, min(step, len(sel)), eng.device, **o)
-            x_d = torch.as_tensor(x).to(eng.device) if P else None
-            try:
-                for s in range(0, len(sel), step):
-                    idx = sel[s:s + step]
-                    x0 = np.concatenate([start_a[idx][:, cols], start_b[idx][:, [cols[k] for k in free_b]], q0[idx, None]]
-                                        + ([np.ascontiguousarray(coef[idx], dtype=np.float64)] if P else []), axis=1)
-                    res = self._fit_binary_block(handle, flux[idx], w[idx], start_a[idx], start_b[idx], x0, a, bool(fit_vrad), float(vrad_step),
-                                                 int(check_every), int(o["maxiter"]), x_d)
-                    xb = res["x_best"].cpu().numpy()
-                    st = res["status"].cpu().numpy()
-                    xb[st == _lib.LMFIT_NAN] = np.nan
-                    out["pars_a"][idx[:, None], np.asarray(cols)[None, :]] = xb[:, :Ka]
-                    out["pars_b"][idx[:, None], np.asarray(cols)[None, :]] = xb[:, b_pos]
-                    out["ratio"][idx] = xb[:, Kl]
-                    out["coef"][idx] = xb[:, Kl + 1:]
-                    out["chisq"][idx] = res["chisq"].cpu().numpy()
-                    out["fisher"][idx] = np.where((st == _lib.LMFIT_NAN)[:, None, None], np.nan, res["A"].cpu().numpy())
-                    out["status"][idx] = st
-                    out["niter"][idx] = res["niter"].cpu().numpy()
-                    out["at_bound"][idx] = res["at_bound"].cpu().numpy().astype(np.uint32)
-            finally:
-                handle.close()
-        out["chisq"][out["status"] == _lib.LMFIT_NAN] = np.nan
-        out["err"] = crlb_from_fisher(out["fisher"])
-        return out
+        x_d = torch.as_tensor(abscissa(self.obs_wave)).to(dev) if P else None
+        b_lab = torch.as_tensor(b_pos[:D]).to(dev)                    # where B's labels sit in x_trial: a tied one is A's
 
-    def _fit_binary_block(self, handle, flux, w, start_a, start_b, x0, a, fit_vrad, vrad_step, check_every, maxiter, x):
-        """One block of stars of ``fit_binary`` through the handle: the theta blocks hold A's rows, then B's."""
-        Pr = self.predictor
-        eng, D, jac_net = Pr.anns.engine, self.n_labels, Pr._jacobian()
-        torch = eng.torch
-        nb, nobs, Ka, P = flux.shape[0], flux.shape[1], a["Ka"], a["P"]
-        dev = eng.device
-        flux_d = torch.as_tensor(np.ascontiguousarray(flux)).to(dev)
-        w_d = torch.as_tensor(np.ascontiguousarray(w)).to(dev)
-        handle.begin(x0, a["lo"], a["hi"])
-        xt = handle.trial()
-        b_lab = torch.as_tensor(a["b_pos"][:D]).to(dev)               # where B's labels sit in x_trial: a tied one is A's
-        th = np.full((2 * nb, eng.ncols), np.nan)
-        th[:nb, :8], th[nb:, :8] = start_a, start_b
-        th_y = torch.as_tensor(th).to(dev)
-        th_j = th_y.repeat_interleave(D, dim=0)
-        th_pm = th_y.repeat(2, 1) if fit_vrad else None
-        rows = torch.empty((2, nb, 1 + Ka, nobs), dtype=torch.float32, device=dev)
-        rv = rows.view(2 * nb, 1 + Ka, nobs)
-        tm = self.timing
-        marks = []
+        def block(handle, idx):
+            nb = len(idx)
+            x0 = np.concatenate([start_a[idx][:, cols], start_b[idx][:, [cols[k] for k in free_b]], q0[idx, None]]
+                                + ([np.ascontiguousarray(coef[idx], dtype=np.float64)] if P else []), axis=1)
 
-        def mark():
-            if tm is not None:
-                ev = torch.cuda.Event(enable_timing=True)
-                ev.record(torch.cuda.current_stream(dev))
-                marks.append(ev)
-        it = 0
-        while it < maxiter:
-            it += 1
-            mark()
-            y, jac = jac_net.eval(torch.cat([xt[:, :D], xt.index_select(1, b_lab)], dim=0))
-            mark()
-            if fit_vrad:
-                v = torch.cat([xt[:, D], xt[:, int(a["b_pos"][D])]])
-                th_y[:, 4] = v
-                th_j[:, 4] = v.repeat_interleave(D)
-                th_pm[:2 * nb, 4] = v + vrad_step
-                th_pm[2 * nb:, 4] = v - vrad_step
-                pm = eng.smooth_batch(y.repeat(2, 1), th_pm, stage=2)
-                rv[:, Ka] = (pm[:2 * nb] - pm[2 * nb:]) / (2.0 * vrad_step)
-            rv[:, 0] = eng.smooth_batch(y, th_y, stage=2)
-            rv[:, 1:1 + D] = smooth_rows(eng, jac.reshape(2 * nb * D, -1), th_j, 2).reshape(2 * nb, D, nobs)
-            mark()
-            handle.update_pair(rows[0], rows[1], flux_d, w_d, a["ia"], a["ib"], P, x)
-            mark()
-            if it % check_every == 0 and not bool((handle.status() == _lib.LMFIT_RUNNING).any().item()):
-                break
-        res = handle.result()
-        if tm is not None:
-            torch.cuda.synchronize(dev)
-            steps = ("network", "broadening", "update")
-            for i in range(0, len(marks), len(steps) + 1):
-                for j, name in enumerate(steps):
-                    tm[name] += marks[i + j].elapsed_time(marks[i + j + 1])
-            tm["iterations"] += it
-        return res
+            def update(rows, flux_d, w_d, mark):
+                handle.update_pair(rows[:nb], rows[nb:], flux_d, w_d, a["ia"], a["ib"], P, x_d)
+            return x0, np.concatenate([start_a[idx], start_b[idx]]), update
+
+        def place(idx, xb):
+            out["pars_a"][idx[:, None], np.asarray(cols)[None, :]] = xb[:, :Ka]
+            out["pars_b"][idx[:, None], np.asarray(cols)[None, :]] = xb[:, b_pos]
+            out["ratio"][idx] = xb[:, Kl]
+            out["coef"][idx] = xb[:, Kl + 1:]
+
+        def labels_of(xt):
+            return torch.cat([xt[:, :D], xt.index_select(1, b_lab)], dim=0)
+
+        def vrad_of(xt):
+            return torch.cat([xt[:, D], xt[:, int(b_pos[D])]])
+        # the theta blocks and the rows hold A's stars, then B's; a block's size counts both components
+        return self._fit_blocks(out, self._with_continuum(cont_status), flux, w, a["lo"], a["hi"], o, block, place, cols=cols, fit_vrad=fit_vrad,
+                                vrad_step=vrad_step, check_every=check_every, timing=timing, nc=2, labels_of=labels_of, vrad_of=vrad_of, nan_results=True)
 
     def fit_binary_from_bank(self, flux, eflux, bank, topk=1, primaries=4, **fit_binary_kwargs):
         """``fit_binary`` started from the ``topk`` pairs of templates of ``bank`` that fit each star best with both amplitudes free
@@ -1026,15 +972,8 @@ class OptFit(object):
         one-template-and-scale chi^2 of the same pixels: what ``chisq`` has to beat for the star to count as a binary).  A star
         without a pair keeps status NAN, NaN parameters and ``start_index_a`` -1.  ``fit_binary_kwargs`` go to ``fit_binary``; with
         ``npoly`` = 0 the model has no scale, so the spectra must be normalised."""
-        if not hasattr(bank, "match_pairs") or not hasattr(bank, "obs_wave"):
-            raise TypeError("bank must be a TemplateBank")
-        if np.shape(bank.obs_wave) != self.obs_wave.shape or not np.array_equal(np.asarray(bank.obs_wave), self.obs_wave):
-            raise ValueError("the bank's obs_wave differs from the fitter's")
-        for name in ("start_a", "start_b", "ratio", "coef"):
-            if name in fit_binary_kwargs:
-                raise TypeError("fit_binary_from_bank takes its starts, ratio and coefficients from the bank")
-        flux = np.atleast_2d(np.asarray(flux, dtype=np.float32))
-        eflux = np.atleast_2d(np.asarray(eflux, dtype=np.float64))
+        flux, eflux = self._bank_inputs(flux, eflux, bank, "match_pairs", fit_binary_kwargs, ("start_a", "start_b", "ratio", "coef"),
+                                        "fit_binary_from_bank takes its starts, ratio and coefficients from the bank")
         N = flux.shape[0]
         kw = dict(fit_binary_kwargs)
         rb = kw.get("ratio_bounds", (0.01, 0.99))
@@ -1044,30 +983,18 @@ class OptFit(object):
                               ratio=0.5 * (rb[0] + rb[1]), **kw)
         K = a["Kl"] + 1 + P
         m = bank.match_pairs(flux, eflux, topk=topk, primaries=primaries)
-        k = m["index_a"].shape[1]
-        out = dict(pars_a=np.full((N, 8), np.nan), pars_b=np.full((N, 8), np.nan), ratio=np.full(N, np.nan), coef=np.full((N, P), np.nan),
-                   chisq=np.full(N, np.nan), npix=m["npix"], fisher=np.full((N, K, K), np.nan), status=np.full(N, _lib.LMFIT_NAN, dtype=np.int32),
-                   niter=np.zeros(N, dtype=np.int32), at_bound=np.zeros(N, dtype=np.uint32), labels=list(a["names"]), err=np.full((N, K), np.nan),
-                   start_index_a=np.full(N, -1, dtype=np.int32), start_index_b=np.full(N, -1, dtype=np.int32), start_chisq=np.full(N, np.inf),
-                   start_rank=np.full(N, -1, dtype=np.int32), single_chisq=m["single_chisq"])
-        per_star = ("pars_a", "pars_b", "ratio", "coef", "chisq", "fisher", "status", "niter", "at_bound", "err")
-        for r in range(k):
-            sel = np.flatnonzero(m["index_a"][:, r] >= 0)
-            if len(sel) == 0:
-                continue
+        out = dict(pars_a=np.full((N, 8), np.nan), pars_b=np.full((N, 8), np.nan), ratio=np.full(N, np.nan), coef=np.full((N, P), np.nan), npix=m["npix"],
+                   labels=list(a["names"]), start_index_a=np.full(N, -1, dtype=np.int32), start_index_b=np.full(N, -1, dtype=np.int32),
+                   single_chisq=m["single_chisq"], **self._bank_results(N, K))
+
+        def fit_rank(sel, r):
             if P:
                 kw["coef"] = np.concatenate([m["scale"][sel, r][:, None], np.zeros((len(sel), P - 1))], axis=1)
-            res = self.fit_binary(flux[sel], eflux[sel], m["pars_a"][sel, r], m["pars_b"][sel, r], ratio=np.clip(m["ratio"][sel, r], rb[0], rb[1]), **kw)
-            valid = (res["status"] != _lib.LMFIT_NAN) & (res["status"] != _lib.LMFIT_SINGULAR)
-            held = out["start_rank"][sel] >= 0
-            held_valid = held & (out["status"][sel] != _lib.LMFIT_NAN) & (out["status"][sel] != _lib.LMFIT_SINGULAR)
-            take = ~held | (valid & (~held_valid | (res["chisq"] < out["chisq"][sel])))
-            dst = sel[take]
-            for name in per_star:
-                out[name][dst] = res[name][take]
-            out["start_index_a"][dst], out["start_index_b"][dst] = m["index_a"][dst, r], m["index_b"][dst, r]
-            out["start_chisq"][dst], out["start_rank"][dst] = m["chisq"][dst, r], r
-        return out
+            return self.fit_binary(flux[sel], eflux[sel], m["pars_a"][sel, r], m["pars_b"][sel, r], ratio=np.clip(m["ratio"][sel, r], rb[0], rb[1]), **kw)
+
+        def record(dst, r):
+            out["start_index_a"][dst], out["start_index_b"][dst], out["start_chisq"][dst] = m["index_a"][dst, r], m["index_b"][dst, r], m["chisq"][dst, r]
+        return keep_best_rank(m["index_a"], out, ("pars_a", "pars_b", "ratio", "coef", "chisq", "fisher", "status", "niter", "at_bound", "err"), fit_rank, record)
 
     def fit_joint_from_bank(self, flux, eflux, bank, npoly=4, topk=1, **fit_joint_kwargs):
         """``fit_joint`` started from the ``topk`` templates of ``bank`` that match each star best under a free continuum
@@ -1077,39 +1004,18 @@ class OptFit(object):
         rank on a tie (rank 0's if none qualifies).  Returns ``fit_joint``'s dict plus ``start_index``, ``start_chisq`` and
         ``start_rank``; a star that no template matches keeps status NAN, NaN ``pars`` and ``start_index`` -1.
         ``fit_joint_kwargs`` go to ``fit_joint``."""
-        if not hasattr(bank, "match") or not hasattr(bank, "obs_wave"):
-            raise TypeError("bank must be a TemplateBank")
-        if np.shape(bank.obs_wave) != self.obs_wave.shape or not np.array_equal(np.asarray(bank.obs_wave), self.obs_wave):
-            raise ValueError("the bank's obs_wave differs from the fitter's")
-        for name in ("start", "coef"):
-            if name in fit_joint_kwargs:
-                raise TypeError("fit_joint_from_bank takes its starts and coefficients from the bank")
+        flux, eflux = self._bank_inputs(flux, eflux, bank, "match", fit_joint_kwargs, ("start", "coef"),
+                                        "fit_joint_from_bank takes its starts and coefficients from the bank")
         if isinstance(npoly, bool) or int(npoly) != npoly or not (1 <= int(npoly) <= _lib.TMATCH_MAX_POLY):
             raise ValueError("npoly must be 1 .. %d, got %r" % (_lib.TMATCH_MAX_POLY, npoly))
         P = int(npoly)
-        flux = np.atleast_2d(np.asarray(flux, dtype=np.float32))
-        eflux = np.atleast_2d(np.asarray(eflux, dtype=np.float64))
         m = bank.match(flux, eflux, topk=topk, npoly=P)
-        N, k = m["index"].shape
-        fit_vrad = bool(fit_joint_kwargs.get("fit_vrad", False))
-        K = len(fitted_columns(self.n_labels, fit_vrad)) + P
-        out = dict(pars=np.full((N, 8), np.nan), chisq=np.full(N, np.nan), npix=m["npix"], fisher=np.full((N, K, K), np.nan),
-                   status=np.full(N, _lib.LMFIT_NAN, dtype=np.int32), niter=np.zeros(N, dtype=np.int32), at_bound=np.zeros(N, dtype=np.uint32),
-                   labels=self.labels(fit_vrad) + ["pc_%d" % j for j in range(P)], err=np.full((N, K), np.nan), coef=np.full((N, P), np.nan),
-                   cont_status=np.full(N, _lib.CONTFIT_OK, dtype=np.int32),
-                   start_index=np.full(N, -1, dtype=np.int32), start_chisq=np.full(N, np.inf), start_rank=np.full(N, -1, dtype=np.int32))
-        per_star = ("pars", "chisq", "npix", "fisher", "status", "niter", "at_bound", "err", "coef", "cont_status")
-        for r in range(k):
-            sel = np.flatnonzero(m["index"][:, r] >= 0)
-            if len(sel) == 0:
-                continue
-            res = self.fit_joint(flux[sel], eflux[sel], m["pars"][sel, r], npoly=P, coef=m["coef"][sel, r], **fit_joint_kwargs)
-            valid = (res["status"] != _lib.LMFIT_NAN) & (res["status"] != _lib.LMFIT_SINGULAR)
-            held = out["start_rank"][sel] >= 0
-            held_valid = held & (out["status"][sel] != _lib.LMFIT_NAN) & (out["status"][sel] != _lib.LMFIT_SINGULAR)
-            take = ~held | (valid & (~held_valid | (res["chisq"] < out["chisq"][sel])))
-            dst = sel[take]
-            for name in per_star:
-                out[name][dst] = res[name][take]
-            out["start_index"][dst], out["start_chisq"][dst], out["start_rank"][dst] = m["index"][dst, r], m["chisq"][dst, r], r
-        return out
+        N = m["index"].shape[0]
+        labels = self.labels(bool(fit_joint_kwargs.get("fit_vrad", False))) + ["pc_%d" % j for j in range(P)]
+        out = dict(pars=np.full((N, 8), np.nan), npix=m["npix"], labels=labels, coef=np.full((N, P), np.nan), cont_status=np.full(N, _lib.CONTFIT_OK, dtype=np.int32),
+                   start_index=np.full(N, -1, dtype=np.int32), **self._bank_results(N, len(labels)))
+
+        def record(dst, r):
+            out["start_index"][dst], out["start_chisq"][dst] = m["index"][dst, r], m["chisq"][dst, r]
+        return keep_best_rank(m["index"], out, ("pars", "chisq", "npix", "fisher", "status", "niter", "at_bound", "err", "coef", "cont_status"),
+                              lambda sel, r: self.fit_joint(flux[sel], eflux[sel], m["pars"][sel, r], npoly=P, coef=m["coef"][sel, r], **fit_joint_kwargs), record)
